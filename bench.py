@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — sessions/sec of TCAR training (BASELINE.json metric), one JSON line per run.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config globo|adressa|mind|stress10m]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config globo|adressa|mind|stress10m] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps), times the K steps and prints the JSON line: `value`, `ms_per_step` and the step's
+description; every figure below that takes runs of its own (the secondary loop, the event-timed roofline pass, ms_per_step_by_T,
+the CPU baseline, the trainer-loop epoch, the gather roofline) is measured only with `--full` and is null otherwise.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): `loss` [B] of that step, every
+variable except the item table after its update, and `item_emb_rows`, a fixed seeded sample of the item table's rows
+(dump_outputs below).  The inputs depend on the arguments only (seeded), so two builds can be compared output for output.
 
 N > 1: when the process is not already a rank of a torch.distributed.run job (WORLD_SIZE unset) it STARTS one as a child
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`)
@@ -217,6 +224,28 @@ def bucket_batch(fold, T, B, K, rng):
     return {k: np.ascontiguousarray(v).astype(np.int32) for k, v in b.items()}
 
 
+DUMP_ITEM_ROWS = 8192        # rows of the item table in --dump-outputs (a fixed sample: the whole table is 46 MB at N = 46,033)
+
+
+def dump_outputs(eng, loss, out_dir):
+    """What the last timed step handed its caller — the per-session loss and the updated variables — as float32 .npy files.
+    The item table is sampled (DUMP_ITEM_ROWS rows of the reference's [N + 1, H] table, drawn once from a fixed seed); every
+    other variable is written whole in the reference's shape ('/' in a name becomes '.')."""
+    import torch
+    eng.flush()
+    eng.check_forks()
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"loss": loss.float().cpu().numpy()}
+    for name, v in eng._unpack_arena(eng.W.cpu().numpy()).items():
+        out["var." + name.replace("/", ".")] = v
+    g = eng.geo
+    rows = np.sort(np.random.RandomState(1234).choice(g.N, min(g.N, DUMP_ITEM_ROWS), replace=False))   # row r + 1 of item_emb
+    out["item_emb_rows"] = eng.E[torch.as_tensor(rows, device=eng.E.device), :g.H].cpu().numpy()
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float32))
+    return sorted(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -260,7 +289,17 @@ def main():
     ap.add_argument("--launch_check", action="store_true",
                     help="only the rank launch + the three collectives of the exchanges on tiny tensors (dp.preflight): with "
                          "--backend gloo on CPU (tests/), with nccl on the GPUs; prints n_gpus and the backend / RCCL versions")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the secondary loop, the event-timed roofline pass, "
+                         "ms_per_step_by_T, the CPU baseline, the trainer-loop epoch and the gather roofline (each still subject to "
+                         "its --no_* switch); a plain run times the headline loop only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (loss, updated variables, a fixed sample of the "
+                         "item table's rows) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps and the result line — nothing that takes runs of its own
+        args.no_cpu_baseline = args.no_e2e = args.no_kernel_timing = args.no_by_T = args.no_gather_roofline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))           # before any import of torch: this process never initialises a GPU
@@ -391,16 +430,19 @@ def main():
     src = None if cfg["neg_mode"] == "uniform" else (fold.neighbor_dict() if cfg["neg_mode"] == "neighbor" else fold.impression_dict(fold.train))
     ds = DeviceSampler(eng, fold.train, cfg["neg_mode"], src, fold.item_dict, seed=2020 + rank)
     sched = lambda first, n: [batch_ids[(first + i) % len(batch_ids)] for i in range(n)]
+    last = {}                                    # the loss the last timed step returned (--dump-outputs)
 
     def run(n, first, sampler_in_loop):
+        loss = None
         if sampler_in_loop:
             ds.plan(sched(first, n))
             for bt in ds.planned(K, cfg["gap_mode"]):
-                eng.train_step(None, bt=bt, **defer)
+                loss = eng.train_step(None, bt=bt, **defer)
         else:
             for i in range(n):
-                eng.train_step(None, bt=resident[(first + i) % len(resident)], **defer)
+                loss = eng.train_step(None, bt=resident[(first + i) % len(resident)], **defer)
         eng.flush()                              # K steps contain exactly K updates
+        return loss                              # (the last step's: a view of the engine's buffer, valid until its next step)
 
     def timed(sampler_in_loop):
         import gc
@@ -421,10 +463,10 @@ def main():
             torch.cuda._sleep(int(args.stall_ms * 1e-3 * 2.0e9))        # (~2 GHz shader clock: the length is approximate)
         if sampler_in_loop:
             for bt in ds.planned(K, cfg["gap_mode"]):
-                eng.train_step(None, bt=bt, **defer)
+                last["loss"] = eng.train_step(None, bt=bt, **defer)
             eng.flush()
         else:
-            run(args.steps, args.warmup, False)
+            last["loss"] = run(args.steps, args.warmup, False)
         t_enq = time.perf_counter() - t0         # host time to enqueue every step (the loop never synchronises)
         sync()
         dt = time.perf_counter() - t0
@@ -445,6 +487,8 @@ def main():
     dt, t_enq = timed(headline_sampler)
     eng.check_forks()                          # (raises if a flag fork's poll ever timed out: the measurement would be void)
     last_loss = float(eng.loss[:B].mean())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, last["loss"], args.dump_outputs)       # before any later pass overwrites the step's results
     dt_ev = None
     if not args.no_kernel_timing:
         # kernel timing: a SECOND pass of the same K steps with HIP events around the three scoring GEMMs and the projection

@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of environment settings: every argument is one setting ("VAR=1 OTHER=0" or "" for the defaults); the default
 # bench runs ROUNDS times per setting, interleaved.  Usage: tools/ab.sh 3 "" "TCAR_FUSED_Q=0"
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/.."
 ROUNDS=$1; shift
 for r in $(seq $ROUNDS); do
   for s in "$@"; do

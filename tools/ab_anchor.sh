@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the anchored softmax form (TCAR_FUSED_CE = 2, default) against the group-maximum form + rescale pass (1): interleaved rounds of
 # the default bench on ONE box; results -> gpurun_out/r06_ab_anchor.txt
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/.."
 python -c "import __graft_entry__ as g; g.build()" 2>&1 | tail -1
 mkdir -p gpurun_out
 out=gpurun_out/r06_ab_anchor.txt; : > $out

@@ -12,7 +12,7 @@
 #   head                       tools/head_bench.py                        -> <tag>_head_bench.txt
 #   py:<script and args>       any python tool                            -> <tag>_py.log (appended)
 #   sh:<command line>          any shell command (e.g. a tools/micro binary)  -> <tag>_sh.log (appended)
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 tag=$1; shift
 for step in "$@"; do
@@ -27,6 +27,7 @@ for step in "$@"; do
     bench)
       name=${rest%%:*}; args=${rest#*:}; [ "$args" == "$rest" ] && args=""; [ -z "$name" ] && name=default
       envs=""; while [[ "$args" =~ ^([A-Z_0-9]+=[^ ]*)\ ?(.*)$ ]]; do envs="$envs ${BASH_REMATCH[1]}"; args="${BASH_REMATCH[2]}"; done
+      args="--full $args"        # the whole record: secondary loop, roofline pass, by-T times, CPU baseline, trainer loop
       env $envs python bench.py $args > gpurun_out/${tag}_bench_${name}.json 2> gpurun_out/${tag}_bench_${name}.err
       python - <<PY
 import json
@@ -49,6 +50,7 @@ PY
       done; done ;;
     trace)
       envs=""; while [[ "$rest" =~ ^([A-Z_0-9]+=[^ ]*)\ ?(.*)$ ]]; do envs="$envs ${BASH_REMATCH[1]}"; rest="${BASH_REMATCH[2]}"; done
+      rest="--full $rest"        # the traced run keeps its event-timed second pass
       ( cd /tmp && export TMPDIR=/tmp $envs && timeout 400 rocprofv3 --kernel-trace --stats -d $OLDPWD/gpurun_out/prof_${tag} -o tr -- python3 $OLDPWD/bench.py --steps 200 --warmup 20 --no_cpu_baseline --no_e2e --no_by_T $rest > $OLDPWD/gpurun_out/${tag}_trace.log 2>&1 )
       db=$(ls gpurun_out/prof_${tag}/*/tr_results.db gpurun_out/prof_${tag}/tr_results.db 2>/dev/null | head -1)
       python tools/kstats.py $db gpurun_out/${tag}_kernel_stats.csv > gpurun_out/${tag}_kernel_stats.txt

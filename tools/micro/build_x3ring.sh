@@ -4,7 +4,7 @@
 # `build_x3ring.sh deep`: instead, long-K launches of at most 256 workgroups take 128-deep stages (tcar_fixed::x3_deep = 1).
 # `build_x3ring.sh bwdhi`: instead, the session-side backward GEMMs contract plain bf16 operands (tcar_fixed::bwd_small_hi = 1).
 set -e
-cd ${GRAFT_REPO_ROOT:-/root/repo}
+cd "$(dirname "$0")/../.."
 python -c "import sys; sys.path.insert(0, '.'); import tcar_amd; from tcar_amd import _lib; _lib.build()"
 C=session-based-news-recommendation_amd/csrc
 F="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -fno-slp-vectorize"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC passes over the embedding gather's throughput form (gather_clip_fwd_big_kernel) at 655,360 rows: FETCH_SIZE and WRITE_SIZE in
 # separate runs, kernel-trace only (MI355X_MICROARCH.md, HBM / rocprofv3); packed into gpurun_out/pmc_gather_fwd.json
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for SET in "FETCH_SIZE" "WRITE_SIZE"; do
   OUT=$ROOT/gpurun_out/pmc_gather_$SET
@@ -11,7 +11,7 @@ for SET in "FETCH_SIZE" "WRITE_SIZE"; do
 done
 python3 - <<PY
 import json, os
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = "$ROOT"
 f = json.load(open(root + "/gpurun_out/pmc_gather_FETCH_SIZE.json")); w = json.load(open(root + "/gpurun_out/pmc_gather_WRITE_SIZE.json"))
 B, T = 16384, 40
 alg_r = alg_w = B * (3536.0 * T + 512)

@@ -4,7 +4,7 @@
 # (PMC_KERNEL=<substring>: the kernel to summarise when it is not gemm_bf16_kernel)
 # usage: tools/pmc_gemm.sh <fwd|fwdce|fwdce2|dx|de|dx2|de2> [nsplit=3] [iters=5]   (fwdce2 = the step's form: one-hot time segment)
 MODE=$1; NS=${2:-3}; IT=${3:-5}
-ROOT=${GRAFT_REPO_ROOT:-/root/repo}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for SET in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "TCC_HIT_sum TCC_MISS_sum"; do
   TAG=$(echo $SET | cut -d' ' -f1)

@@ -4,7 +4,7 @@ HBM bytes per launch = FETCH_SIZE x 2 + WRITE_SIZE (KB counters; gfx950 reports 
 MI355X_MICROARCH.md, HBM section; WRITE_SIZE is exact)."""
 import json, os, sys
 mode, ns = sys.argv[1], int(sys.argv[2])
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N, B, EK = int(os.environ.get("GB_N", 46033)), 512, 832
 Npad = (N + 127) // 128 * 128
 tag = {"fwd": "score_fwd", "fwdce": "score_fwd_ce_classic", "fwdce2": "score_fwd_ce", "dx": "score_dx", "de": "score_dE",
