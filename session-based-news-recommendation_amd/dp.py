@@ -31,6 +31,7 @@ after step 3) while the item block is still on the wire.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Callable, Dict, Optional
 
 import numpy as np
@@ -42,57 +43,192 @@ from ._lib import check
 from .engine import SLOT, TcarEngine
 
 
-class GradExchange:
+class _GroupOps:
+    """The process group behind the three calls of rccl.RcclComm (`Collectives.ops`, the known-answer check)."""
+
+    def __init__(self, group):
+        self.group = group
+
+    def all_gather(self, send: torch.Tensor, recv: torch.Tensor):
+        dist.all_gather_into_tensor(recv.view(-1), send.reshape(-1), group=self.group)
+
+    def reduce_scatter(self, send: torch.Tensor, recv: torch.Tensor):
+        dist.reduce_scatter_tensor(recv, send, group=self.group)
+
+    def all_reduce(self, t: torch.Tensor):
+        dist.all_reduce(t, group=self.group)
+
+
+class Collectives:
+    """The collectives of both exchanges (`GradExchange` below, `sharded.ShardExchange`: each is this layer plus its schedule),
+    issued one way for both: `ops` is the direct RCCL communicator (rccl.py, on torch's current stream) or the process group.
+    Every decision the exchanges need is taken here:
+      collective   a live group of more than one rank, or `force` (TCAR_FORCE_COLLECTIVES=1: a group of ONE rank still issues
+                   every collective of the schedule, with identity results); otherwise every collective short-circuits
+      world, rank  the group's; arguments may set them only where no collective runs
+      sim          the shapes of a `world`-rank job and no collective: every all-gather repeats the local rows, the reduce-scatter
+                   keeps the first slice.  None: TCAR_SIM_WORLD=W on ONE process without a process group (rank 0 of W; the
+                   per-rank compute of a large job on one GPU, results meaningless beyond their shapes)
+      direct       None: RCCL directly on the nccl backend unless TCAR_RCCL_DIRECT=0; False: the process group; True: required
+      reduce_scatter   None: where the backend has one (nccl); otherwise all-reduce + slice
+    Collectives issued with a key are counted for bench.py and the tests: `order`, `bytes_moved`, and with `timing` on (never in a
+    headline pass: an event pair costs its stream a few us) a span per call — CUDA events on the issuing stream, host seconds on
+    CPU — averaged by collective_ms()."""
+
+    def __init__(self, group=None, world: Optional[int] = None, rank: Optional[int] = None, sim: Optional[bool] = False,
+                 reduce_scatter: Optional[bool] = None, force: Optional[bool] = None, direct: Optional[bool] = None):
+        live = dist.is_available() and dist.is_initialized()
+        if sim is None:
+            w = int(os.environ.get("TCAR_SIM_WORLD", "0")) if not live and world is None else 0
+            sim = w > 1
+            if sim:
+                world, rank = w, 0
+        self.group, self.sim = group, bool(sim)
+        self.world = world if world is not None else (dist.get_world_size(group) if live else 1)
+        self.rank = rank if rank is not None else (dist.get_rank(group) if live else 0)
+        if force is None:
+            force = bool(int(os.environ.get("TCAR_FORCE_COLLECTIVES", "0") or 0))
+        self.collective = live and not self.sim and (self.world > 1 or bool(force))
+        self.backend = dist.get_backend(group) if self.collective else "none"
+        if self.collective and (self.world, self.rank) != (dist.get_world_size(group), dist.get_rank(group)):
+            # (the reduce-scatter fallback slices, and the in-place item-row all-gather sends from, slot `rank`: RCCL's
+            #  sendbuff == recvbuff + rank * count holds only for the communicator's own rank, which is the group's)
+            raise ValueError("rank %d of %d, but the process group has this process as rank %d of %d"
+                             % (self.rank, self.world, dist.get_rank(group), dist.get_world_size(group)))
+        self.use_reduce_scatter = (self.backend == "nccl") if reduce_scatter is None else bool(reduce_scatter)
+        # RCCL called directly adds no stream beside the four the step keeps busy (why that matters: rccl.py).  make_direct is a
+        # collective: every rank of an nccl group calls it, also one whose `direct` / TCAR_RCCL_DIRECT says no (it votes no)
+        self.direct = None
+        if self.collective and self.backend == "nccl":
+            from . import rccl
+            self.direct = rccl.make_direct(group, want=direct is not False and os.environ.get("TCAR_RCCL_DIRECT", "1") != "0")
+            if direct is True and self.direct is None:
+                raise RuntimeError("the direct RCCL path was required and could not be built")
+        self.ops = self.direct if self.direct is not None else _GroupOps(group)
+        self.bytes_moved: Dict[str, int] = {}
+        self.order = []
+        self.timing = False
+        self._times: Dict[str, list] = {}
+        self._pending_rows = None
+
+    def close(self):
+        """Destroy the direct communicator (idempotent) once every collective issued on it has finished (the engines' close()
+        synchronises first).  A collective issued afterwards goes to the destroyed communicator (an RCCL error), never silently to
+        the process group."""
+        if self.direct is not None:
+            self.direct.destroy()
+
+    def _timed(self, key, t, fn, *args, **kw):
+        """issue collective fn(*args, **kw) and, when timing is on, bracket it (for an async collective: the issue only)"""
+        if not self.timing or key is None:
+            return fn(*args, **kw)
+        if t.is_cuda:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(*args, **kw)
+            e1.record()
+            self._times.setdefault(key, []).append((e0, e1))
+        else:
+            import time
+            t0 = time.perf_counter()
+            out = fn(*args, **kw)
+            self._times.setdefault(key, []).append((t0, time.perf_counter()))
+        return out
+
+    def _note(self, key, t):
+        if key is not None:
+            self.bytes_moved[key] = t.numel() * t.element_size()
+            self.order.append(key)
+
+    def collective_ms(self) -> Dict[str, float]:
+        """mean milliseconds per collective over the timed steps (call after a device synchronise)"""
+        out = {}
+        for key, spans in self._times.items():
+            if not spans:
+                continue
+            if isinstance(spans[0][0], float):
+                out[key] = round(1e3 * sum(b - a for a, b in spans) / len(spans), 4)
+            else:
+                out[key] = round(sum(a.elapsed_time(b) for a, b in spans) / len(spans), 4)
+        return out
+
+    def all_gather(self, t: torch.Tensor, key: Optional[str] = None) -> torch.Tensor:
+        """[..] -> [W, ..] (rank-major); no collective: a view (sim: W copies)"""
+        if self.sim:
+            return t.unsqueeze(0).expand((self.world,) + tuple(t.shape)).contiguous()
+        if not self.collective:
+            return t.unsqueeze(0)
+        out = torch.empty((self.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+        self._timed(key, t, self.ops.all_gather, t.contiguous(), out)
+        self._note(key, out)
+        return out
+
+    def reduce_scatter_rows(self, full: torch.Tensor, cap: int, key: Optional[str] = None) -> torch.Tensor:
+        """sum over the ranks of full [W*cap, C]; returns this rank's rows [cap, C]"""
+        if not self.collective:
+            return full[:cap]
+        self._note(key, full)
+        if self.use_reduce_scatter:
+            out = torch.empty(cap, full.shape[1], dtype=full.dtype, device=full.device)
+            self._timed(key, full, self.ops.reduce_scatter, full.contiguous(), out)
+            return out
+        self._timed(key, full, self.ops.all_reduce, full)     # gloo (CPU tests, single-GPU dry runs): all-reduce + slice
+        return full[self.rank * cap:(self.rank + 1) * cap]
+
+    def all_reduce(self, t: torch.Tensor, key: Optional[str] = None) -> torch.Tensor:
+        """in-place sum over the ranks (direct: asserts contiguity — an in-place collective on a copy would be lost)"""
+        if self.collective:
+            self._timed(key, t, self.ops.all_reduce, t)
+            self._note(key, t)
+        return t
+
+    def share_rows(self, stage: torch.Tensor, install) -> None:
+        """the item-row all-gather: `stage` [W, S, ldh] holds this rank's updated rows in slot `rank`; issued asynchronously —
+        wait_rows() calls `install(stage)` to copy the gathered table into place once it has landed"""
+        if not self.collective:
+            return
+        mine = stage[self.rank].reshape(-1)
+        if self.direct is not None:
+            # on the step's own stream: nothing of this rank runs between the update and the next step's gathers, which need the
+            # rows anyway — a side stream would buy no overlap and cost a hardware queue (rccl.py).  IN PLACE: this rank's rows
+            # already sit in their slot of the gathered table (RCCL: sendbuff == recvbuff + rank * sendcount), no staging copy
+            work = self._timed("item_rows (issue)", stage, self.direct.all_gather, mine, stage.view(-1))
+        else:
+            mine = mine.clone()
+            work = self._timed("item_rows (issue)", stage, dist.all_gather_into_tensor, stage.view(-1), mine, group=self.group,
+                               async_op=True)
+        self._note("item_rows", stage)
+        self._pending_rows = (work, stage, install, mine)
+
+    def wait_rows(self) -> None:
+        if self._pending_rows is not None:
+            work, stage, install, _ = self._pending_rows
+            self._pending_rows = None
+            if work is not None:
+                work.wait()                   # NCCL: orders the current stream behind the collective, no host block
+            install(stage)
+
+
+class GradExchange(Collectives):
     """The collective schedule above, independent of where the local pieces come from."""
 
     def __init__(self, group=None, force=None, direct=None):
-        import os
-        self.group = group
-        live = dist.is_available() and dist.is_initialized()
-        self.world = dist.get_world_size(group) if live else 1
-        # force (TCAR_FORCE_COLLECTIVES=1): a process group of ONE rank still issues every collective (identity results) — the
-        # calls, streams and staging buffers of an N-rank job on the one GPU there is
-        if force is None:
-            force = bool(int(os.environ.get("TCAR_FORCE_COLLECTIVES", "0") or 0))
-        self.collective = live and (self.world > 1 or bool(force))
-        # RCCL directly on the issuing stream instead of through the process group (rccl.py; sharded.ShardExchange has the account)
-        self.direct = None
-        if self.collective and dist.get_backend(group) == "nccl" and direct is not False:
-            from . import rccl
-            got = rccl.make_direct(group, n=1)
-            self.direct = got[0] if got else None
-            if direct is True and self.direct is None:
-                raise RuntimeError("the direct RCCL path was required and could not be built")
+        super().__init__(group, force=force, direct=direct)
 
     def communicate(self, big: torch.Tensor, arena_pieces: torch.Tensor, ids: torch.Tensor, rows: torch.Tensor,
                     big_done: bool = False):
         """Every collective of the step, in ONE canonical order on every rank (also the ranks whose shard is empty):
         all-reduce big (1) -> all-gather ids, rows (5) -> all-reduce arena (3).  None of them depends on another one's
         result, so a caller may issue them back to back on a communication stream.  `big_done`: (1) was already issued."""
-        g = self.group
         if not self.collective:
             return ids.reshape(-1), rows.reshape(-1, rows.shape[-1])
-        d = self.direct
         if not big_done:
             for part in (big if isinstance(big, (list, tuple)) else (big,)):
                 self.all_reduce(part)                                       # 1  (parts in the caller's canonical order)
-        all_ids = torch.empty((self.world,) + tuple(ids.shape), dtype=ids.dtype, device=ids.device)
-        all_rows = torch.empty((self.world,) + tuple(rows.shape), dtype=rows.dtype, device=rows.device)
-        if d is not None:
-            d.all_gather(ids.reshape(-1).contiguous(), all_ids.view(-1))    # 5
-            d.all_gather(rows.reshape(-1).contiguous(), all_rows.view(-1))
-        else:
-            dist.all_gather_into_tensor(all_ids.view(-1), ids.reshape(-1).contiguous(), group=g)      # 5
-            dist.all_gather_into_tensor(all_rows.view(-1), rows.reshape(-1).contiguous(), group=g)
+        all_ids = self.all_gather(ids)                                      # 5
+        all_rows = self.all_gather(rows)
         self.all_reduce(arena_pieces)                                       # 3
         return all_ids.view(-1), all_rows.view(-1, rows.shape[-1])
-
-    def all_reduce(self, t: torch.Tensor):
-        """in-place sum over the ranks on torch's CURRENT stream (direct RCCL) / through the process group"""
-        if self.direct is not None:
-            self.direct.all_reduce(t)                  # (asserts contiguity: an in-place collective on a copy would be lost)
-        else:
-            dist.all_reduce(t, group=self.group)
 
     @staticmethod
     def finish(all_ids: torch.Tensor, all_rows: torch.Tensor, sqnorm_item: Callable[[], None],
@@ -111,12 +247,41 @@ class GradExchange:
         self.finish(all_ids, all_rows, sqnorm_item, cand_time_bwd, scatter_rows, sqnorm_dense)
 
 
+def known_answers(ops, world: int, rank: int, dev) -> Optional[str]:
+    """ONE tiny in-place all-reduce, all-gather and reduce-scatter (the three collectives the exchanges use) through `ops` — the
+    process group (`preflight`) or a direct communicator (rccl.make_direct) — on `dev`, then the results of those issued against
+    their known answers (every rank issues all three first: a wrong answer stops no rank short of its peers' collectives).  Returns
+    None, or "<collective>: <what went wrong>" for the first that answered wrongly, else for the one that raised."""
+    t = torch.full((4,), float(rank + 1), device=dev)
+    mine, out = torch.full((3,), float(rank), device=dev), torch.empty(world * 3, device=dev)
+    full, part = torch.arange(world * 2, dtype=torch.float32, device=dev) + rank, torch.empty(2, device=dev)
+    step, err = "all_reduce", None
+    try:
+        ops.all_reduce(t)
+        step = "all_gather"
+        ops.all_gather(mine, out)
+        step = "reduce_scatter"
+        ops.reduce_scatter(full, part)
+        step = "synchronize"
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+    except Exception as e:
+        err = "%s: %s: %s" % (step, type(e).__name__, e)
+    for name, got, want in (("all_reduce", t, [world * (world + 1) / 2.0] * 4),
+                            ("all_gather", out.view(world, 3)[:, 0], [float(r) for r in range(world)]),
+                            ("reduce_scatter", part, [world * (2 * rank + j) + world * (world - 1) / 2.0 for j in range(2)])):
+        if err is not None and name == step:
+            break
+        if got.tolist() != want:
+            return "%s: returned %r, expected %r" % (name, got.tolist(), want)
+    return err
+
+
 def preflight(group=None, device=None, verbose: bool = True) -> Dict[str, object]:
-    """First contact with the process group: ONE tiny all_gather_into_tensor, reduce_scatter_tensor and all_reduce (the three
-    collectives the two exchanges use) on `device`, checked against their known answers, before any large buffer exists.  A job
-    whose collectives cannot run fails HERE with the backend, world size, device and library versions in the message instead
-    of inside step 1.  Returns the capabilities ({"reduce_scatter": bool, ...}); `reduce_scatter` False (gloo has none) makes
-    ShardedEngine reduce dX with an all-reduce."""
+    """First contact with the process group: `known_answers` through it on `device`, before any large buffer exists.  A job whose
+    collectives cannot run fails HERE with the backend, world size, device and library versions in the message instead of inside
+    step 1.  Returns the capabilities ({"reduce_scatter": bool, ...}); `reduce_scatter` False (a backend without one: reported,
+    not fatal) makes ShardedEngine reduce dX with an all-reduce."""
     import sys
     if not (dist.is_available() and dist.is_initialized()):
         return {"world": 1, "backend": "none", "reduce_scatter": False}
@@ -129,36 +294,12 @@ def preflight(group=None, device=None, verbose: bool = True) -> Dict[str, object
             info["rccl"] = ".".join(str(x) for x in torch.cuda.nccl.version())
     except Exception as e:                                   # version query only: never fatal
         info["rccl"] = "unknown (%s)" % type(e).__name__
-    step = "all_reduce"
-    try:
-        t = torch.full((4,), float(rank + 1), device=dev)
-        dist.all_reduce(t, group=group)
-        want = world * (world + 1) / 2.0
-        if not bool((t == want).all()):
-            raise RuntimeError("all_reduce returned %r, expected %r" % (t.tolist(), want))
-        step = "all_gather_into_tensor"
-        mine = torch.full((3,), float(rank), device=dev)
-        out = torch.empty(world * 3, device=dev)
-        dist.all_gather_into_tensor(out, mine, group=group)
-        if out.view(world, 3)[:, 0].tolist() != [float(r) for r in range(world)]:
-            raise RuntimeError("all_gather_into_tensor returned %r" % out.tolist())
-        step = "reduce_scatter_tensor"
-        try:
-            full = torch.arange(world * 2, dtype=torch.float32, device=dev) + rank
-            part = torch.empty(2, device=dev)
-            dist.reduce_scatter_tensor(part, full, group=group)
-            exp = [world * (2 * rank + j) + world * (world - 1) / 2.0 for j in range(2)]
-            if part.tolist() != exp:
-                raise RuntimeError("reduce_scatter_tensor returned %r, expected %r" % (part.tolist(), exp))
-            info["reduce_scatter"] = True
-        except (RuntimeError, NotImplementedError) as e:
-            if backend == "nccl":
-                raise
-            info["reduce_scatter_error"] = "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:120])
-        if dev.type == "cuda":
-            torch.cuda.synchronize(dev)
-    except Exception as e:
-        raise RuntimeError("collective preflight failed at %s (%s): %s: %s" % (step, info, type(e).__name__, e)) from e
+    bad = known_answers(_GroupOps(group), world, rank, dev)
+    if bad is not None and (backend == "nccl" or not bad.startswith("reduce_scatter:")):
+        raise RuntimeError("collective preflight failed at %s (%s)" % (bad, info))
+    info["reduce_scatter"] = bad is None
+    if bad is not None:
+        info["reduce_scatter_error"] = bad.splitlines()[0][:120]
     if verbose and rank == 0:
         print("[tcar] collective preflight ok: %s" % info, file=sys.stderr)
     return info
@@ -180,14 +321,13 @@ class DPEngine(TcarEngine):
     flag_forks = False   # (the gradient exchange is enqueued inside the fused backward: event forks)
 
     def __init__(self, *a, group=None, force_collectives=None, direct_rccl=None, **kw):
-        import os
-        live = dist.is_available() and dist.is_initialized()
-        fc = force_collectives if force_collectives is not None else bool(int(os.environ.get("TCAR_FORCE_COLLECTIVES", "0") or 0))
-        if live and (dist.get_world_size(group) > 1 or fc):
-            self.priority_stream = False          # (TcarEngine.priority_stream: no priority stream beside live collectives)
-        super().__init__(*a, **kw)
         self.group = group
         self.xch = GradExchange(group, force=force_collectives, direct=direct_rccl)
+        if self.xch.collective:
+            # (TcarEngine.priority_stream: no priority stream beside live collectives.  One that an earlier engine of this process
+            #  made current stays current: restoring the default stream is left for later)
+            self.priority_stream = False
+        super().__init__(*a, **kw)
         g = self.geo
         # step 1 in two parts, the candidate-time block FIRST: its clip backward can then run (into a scratch copy of the
         # time-table gradients) while the item block is still being reduced
@@ -195,6 +335,12 @@ class DPEngine(TcarEngine):
         self._ct_rows = 139 * g.ldt
         self._ct_scratch = torch.zeros(self._ct_rows + _lib.NSLOT, dtype=torch.float32, device=self.dev)
         self.rows_cap = 0
+
+    def close(self):
+        """Synchronise the device, then destroy the direct RCCL communicator (idempotent).  Call it before
+        destroy_process_group(): nothing destroys the communicator at interpreter exit."""
+        torch.cuda.synchronize(self.dev)
+        self.xch.close()
 
     def _ensure_rows(self, rows: int):
         if rows > self.rows_cap:
@@ -357,15 +503,10 @@ def make_dp_engine(params, content_emb, mwdhm, device="cuda:0", group=None, scor
     """Data-parallel engine factory.  mode "replica": every rank holds the whole catalog and the dense item gradient is
     all-reduced (`DPEngine`); "sharded": catalog-sharded scoring (`sharded.ShardedEngine`, ~1/8 of the bytes); "auto"
     picks the sharded exchange when there is more than one rank."""
+    from .sharded import ShardedEngine       # (here: sharded.py builds on this module)
     world = dist.get_world_size(group) if (dist.is_available() and dist.is_initialized()) else 1
     if mode == "auto":
-        if world > 1 and scoring != "f32":
-            from . import sharded  # noqa: F401  (sets _HAVE_SHARDED)
-        mode = "sharded" if (world > 1 and _HAVE_SHARDED and scoring != "f32") else "replica"
+        mode = "sharded" if (world > 1 and scoring != "f32") else "replica"
     if mode == "sharded":
-        from .sharded import ShardedEngine
         return ShardedEngine(params, content_emb, mwdhm, device=device, group=group, scoring=scoring, **kw)
     return DPEngine(params, content_emb, mwdhm, device=device, group=group, scoring=scoring, **kw)
-
-
-_HAVE_SHARDED = False        # flipped by sharded.py once the catalog-sharded engine is in place

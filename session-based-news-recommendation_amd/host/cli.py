@@ -174,6 +174,7 @@ def main(argv=None):
         model.test(None, sent, a)
     if dp_group is not None:
         import torch.distributed as dist
+        model.engine.close()                     # the direct RCCL communicator, before the group it was built through
         dist.destroy_process_group()
     return model
 

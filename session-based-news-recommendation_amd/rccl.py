@@ -8,11 +8,10 @@ world-1 communicator.  `ncclAllGather` / `ncclReduceScatter` / `ncclAllReduce` i
 stream-ordered behind the kernels that produced their input and in front of the kernels that read their output, no event, no hop
 (and one C call each: ~10 us of host time against ~30 through the process group).
 
-The communicator is built once per exchange from a `ncclUniqueId` that rank 0 creates and `torch.distributed` broadcasts (the
-process group stays the rendezvous and the fallback: `selftest()` runs the three collectives on tiny tensors against their known
-answers on every rank, and the exchanges fall back to the process group — on ALL ranks, agreed through the group — if the direct
-path cannot be built or answers wrongly).  `librccl.so` is the copy bundled with PyTorch-ROCm (the one the `nccl` backend itself
-uses), so both paths share one RCCL.
+The communicator is built once per exchange (dp.Collectives) from a `ncclUniqueId` that rank 0 creates and `torch.distributed`
+broadcasts: the process group stays the rendezvous and the fallback — `make_direct` agrees through it, on ALL ranks, whether the
+direct path is taken.  `librccl.so` is the copy bundled with PyTorch-ROCm (the one the `nccl` backend itself uses), so both paths
+share one RCCL.
 
 Not a compatibility layer: RCCL is the only backend this talks to."""
 from __future__ import annotations
@@ -114,55 +113,53 @@ class RcclComm:
         _ck(self._lib.ncclAllReduce(C.c_void_p(t.data_ptr()), C.c_void_p(t.data_ptr()), t.numel(), _DT[t.dtype], op, self.comm,
                                     self._st(stream)), "ncclAllReduce")
 
-    def selftest(self) -> bool:
-        """the three collectives on tiny tensors against their known answers (as dp.preflight does through the process group)"""
-        w, r, dev = self.world, self.rank, self.dev
-        t = torch.full((4,), float(r + 1), device=dev)
-        self.all_reduce(t)
-        mine = torch.full((3,), float(r), device=dev)
-        out = torch.empty(w * 3, device=dev)
-        self.all_gather(mine, out)
-        full = torch.arange(w * 2, dtype=torch.float32, device=dev) + r
-        part = torch.empty(2, device=dev)
-        self.reduce_scatter(full, part)
-        torch.cuda.synchronize(dev)
-        ok = bool((t == w * (w + 1) / 2.0).all()) and out.view(w, 3)[:, 0].tolist() == [float(i) for i in range(w)] and \
-            part.tolist() == [w * (2 * r + j) + w * (w - 1) / 2.0 for j in range(2)]
-        return ok
-
     def destroy(self):
         if getattr(self, "comm", None) is not None and self.comm.value:
             self._lib.ncclCommDestroy(self.comm)
             self.comm = C.c_void_p()
 
 
-def make_direct(group=None, device=None, n: int = 1, verbose: bool = True):
-    """`n` direct communicators for the ranks of `group`, or None when the direct path is switched off (TCAR_RCCL_DIRECT=0), the
-    backend is not RCCL, or any rank fails to build / verify it — the decision is all-reduced through the process group so that
-    every rank takes the same path."""
-    if os.environ.get("TCAR_RCCL_DIRECT", "1") == "0":
-        return None
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_backend(group) != "nccl":
-        return None
-    comms, err = [], None
+def _local_check(want: bool) -> Optional[str]:
+    """What this rank can tell on its own: None when the direct path may be tried, else why not."""
+    if not want:
+        return "switched off"
     try:
-        for _ in range(n):
-            comms.append(RcclComm(group, device))
-        good = all(c.selftest() for c in comms)
-    except Exception as e:                    # (construction is collective: a rank that fails here has already left the others
-        good, err = False, e                  #  inside ncclCommInitRank — they time out there; nothing this function can mend)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    flag = torch.tensor([1 if good else 0], device=dev, dtype=torch.int32)
+        _lib()                                # librccl.so loads and every symbol it binds resolves
+    except Exception as e:
+        return "%s: %s" % (type(e).__name__, e)
+    return None
+
+
+def _agree(ok: bool, group, dev) -> bool:
+    """True on every rank when `ok` holds on every rank (a MIN all-reduce through the process group)."""
+    flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
     dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=group)
-    if int(flag.item()) != 1:
-        if verbose:
-            import sys
-            print("[tcar] direct RCCL path unavailable (%s): collectives through torch.distributed" % (err or "self-test mismatch"),
-                  file=sys.stderr)
-        for c in comms:
-            try:
-                c.destroy()
-            except Exception:
-                pass
-        return None
-    return comms
+    return int(flag.item()) == 1
+
+
+def make_direct(group=None, device=None, want: bool = True, verbose: bool = True) -> Optional[RcclComm]:
+    """ONE direct communicator over the ranks of `group` (nccl backend), or None — on EVERY rank: a collective call that every rank
+    makes, also one that does not `want` the direct path (TCAR_RCCL_DIRECT=0, direct=False: it votes no).  Two agreements through
+    the process group: the first, before any rank broadcasts an id or enters ncclCommInitRank, over what each rank can check alone
+    (`want`, librccl.so and its symbols); the second over the communicator's known answers (dp.known_answers).
+    Not handled (left for later): a rank that fails or hangs INSIDE the id broadcast or ncclCommInitRank leaves its peers there —
+    that needs a watchdog or the non-blocking ncclCommInitRankConfig."""
+    from .dp import known_answers
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    err = _local_check(want)
+    comm = None
+    if _agree(err is None, group, dev):
+        try:
+            comm = RcclComm(group, dev)
+            err = known_answers(comm, comm.world, comm.rank, dev)
+        except Exception as e:
+            err = "%s: %s" % (type(e).__name__, e)
+        if _agree(err is None, group, dev):
+            return comm
+    if verbose and want:
+        import sys
+        print("[tcar] direct RCCL path unavailable (%s): collectives through torch.distributed" % (err or "on another rank"),
+              file=sys.stderr)
+    if comm is not None:
+        comm.destroy()
+    return None

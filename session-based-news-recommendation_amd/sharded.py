@@ -38,7 +38,6 @@ from typing import Dict, Optional
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _lib, dp
 from ._lib import Batch, Dims, GemmDesc, Segments, check
@@ -50,7 +49,7 @@ def shard_rows(n_items: int, world: int):
     return _ru((n_items + world - 1) // world, 128)
 
 
-class ShardExchange:
+class ShardExchange(dp.Collectives):
     """The collective schedule of the catalog-sharded step, independent of where the local pieces come from (the engine binds
     them to the HIP entry points; tests/test_sharded_gloo.py drives the SAME schedule over gloo on CPU tensors with fp64
     torch pieces).  Every rank — also one whose shard of the batch is empty — issues the same six collectives in the same
@@ -66,141 +65,6 @@ class ShardExchange:
     Collective 6 is issued asynchronously: nothing of the step that follows needs the other shards' rows before its session
     gathers, so `wait_rows()` is called at the top of the next step (and by every other reader of the item table)."""
 
-    def __init__(self, group=None, world: Optional[int] = None, rank: Optional[int] = None, sim: bool = False,
-                 reduce_scatter: Optional[bool] = None, force: Optional[bool] = None, direct: Optional[bool] = None):
-        live = dist.is_available() and dist.is_initialized()
-        self.group = group
-        self.world = world if world is not None else (dist.get_world_size(group) if live else 1)
-        self.rank = rank if rank is not None else (dist.get_rank(group) if live else 0)
-        self.sim = sim
-        # force (TCAR_FORCE_COLLECTIVES=1): a process group of ONE rank still issues every collective of the schedule — the code
-        # an N-rank job runs (RCCL calls, their stream, the staging copies), with identity results.  Default: a single rank
-        # short-circuits them.
-        if force is None:
-            force = bool(int(os.environ.get("TCAR_FORCE_COLLECTIVES", "0") or 0))
-        self.collective = live and not sim and (self.world > 1 or bool(force))
-        self.backend = dist.get_backend(group) if self.collective else "none"
-        # RCCL called directly on the step's OWN stream (rccl.py) instead of through the process group.  Not for the host time of a
-        # call (measured: 10 us against ~30) but for the STREAMS: ProcessGroupNCCL runs every collective on a stream of its own, and
-        # the step already keeps four busy (main, aux, third, the sampler's).  HIP multiplexes streams onto 4 hardware queues by
-        # default; with a fifth, two of them share a queue and — which two depends on creation order — the step ran at 1.6-1.9 ms
-        # instead of 0.65-0.73 (profiles/r06_ab_experiments.txt, GPU_MAX_HW_QUEUES = 4 / 6 / 8 / 12).  Direct calls add NO stream:
-        # every collective, also the item-row all-gather of collective 6, is issued on the stream the step runs on.  `direct`: None
-        # = default (on for the nccl backend, TCAR_RCCL_DIRECT=0 switches it off), False = process group, True = required.
-        self.direct = None
-        if self.collective and self.backend == "nccl" and direct is not False:
-            from . import rccl
-            self.direct = rccl.make_direct(group, n=1)
-            if direct is True and self.direct is None:
-                raise RuntimeError("the direct RCCL path was required and could not be built")
-        self.use_reduce_scatter = (self.backend == "nccl") if reduce_scatter is None else bool(reduce_scatter)
-        self.bytes_moved: Dict[str, int] = {}
-        self.order = []                 # names of the collectives in issue order (tests)
-        self._pending_rows = None
-        # optional per-collective timing (bench.py's second, event-instrumented pass; never in the headline pass: an event pair
-        # costs its stream a few us): key -> list of (start, end) — CUDA events on the issuing stream, or host seconds on CPU
-        self.timing = False
-        self._times: Dict[str, list] = {}
-
-    def _timed(self, key, t, fn):
-        """run collective `fn` and, when timing is on, bracket it (for an async collective: the issue only)"""
-        if not self.timing:
-            return fn()
-        if t.is_cuda:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            self._times.setdefault(key, []).append((e0, e1))
-        else:
-            import time
-            t0 = time.perf_counter()
-            out = fn()
-            self._times.setdefault(key, []).append((t0, time.perf_counter()))
-        return out
-
-    def collective_ms(self) -> Dict[str, float]:
-        """mean milliseconds per collective over the timed steps (call after a device synchronise)"""
-        out = {}
-        for key, spans in self._times.items():
-            if not spans:
-                continue
-            if isinstance(spans[0][0], float):
-                out[key] = round(1e3 * sum(b - a for a, b in spans) / len(spans), 4)
-            else:
-                out[key] = round(sum(a.elapsed_time(b) for a, b in spans) / len(spans), 4)
-        return out
-
-    def _note(self, key, t):
-        self.bytes_moved[key] = t.numel() * t.element_size()
-        self.order.append(key)
-
-    def allgather(self, t: torch.Tensor, key: str) -> torch.Tensor:
-        """[..] -> [W, ..] (rank-major); world 1: a view"""
-        if self.sim:
-            return t.unsqueeze(0).expand((self.world,) + tuple(t.shape)).contiguous()
-        if not self.collective:
-            return t.unsqueeze(0)
-        out = torch.empty((self.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
-        if self.direct is not None:
-            self._timed(key, t, lambda: self.direct[0].all_gather(t.contiguous(), out))
-        else:
-            self._timed(key, t, lambda: dist.all_gather_into_tensor(out.view(-1), t.reshape(-1).contiguous(), group=self.group))
-        self._note(key, out)
-        return out
-
-    def reduce_scatter_rows(self, full: torch.Tensor, cap: int, key: str) -> torch.Tensor:
-        """sum over the ranks of full [W*cap, C]; returns this rank's rows [cap, C]"""
-        if not self.collective:
-            return full[:cap]
-        self._note(key, full)
-        if self.direct is not None:
-            out = torch.empty(cap, full.shape[1], dtype=full.dtype, device=full.device)
-            self._timed(key, full, lambda: self.direct[0].reduce_scatter(full.contiguous(), out))
-            return out
-        if self.use_reduce_scatter:
-            out = torch.empty(cap, full.shape[1], dtype=full.dtype, device=full.device)
-            self._timed(key, full, lambda: dist.reduce_scatter_tensor(out, full, group=self.group))
-            return out
-        self._timed(key, full, lambda: dist.all_reduce(full, group=self.group))     # gloo (CPU tests, single-GPU dry runs) has no reduce-scatter
-        return full[self.rank * cap:(self.rank + 1) * cap]
-
-    def allreduce(self, t: torch.Tensor, key: str) -> torch.Tensor:
-        if self.collective:
-            if self.direct is not None:
-                self._timed(key, t, lambda: self.direct[0].all_reduce(t))
-            else:
-                self._timed(key, t, lambda: dist.all_reduce(t, group=self.group))
-            self._note(key, t)
-        return t
-
-    def share_rows(self, stage: torch.Tensor, install) -> None:
-        """collective 6: `stage` [W, S, ldh] holds this rank's updated rows in slot `rank`; `install(stage)` copies the gathered
-        table into place once the collective has landed (wait_rows)"""
-        if not self.collective:
-            return
-        if self.direct is not None:
-            # on the step's own stream: nothing of this rank runs between the update and the next step's gathers, which need the
-            # rows anyway — a side stream would buy no overlap and cost a hardware queue (see __init__).  IN PLACE: this rank's rows
-            # already sit in their slot of the gathered table (RCCL: sendbuff == recvbuff + rank * sendcount), no staging copy
-            mine = stage[self.rank].reshape(-1)
-            self._timed("item_rows (issue)", stage, lambda: self.direct[0].all_gather(mine, stage.view(-1)))
-            work = None
-        else:
-            mine = stage[self.rank].reshape(-1).clone()
-            work = self._timed("item_rows (issue)", stage,
-                               lambda: dist.all_gather_into_tensor(stage.view(-1), mine, group=self.group, async_op=True))
-        self._note("item_rows", stage)
-        self._pending_rows = (work, stage, install, mine)
-
-    def wait_rows(self) -> None:
-        if self._pending_rows is not None:
-            work, stage, install, _ = self._pending_rows
-            self._pending_rows = None
-            if work is not None:
-                work.wait()                   # NCCL: orders the current stream behind the collective, no host block
-            install(stage)
-
     def step(self, pieces, cap: int, update: bool) -> None:
         """one training step; `pieces` supplies the local compute between the exchanges:
              begin() -> head [cap, ld]             score(head_all [W*cap, ld]) -> stats [W*cap, 3]
@@ -212,16 +76,16 @@ class ShardExchange:
         self.order = []
         self.wait_rows()
         head = pieces.begin()
-        head_all = self.allgather(head, "attout+labels+negatives").view(self.world * cap, -1)
+        head_all = self.all_gather(head, "attout+labels+negatives").view(self.world * cap, -1)
         stats = pieces.score(head_all)
-        stats_all = self.allgather(stats, "softmax_stats")
+        stats_all = self.all_gather(stats, "softmax_stats")
         dx_full = pieces.backward(stats_all)
         pieces.finish()
         dx_rows = self.reduce_scatter_rows(dx_full, cap, "dX")
         rows = pieces.session_backward(dx_rows)
-        all_rows = self.allgather(rows, "rows+ids").view(-1, rows.shape[-1])
+        all_rows = self.all_gather(rows, "rows+ids").view(-1, rows.shape[-1])
         pieces.scatter(all_rows)
-        self.allreduce(pieces.arena(), "arena")
+        self.all_reduce(pieces.arena(), "arena")
         pieces.norms()
         if update:
             out = pieces.update()
@@ -324,37 +188,28 @@ class ShardedEngine(TcarEngine):
         if scoring == "f32":
             raise ValueError("the catalog-sharded step runs the split-bf16 scoring modes (use mode='replica' for f32)")
         self.group = group
-        live = dist.is_available() and dist.is_initialized()
-        self.world = world if world is not None else (dist.get_world_size(group) if live else 1)
-        self.dp_rank = rank if rank is not None else (dist.get_rank(group) if live else 0)
-        # TCAR_SIM_WORLD=W on ONE process without a process group (tools, bench.py with TCAR_FORCE_DP=1): the shapes of rank 0
-        # of a W-rank job — every "all-gather" repeats the local rows W times, the reduce-scatter keeps the first slice — to
-        # time the per-rank compute of a large job on one GPU.  Results are meaningless beyond their shapes.
-        self._sim = False
-        if not live and world is None and int(os.environ.get("TCAR_SIM_WORLD", "0")) > 1:
-            self.world, self.dp_rank, self._sim = int(os.environ["TCAR_SIM_WORLD"]), 0, True
+        # the collective schedule; its layer (dp.Collectives) decides world, rank (TCAR_SIM_WORLD included) and how collectives run
+        self.xch = ShardExchange(group, world, rank, sim=None, force=force_collectives, direct=direct_rccl)
+        self.world, self.dp_rank = self.xch.world, self.xch.rank
         self._mwdhm_full = np.asarray(mwdhm)
         N = content_emb.shape[0] - 1
         self.S = shard_rows(N, self.world)
         n0 = min(N, self.dp_rank * self.S)
         nl = max(0, min(N, n0 + self.S) - n0)
         if nl <= 0:
+            self.xch.close()
             raise ValueError("more ranks than 128-row catalog blocks")
         # dX of a shard contracts over N / W catalog rows for W * B sessions: W times more output tiles and a W times shorter
         # K than the single-rank GEMM, so the split that fills the chip (and the slab bytes it writes) shrinks with W
         if "splitk" not in kw and "TCAR_SPLITK" not in os.environ:
             kw["splitk"] = max(2, -(-36 // self.world))
-        if force_collectives is None:
-            force_collectives = bool(int(os.environ.get("TCAR_FORCE_COLLECTIVES", "0") or 0))
-        if live and not self._sim and (self.world > 1 or force_collectives):
+        if self.xch.collective:
             self.priority_stream = False          # (TcarEngine.priority_stream: no priority stream beside live collectives)
         super().__init__(params, content_emb, mwdhm, lr=lr, max_grad=max_grad, neg_weight=neg_weight, device=device,
                          scoring=scoring, shard=(n0, nl), **kw)
         self.n0, self.nl = n0, nl
         self.nlpad = _ru(nl, 128)
         self.n_local_items = nl
-        # the collective schedule (device-agnostic; dX is reduce-scattered where the backend can — RCCL — and all-reduced over gloo)
-        self.xch = ShardExchange(group, self.world, self.dp_rank, sim=self._sim, force=force_collectives, direct=direct_rccl)
         self.backend = self.xch.backend
         if self.xch.collective and self.tune is None and not os.environ.get("TCAR_SHARD_ALL_FLAGS"):
             # Flag forks whose PRODUCER sits behind a collective: the gather behind the item-row all-gather of the
@@ -368,6 +223,8 @@ class ShardedEngine(TcarEngine):
         self.bytes_moved = self.xch.bytes_moved
 
     # ------------------------------------------------------------------------------------------ collectives
+    close = dp.DPEngine.close          # synchronise, then destroy the direct RCCL communicator (idempotent)
+
     def exchange_info(self) -> Dict[str, object]:
         g = self.geo
         return {"mode": "sharded", "world": self.world, "shard_rows": self.S,
@@ -463,7 +320,8 @@ class ShardedEngine(TcarEngine):
         ShardExchange.step; the pieces between them are the C entry points of csrc/step.hip (`_Pieces`).  lr_pending >= 0 (one
         rank): the previous step's update is owed and rides in tcar_shard_begin as the split update of the single-GPU step.
         A rank that exchanges nothing (one rank, no live collectives) makes ONE call: tcar_shard_step_local sequences the same
-        pieces in C++ (round 6: the Python sequencing was ~0.2 ms of host time per step)."""
+        pieces in C++ (round 6: the Python sequencing was ~0.2 ms of host time per step).  With live collectives the step stays
+        sequenced here; one C call that is handed the communicator is left for later."""
         g = self.geo
         B = bt.B if bt is not None else 0
         cap = max(cap, B, 1)
@@ -479,7 +337,7 @@ class ShardedEngine(TcarEngine):
         refresh = 0 if self.onehot else int(self._time_dirty)
         ctx, sctx = self._ctx(), self._shard_ctx()
         sh = self._shard_desc(cap)
-        if (bt is not None and not self.xch.collective and not self._sim and self.world == 1 and getattr(self, "_tm", None) is None
+        if (bt is not None and not self.xch.collective and self.world == 1 and getattr(self, "_tm", None) is None
                 and not os.environ.get("TCAR_SHARD_PY_STEP")):
             sh.att_all, sh.ld_att, sh.head_K = self.head_loc.data_ptr(), self.ld_head, K
             lr_u = -1.0
@@ -568,15 +426,14 @@ class ShardedEngine(TcarEngine):
         if self._pending_lr is not None:
             lr, self._pending_lr = self._pending_lr, None
             check(self.lib.tcar_step_update(C.byref(self._shard_ctx()), lr, self._stream()), "tcar_step_update")
-        if getattr(self, "xch", None) is not None:
-            self.xch.wait_rows()
+        self.xch.wait_rows()
 
     @property
     def can_defer(self) -> bool:
         """the split (deferred) update of the single-GPU step applies when this rank owns the whole table and nothing is exchanged
         behind the update: ONE rank.  With more ranks the owned rows must reach the other ranks before their next gather, so the
         update (1 / world of the table) stays inside its step."""
-        return self.world == 1 and not self._sim and not self.xch.collective and self.overlap and hasattr(self, "adam_bitmap")
+        return self.world == 1 and not self.xch.collective and self.overlap and hasattr(self, "adam_bitmap")
 
     # ------------------------------------------------------------------------------------------- public API
     score_batch = property(lambda self: self.world * max(self.cap, 1))
@@ -662,10 +519,9 @@ class ShardedEngine(TcarEngine):
         """this rank's [nl, ldh] rows of a candidate-side table -> the whole [N + 1, H] table in the reference's shape (row 0
         = the pad row, zero).  A COLLECTIVE: every rank calls it."""
         g = self.geo
-        full = torch.zeros(self.world, self.S, g.ldh, dtype=torch.float32, device=self.dev)
-        full[self.dp_rank, :self.nl] = local
-        if self.xch.collective:
-            dist.all_gather_into_tensor(full.view(-1), full[self.dp_rank].reshape(-1).clone(), group=self.group)
+        mine = torch.zeros(self.S, g.ldh, dtype=torch.float32, device=self.dev)
+        mine[:self.nl] = local
+        full = self.xch.all_gather(mine)             # [W, S, ldh], rank-major
         item = np.zeros((g.N + 1, g.H), dtype=np.float32)
         item[1:] = full.view(-1, g.ldh)[:g.N, :g.H].cpu().numpy()
         return item
@@ -711,5 +567,3 @@ class ShardedEngine(TcarEngine):
         from .engine import VAR_ORDER
         return OrderedDict((k, out[k]) for k in VAR_ORDER)
 
-
-dp._HAVE_SHARDED = True

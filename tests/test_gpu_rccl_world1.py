@@ -125,6 +125,9 @@ if plain is not None:
 else:
     assert eng.async_exchanges == steps, (eng.async_exchanges, steps)     # the big all-reduce ran on the communication stream
     out["async_exchanges"] = eng.async_exchanges
+eng.close()
+eng.close()                                  # idempotent: the direct communicator is destroyed once, before the group
+assert eng.xch.direct is None or not eng.xch.direct.comm.value
 dist.barrier()
 torch.cuda.synchronize()
 dist.destroy_process_group()

@@ -202,7 +202,8 @@ def _worker(rank, world, port, ret, scoring="bf16x3", B=37):
                 d = np.abs(got[k] - want[k]).max()
                 # same kernels, different summation order (float atomics, reduction trees): Adam bound as in test_gpu_parity.  (Anchored
                 # softmax form, B = 256: the shard's anchor is one wave's dot, the single engine's eight partial dots — the two planes
-                # of exponentials are rounded to bf16 relative to slightly different references: the mixed precision's noise bound)
+                # of exponentials are rounded to bf16 relative to slightly different references: the mixed precision's noise bound;
+                # the shard writing the single engine's eight partials, and the tighter gate back, are left for later)
                 travel = 2.0 if scoring == "bf16x3-mixed" else 0.25
                 assert d <= 1e-3 * np.abs(want[k]).max() + travel * 1e-3 * 4, (k, d)
         flat = torch.cat([torch.tensor(v).reshape(-1) for v in got.values()])
