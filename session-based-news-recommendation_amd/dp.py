@@ -40,7 +40,7 @@ import torch.distributed as dist
 
 from . import _lib
 from ._lib import check
-from .engine import SLOT, TcarEngine
+from .engine import TIME_SHORT, TcarEngine
 
 
 class _GroupOps:
@@ -427,7 +427,7 @@ class DPEngine(TcarEngine):
             gr = self._grads()
             base = self._ct_scratch.data_ptr()
             o0 = self.seg["month"]["off"]
-            for k, n in enumerate(["month", "day", "week", "hour", "minute"]):
+            for k, n in enumerate(TIME_SHORT):
                 gr.g_time[k] = base + 4 * (self.seg[n]["off"] - o0)
             gr.sqn = base + 4 * self._ct_rows
             check(self.lib.tcar_cand_time_bwd_indexed(C.byref(self.dims), C.byref(self._time_ptrs()), self._p(self.inv_n),
@@ -454,7 +454,7 @@ class DPEngine(TcarEngine):
         return self._loss_view(bt)
 
     def update(self):
-        if self.native and self.timing is None:
+        if self.native:
             if self.work_B == 0:
                 # a rank whose very first shard is empty has no workspace yet: give it a minimal one, so that the update
                 # always goes through tcar_step_update (which also refreshes the bf16 planes of the item table)
@@ -467,7 +467,7 @@ class DPEngine(TcarEngine):
     def _local(self, bt):
         """forward + rank-local backward, driven from C++ (tcar_step_forward / tcar_step_backward_local)."""
         self.flush()
-        if self.native and self.timing is None:
+        if self.native:
             self._ensure_work(bt.B, bt.T)
             ctx, st = self._ctx(), self._stream()
             check(self.lib.tcar_step_forward(C.byref(ctx), C.byref(bt), int(self._time_dirty), st), "tcar_step_forward")
@@ -483,7 +483,6 @@ class DPEngine(TcarEngine):
         self._local(bt)
         self.finish_backward(bt, cap_rows)
         return self._loss_view(bt)
-
 
     def exchange_info(self) -> Dict[str, object]:
         """Bytes this rank hands to the collectives per step (bench.py prints it)."""

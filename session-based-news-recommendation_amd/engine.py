@@ -16,19 +16,22 @@ HBM layout (fp32, "padded-concat space", see include/tcar_hip.h):
 from __future__ import annotations
 
 import ctypes as C
-import functools
 import os
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Dims, GemmDesc, Grads, Segments, Tables, check
+from ._lib import Batch, Dims, Grads, Segments, Tables, check
+from .oplevel import OpLevelStep
+from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
 TIME_NAMES = ["month_embedding", "day_embedding", "week_embedding", "hour_embedding", "minute_embedding"]
+TIME_SHORT = [n[:-len("_embedding")] for n in TIME_NAMES]           # their arena names (ARENA below)
 TIME_VOCAB = [13, 32, 8, 25, 61]
+TABLE_VARS = ["dec_pos", "duration_embedding"] + TIME_NAMES          # gathered tables: IndexedSlices norm pieces only
 # TF creation order of the 23 trainable variables (model_combine.py:52-128) = squared-norm slot index
 VAR_ORDER = ["item_emb", "dec_pos"] + TIME_NAMES + ["duration_embedding",
              "multi_attention/input_linear_trans/w_3d", "multi_attention/cont_linear_trans/w_3d",
@@ -47,10 +50,6 @@ SLOT = {n: i for i, n in enumerate(VAR_ORDER)}
 # tests/test_gpu_configs.py::test_same_step_twice_bitwise_report keeps both lists honest.
 DETERMINISTIC_GRADS: tuple = tuple(VAR_ORDER)
 ATOMIC_IN_F32: tuple = tuple(n for n in VAR_ORDER if n.endswith("/b1") or n.endswith("res_linear_trans/w_3d"))
-
-
-def _ru(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 class Geometry:
@@ -129,10 +128,54 @@ def use_priority_stream(dev: torch.device) -> None:
         torch.cuda.set_stream(hp)
 
 
-class TcarEngine:
+class Switches(NamedTuple):
+    """The Python-level TCAR_* environment switches of the engines, read ONCE per engine, at construction (`Switches.read`).  (The
+    switches of tcar_tuning_t are `_lib.tuning`, those of the collectives `dp.Collectives`.)"""
+    no_prio: bool; no_overlap: bool; atomic_colsums: bool; atomic_wgrad: bool; no_onehot: bool; no_onehot_bwd: bool
+    no_ce_anchor: bool; no_stream3: bool; no_flag_fork: bool; no_fold_scratch: bool; shard_all_flags: bool
+    shard_materialised: bool; shard_py_step: bool
+    splitk: int                                   # TCAR_SPLITK (0: not set)
+
+    @classmethod
+    def read(cls) -> "Switches":
+        env = os.environ.get
+        return cls(*[bool(env("TCAR_" + f.upper())) for f in cls._fields[:-1]], splitk=int(env("TCAR_SPLITK") or 0))
+
+
+class StepForm(NamedTuple):
+    """Which optional pointers a tcar_ctx_t carries — that IS the step's algorithm: fused_ce / onehot_fwd / onehot_bwd / ce_anchored /
+    sorted_rows of csrc/step.hip are predicates over them.  Decided in one place per engine kind (TcarEngine._form)."""
+    score: ScoreForm
+    det_colsums: bool         # gw_rows: bias / residual-weight gradients as order-fixed column sums
+    wgrad_ks: int             # wgrad_slabs: rows per K split of the weight gradients, folded in split order (0: none, float atomics)
+    sorted_rows: bool         # stream2 + segsum_ws + small_det_ws: second stream, order-fixed item-row and small-table sums
+    stream3: bool; flag_forks: bool; fold_scratch: bool
+
+
+# The per-batch activations of tcar_ctx_t ("workspace"): (attribute = field, rows kind, columns, dtype, fill).  Rows kinds: "r" =
+# session-item rows B * T, "B" = sessions; columns: an attribute of Geometry, a number, None = a vector.
+WORK = ([(n, "r", c, F32, None) for n, c in (("x_icp", "ic"), ("x_pt", "pt"), ("x_act", "ldt"), ("pre1", "ldh"), ("pre2", "ldh"),
+                                             ("dx_icp", "ic"), ("dx_pt", "pt"), ("dx_act", "ldt"), ("dpre1", "ldh"), ("dpre2", "ldh"))]
+        + [("alpha", "3r", None, F32, None)]
+        + [(n, "B", c, F32, None) for n, c in (("click_t", "ct"), ("q1", "ldh"), ("q", "ic"), ("pooled", "ek"), ("attout", "ek"),
+                                               ("ce", None), ("dattout", "ek"), ("dpooled", "ek"), ("dq", "ic"), ("dq1", "ldh"),
+                                               ("gw_rows", "ic"),        # per-session d w_res rows (tcar_colsum_det)
+                                               ("dclick", "ct"))]
+        + [(n, "B", c, F32, 0) for n, c in (("neg_fb", None), ("loss", None), ("neg_coef", None), ("negpart", "ic"))]
+        + [("rank", "B", None, I32, None), ("topk", "B", 20, I32, None)])
+# tcar_ctx_t fields that take the engine attribute of the same name: parameters / optimizer state, then the workspace
+CTX_STATE = ["E", "W", "Gx", "M", "V", "big", "Mi", "Vi", "sqn_dense", "use_dense", "mwdhm", "inv_n", "inv_off", "ct_ws", "et_perm",
+             "adam_bitmap"]
+# the element-count field that goes with a pointer field
+CTX_SIZES = {"wgrad_slabs": "wgrad_slab_floats", "proj_slabs": "proj_slab_floats", "ce_ws": "ce_ws_floats", "segsum_ws": "segsum_bytes",
+             "small_det_ws": "small_det_ws_floats", "fold_scratch": "fold_scratch_words"}
+
+
+class TcarEngine(OpLevelStep):
     def __init__(self, params: Dict[str, np.ndarray], content_emb: np.ndarray, mwdhm: np.ndarray, lr: float = 1e-3,
                  max_grad: Optional[float] = 150.0, neg_weight: float = 0.01, device: str = "cuda:0",
-                 splitk: Optional[int] = None, scoring: str = "f32", shard: Optional[tuple] = None):
+                 splitk: Optional[int] = None, scoring: str = "f32", shard: Optional[tuple] = None,
+                 switches: Optional["Switches"] = None):
         """shard = (n0, n_loc): catalog-sharded data parallelism (sharded.py) — the candidate-side state (bf16 planes of E,
         dense item gradient, candidate-time block, Adam moments, inverted index) covers the catalog rows [n0, n0 + n_loc)
         only; E itself stays whole (the session-side gathers read any row)."""
@@ -141,8 +184,12 @@ class TcarEngine:
             raise _lib.TcarError("TcarEngine needs an MI355X (no CPU fallback)")
         self.dev = torch.device(device)
         self.is_cuda = self.dev.type == "cuda"
-        if self.is_cuda and self.overlap and self.native and self.priority_stream and not os.environ.get("TCAR_NO_PRIO"):
+        self.sw = sw = switches or Switches.read()
+        if self.overlap is None:
+            self.overlap = not sw.no_overlap
+        if self.is_cuda and self.overlap and self.native and self.priority_stream and not sw.no_prio:
             use_priority_stream(self.dev)
+        self.ws = Workspace(self, self.dev)
         N, H = content_emb.shape[0] - 1, content_emb.shape[1]
         Ht = params["month_embedding"].shape[1]
         self.geo = g = Geometry(N, H, Ht)
@@ -150,18 +197,10 @@ class TcarEngine:
         self.b1, self.b2, self.eps = 0.9, 0.999, 1e-8
         self.b1_pow, self.b2_pow = np.float32(self.b1), np.float32(self.b2)
         self.step = 0
-        # split-K of dX = dlogits E: 36 slabs with the 512 x 128 bf16 tile (7 N tiles x 36 = 252 workgroups), 16 in fp32
-        # split-K of the dX GEMM (bf16 modes): 18 slabs of 256 x 128 tiles = 216 workgroups at B = 512 — the same grid as 36 slabs of
-        # 512 x 128 tiles, half the slab bytes for the GEMM to write and the slab reduce to read back (round 4: -9 us per step at the
-        # Globo, Adressa and MIND shapes; 12 / 16 / 20 / 24 measured worse, profiles/r04_ab_experiments.txt)
-        # (the materialised-logits modes — bf16x3, bf16 — contract 832 columns with other tiles: 36 stays better there, 0.649 / 0.509
-        #  against 0.671 / 0.517 ms per step)
-        # (catalogs from 2^20 rows: 64 slabs — the dX GEMM then takes its 256 x 384 tile, 44 % fewer fill bytes per flop, and 64 slabs of
-        #  [B, 672] are noise beside a contraction that long: 10 M items 13.7 -> 7.2 ms, profiles/r06_ab_experiments.txt)
+        # split-K of dX = dlogits E (slabs + reduce): 16 in fp32; 18 in the mixed mode (64 from 2^20 catalog rows, where the GEMM takes
+        # its 256 x 384 tile); 36 in the materialised-logits bf16 modes (profiles/r04_ab_experiments.txt, r06_ab_experiments.txt)
         big_catalog = int(np.asarray(content_emb).shape[0]) - 1 >= (1 << 20)
-        self.splitk = splitk if splitk else (16 if scoring == "f32" else (64 if big_catalog else 18) if scoring == "bf16x3-mixed" else 36)
-        if os.environ.get("TCAR_SPLITK"):
-            self.splitk = int(os.environ["TCAR_SPLITK"])
+        self.splitk = sw.splitk or splitk or (16 if scoring == "f32" else (64 if big_catalog else 18) if scoring == "bf16x3-mixed" else 36)
         # precision of the three full-catalog scoring GEMMs: "f32" (fp32 MFMA), "bf16x3" (split-bf16 planes, three
         # bf16 MFMAs per product, fp32-class accuracy), "bf16" (hi plane only)
         # "bf16x3-mixed": logits in bf16x3 (fp32-class), the two gradient GEMMs in plain bf16 (mixed-precision backward)
@@ -204,8 +243,8 @@ class TcarEngine:
         self.sqn_dense = torch.zeros(_lib.NSLOT, **f32)
         self.sqn_pieces = self.Gx[off:]
         use = np.ones(_lib.NSLOT, dtype=np.int32)
-        for n in ["dec_pos", "duration_embedding"] + TIME_NAMES:
-            use[SLOT[n]] = 0                      # tables: IndexedSlices pieces only
+        for n in TABLE_VARS:
+            use[SLOT[n]] = 0
         self.use_dense = torch.tensor(use, device=self.dev)
         self.mwdhm = torch.tensor(np.ascontiguousarray(np.asarray(mwdhm)[n0:n0 + nl], dtype=np.int32), device=self.dev)
         self.dims = Dims(g.N, g.H, g.Ht, g.ldh, g.ldt)
@@ -228,16 +267,12 @@ class TcarEngine:
         self.ct_ws = torch.zeros(self.lib.tcar_cand_time_ws_floats(C.byref(self.dims_cand)), **f32)
         # segment tables for the optimizer kernels
         self.segs_all = self._segments([a[0] for a in ARENA])
-        self.segs_dense = self._segments([a[0] for a in ARENA if self.use_dense_np(a[1])])
+        self.segs_dense = self._segments([a[0] for a in ARENA if a[1] not in TABLE_VARS])
         self._use_np = use
         self.load_params(params, content_emb)
-        self.work_rows = 0
-        self.work_B = 0
+        self.work_rows, self.work_B = 0, 0
         self._time_dirty = True
         self.pin = None
-
-    def use_dense_np(self, ref: str) -> bool:
-        return ref not in (["dec_pos", "duration_embedding"] + TIME_NAMES)
 
     def _segments(self, names) -> Segments:
         s = Segments()
@@ -314,19 +349,30 @@ class TcarEngine:
                 raise RuntimeError(self._FORK_MSG % n)
         self.poll_fork_errors()
 
+    def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:
+        """the [n_loc, ldh] rows this engine holds of a candidate-side table -> the whole [N + 1, H] table (row 0 = the pad row, zero)"""
+        g = self.geo
+        item = np.zeros((g.N + 1, g.H), dtype=np.float32)
+        item[1:] = local[:, :g.H].cpu().numpy()
+        return item
+
+    def _item_rows_mine(self, full: np.ndarray) -> np.ndarray:
+        """inverse: the whole [N + 1, H] table -> the [n_loc, ldh] rows this engine holds"""
+        g, (n0, nl) = self.geo, self.shard
+        it = np.zeros((nl, g.ldh), dtype=np.float32)
+        it[:, :g.H] = full[1 + n0:1 + n0 + nl]
+        return it
+
     def export_state(self) -> Dict[str, np.ndarray]:
         """Everything a resumed run needs, as plain arrays (np.savez, loadable with allow_pickle=False): the 23 variables
         `var/<name>`, the Adam moments `m/<name>`, `v/<name>` in the reference's shapes, the beta powers and the step
         count (tf.train.AdamOptimizer's beta1_power / beta2_power non-slot variables, model_combine.py:155)."""
         self.flush()
         self.check_forks()
-        g = self.geo
         out = {"var/" + k: v for k, v in self.export_params().items()}
         for tag, arena, item in (("m/", self.M, self.Mi), ("v/", self.V, self.Vi)):
             d = self._unpack_arena(arena.cpu().numpy())
-            it = np.zeros((g.N + 1, g.H), dtype=np.float32)
-            it[1:] = item[:, :g.H].cpu().numpy()
-            d["item_emb"] = it
+            d["item_emb"] = self._item_rows_full(item)
             out.update({tag + k: d[k] for k in VAR_ORDER})
         out["meta/step"] = np.asarray(self.step, dtype=np.int64)
         out["meta/beta_pow"] = np.asarray([self.b1_pow, self.b2_pow], dtype=np.float32)
@@ -335,14 +381,11 @@ class TcarEngine:
     def load_state(self, st) -> None:
         """Inverse of export_state (moments / powers / step are optional: a variables-only file restores the weights)."""
         self.load_params({k[4:]: np.asarray(st[k]) for k in st if k.startswith("var/")})
-        g = self.geo
         if all(("m/" + k) in st and ("v/" + k) in st for k in VAR_ORDER):
             for tag, arena, item in (("m/", self.M, self.Mi), ("v/", self.V, self.Vi)):
                 vals = {k: np.asarray(st[tag + k]) for k in VAR_ORDER}
                 arena.copy_(torch.from_numpy(self._pack_arena(vals)))
-                it = np.zeros((g.N, g.ldh), dtype=np.float32)
-                it[:, :g.H] = vals["item_emb"][1:]
-                item.copy_(torch.from_numpy(it))
+                item.copy_(torch.from_numpy(self._item_rows_mine(vals["item_emb"])))
         if "meta/step" in st:
             self.step = int(np.asarray(st["meta/step"]))
         if "meta/beta_pow" in st:
@@ -376,11 +419,8 @@ class TcarEngine:
 
     def export_grads(self) -> "OrderedDict[str, np.ndarray]":
         """Summed dense gradients of the last backward, reference shapes (item row 0 has no gradient)."""
-        g = self.geo
         out = self._unpack_arena(self.G.cpu().numpy())
-        item = np.zeros((g.N + 1, g.H), dtype=np.float32)
-        item[1:] = self.Gi[:, :g.H].cpu().numpy()
-        out["item_emb"] = item
+        out["item_emb"] = self._item_rows_full(self.Gi)
         return OrderedDict((k, out[k]) for k in VAR_ORDER)
 
     def export_sqnorms(self) -> Dict[str, float]:
@@ -390,51 +430,30 @@ class TcarEngine:
 
     # ------------------------------------------------------------------------------------------- workspace
     def _ensure_work(self, B: int, T: int):
-        g = self.geo
-        rows = B * T
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        if rows > self.work_rows:
-            r = rows
-            self.x_icp = torch.empty(r, g.ic, **f32)
-            self.x_pt = torch.empty(r, g.pt, **f32)
-            self.x_act = torch.empty(r, g.ldt, **f32)
-            self.pre1 = torch.empty(r, g.ldh, **f32)
-            self.pre2 = torch.empty(r, g.ldh, **f32)
-            self.alpha = torch.empty(3 * r, **f32)
-            self.dx_icp = torch.empty(r, g.ic, **f32)
-            self.dx_pt = torch.empty(r, g.pt, **f32)
-            self.dx_act = torch.empty(r, g.ldt, **f32)
-            self.dpre1 = torch.empty(r, g.ldh, **f32)
-            self.dpre2 = torch.empty(r, g.ldh, **f32)
-            self.work_rows = r
+        """the workspace covers the largest B * T and the largest B seen (WORK + the materialised part of the scoring family)"""
+        g, kinds = self.geo, ()
+        if B * T > self.work_rows:
+            self.work_rows, kinds = B * T, ("r", "3r")
         if B > self.work_B:
-            self.click_t = torch.empty(B, g.ct, **f32)
-            self.q1 = torch.empty(B, g.ldh, **f32)
-            self.q = torch.empty(B, g.ic, **f32)
-            self.pooled = torch.empty(B, g.ek, **f32)
-            self.attout = torch.empty(B, g.ek, **f32)
-            self.logits = torch.empty(B, g.Npad, **f32)
-            self.ce = torch.empty(B, **f32)
-            self.neg_fb = torch.zeros(B, **f32)
-            self.loss = torch.zeros(B, **f32)
-            self.neg_coef = torch.zeros(B, **f32)
-            self.negpart = torch.zeros(B, g.ic, **f32)
-            self.dattout = torch.empty(B, g.ek, **f32)
-            self.dpooled = torch.empty(B, g.ek, **f32)
-            self.dq = torch.empty(B, g.ic, **f32)
-            self.dq1 = torch.empty(B, g.ldh, **f32)
-            self.gw_rows = torch.empty(B, g.ic, **f32)     # per-session d w_res rows (order-fixed column sums, tcar_colsum_det)
-            self.dclick = torch.empty(B, g.ct, **f32)
-            self.slabs = torch.empty(self.splitk, B, g.ek, **f32)
-            if self.scoring_code:
-                bf = dict(dtype=torch.bfloat16, device=self.dev)
-                Bp = _ru(B, 128)
-                self.a16h, self.a16l = torch.zeros(Bp, g.ek, **bf), torch.zeros(Bp, g.ek, **bf)
-                self.ap16h, self.ap16l = torch.zeros(Bp, g.ldh + g.pt, **bf), torch.zeros(Bp, g.ldh + g.pt, **bf)
-                self.dl16h, self.dl16l = torch.zeros(Bp, g.Npad, **bf), torch.zeros(Bp, g.Npad, **bf)
-            self.rank = torch.empty(B, dtype=torch.int32, device=self.dev)
-            self.topk = torch.empty(B, 20, dtype=torch.int32, device=self.dev)
-            self.work_B = B
+            self.work_B, kinds = B, kinds + ("B",)
+        if kinds:
+            rows = {"r": self.work_rows, "3r": 3 * self.work_rows, "B": self.work_B}
+            self.ws.ensure(Spec(n, (rows[k],) if c is None else (rows[k], getattr(g, c) if isinstance(c, str) else c), dt, fill)
+                           for n, k, c, dt, fill in WORK if k in kinds)
+            if "B" in kinds:
+                self.ws.ensure(self._scoring_specs(ScoreForm(planes=bool(self.scoring_code))))
+
+    def _scoring_specs(self, form: ScoreForm) -> List[Spec]:
+        """the scoring family of this engine: work_B sessions against the WHOLE catalog (also where it owns a shard of the candidate
+        side: the one-hot forms exist only where it owns all of it); the optional buffers carry a leading underscore"""
+        plain = ("slabs", "logits", "a16h", "a16l", "ap16h", "ap16l", "dl16h", "dl16l")
+        return scoring_specs(self.geo, self.work_B, self.geo.N, self.splitk, form, lambda f: f if f in plain else "_" + f,
+                             self._fill_onehot)
+
+    def _fill_onehot(self, oh16: torch.Tensor):
+        """the static one-hot plane of publish_time_MWDHM of the candidate rows this engine owns"""
+        check(self.lib.tcar_time_onehot(C.byref(self.dims_cand), self._p(self.mwdhm), self._p(oh16), 160, self._stream()),
+              "tcar_time_onehot")
 
     # --------------------------------------------------------------------------------------------- helpers
     def _stream(self):
@@ -449,56 +468,6 @@ class TcarEngine:
 
     def _g(self, name: str):
         return C.c_void_p(self.G.data_ptr() + 4 * self.seg[name]["off"])
-
-    def gemm(self, layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, bias=None, act=0, beta=0, splitk=1, tag=None):
-        ev = self._tick(tag)
-        check(self.lib.tcar_gemm_f32(layout, M, N, K, A, lda, Bm, ldb, Cm, ldc, bias, act, beta, splitk,
-                                     self._stream()), "tcar_gemm_f32")
-        self._tock(ev)
-
-    @staticmethod
-    def desc(M, N, segs, Cm, ldc, bias=None, act=0, beta=0, splitk=1, atomic=0) -> GemmDesc:
-        """One problem of a grouped GEMM; segs = [(A, lda, B, ldb, K), ...] accumulate into one C."""
-        d = GemmDesc()
-        d.nseg = len(segs)
-        for i, (A, lda, Bm, ldb, K) in enumerate(segs):
-            d.A[i], d.lda[i], d.B[i], d.ldb[i], d.K[i] = A.value, lda, Bm.value, ldb, K
-        d.C, d.ldc, d.bias = Cm.value, ldc, (bias.value if bias is not None else None)
-        d.M, d.N, d.act, d.beta, d.splitk, d.atomic = M, N, act, beta, splitk, atomic
-        return d
-
-    def ggemm(self, layout, descs, tag=None):
-        arr = (GemmDesc * len(descs))(*descs)
-        ev = self._tick(tag)
-        check(self.lib.tcar_gemm_f32_grouped(layout, len(descs), arr, self._stream()), "tcar_gemm_f32_grouped")
-        self._tock(ev)
-
-    # per-kernel device timing (bench.py): HIP events on the stream the kernels are launched on
-    timing = None
-
-    def enable_timing(self, tags):
-        self.timing = {t: [] for t in tags}
-
-    def _tick(self, tag):
-        if self.timing is None or tag not in self.timing:
-            return None
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(self.dev))
-        self.timing[tag].append((e0, e1))
-        return e1
-
-    def _tock(self, ev):
-        if ev is not None:
-            ev.record(torch.cuda.current_stream(self.dev))
-
-    def timing_summary(self):
-        """tag -> (launches, mean ms); call after a device synchronize."""
-        out = {}
-        for t, evs in (self.timing or {}).items():
-            if evs:
-                ms = [a.elapsed_time(b) for a, b in evs]
-                out[t] = (len(ms), float(np.mean(ms)))
-        return out
 
     def make_resident(self, batch: Dict[str, np.ndarray]) -> Batch:
         """Upload a batch into its OWN device buffer (kept alive by the engine) and return its descriptor.  The staging
@@ -520,7 +489,7 @@ class TcarEngine:
         t = Tables()
         t.E = self.E.data_ptr()
         t.pos = self._w("pos").value
-        for k, n in enumerate(["month", "day", "week", "hour", "minute"]):
+        for k, n in enumerate(TIME_SHORT):
             t.time[k] = self._w(n).value
         t.dur = self._w("dur").value
         return t
@@ -529,7 +498,7 @@ class TcarEngine:
         gr = Grads()
         gr.g_item = self.Gi.data_ptr()
         gr.g_pos = self._g("pos").value
-        for k, n in enumerate(["month", "day", "week", "hour", "minute"]):
+        for k, n in enumerate(TIME_SHORT):
             gr.g_time[k] = self._g(n).value
             gr.slot_time[k] = SLOT[TIME_NAMES[k]]
         gr.g_dur = self._g("dur").value
@@ -539,7 +508,7 @@ class TcarEngine:
 
     def _time_ptrs(self):
         arr = (C.c_void_p * 5)()
-        for k, n in enumerate(["month", "day", "week", "hour", "minute"]):
+        for k, n in enumerate(TIME_SHORT):
             arr[k] = self._w(n).value
         return arr
 
@@ -597,255 +566,67 @@ class TcarEngine:
         bt._keep = self.ibufs[i]
         return bt
 
-    # --------------------------------------------------------------------------------------------- forward
-    def forward(self, bt: Batch):
-        """model_combine.py:52-138 up to the full-catalog logits (Python-sequenced op-level path, fp32 scoring only;
-        the bf16 scoring modes are sequenced by the C++ step driver)."""
-        if self.scoring_code:
-            raise _lib.TcarError("the Python-sequenced op-level path supports scoring='f32' only")
-        g, lib, st = self.geo, self.lib, self._stream()
-        B, T = bt.B, bt.T
-        BT = B * T
-        self._ensure_work(B, T)
-        p = self._p
-        if self._time_dirty:
-            check(lib.tcar_cand_time_fwd(C.byref(self.dims), C.byref(self._time_ptrs()), p(self.mwdhm), p(self.E), st),
-                  "tcar_cand_time_fwd")
-            self._time_dirty = False
-        tab = self._tables()
-        ev = self._tick("gather_fwd")
-        check(lib.tcar_gather_clip_fwd(C.byref(self.dims), C.byref(tab), C.byref(bt), p(self.x_icp), p(self.x_pt),
-                                       p(self.x_act), p(self.click_t), st), "tcar_gather_clip_fwd")
-        self._tock(ev)
-        # one grouped launch:  pre1 = X_ic W_in + X_c W_c + X_act W_int (modules.py:126-131),
-        # pre2 = X_pt W'_in + X_c W'_c (modules.py:94-96), q1 = relu(click_t Wq1 + b) (modules.py:138)
-        D = self.desc
-        x_c = p(self.x_icp, g.ldh)
-        self.ggemm(0, [
-            D(BT, g.ldh, [(p(self.x_icp), g.ic, self._w("m_win"), g.ldh, g.ic), (x_c, g.ic, self._w("m_wc"), g.ldh, g.ldh),
-                          (p(self.x_act), g.ldt, self._w("m_wint"), g.ldh, g.ldt)], p(self.pre1), g.ldh),
-            D(BT, g.ldh, [(p(self.x_pt), g.pt, self._w("s_win"), g.ldh, g.pt), (x_c, g.ic, self._w("s_wc"), g.ldh, g.ldh)],
-              p(self.pre2), g.ldh),
-            D(B, g.ldh, [(p(self.click_t), g.ct, self._w("q1_w"), g.ldh, g.ct)], p(self.q1), g.ldh,
-              bias=self._w("q1_b"), act=1)])
-        # q = tanh(q1 Wq2 + b)                           (modules.py:139)
-        self.ggemm(0, [D(B, g.ic, [(p(self.q1), g.ldh, self._w("q2_w"), g.ic, g.ldh)], p(self.q), g.ic,
-                         bias=self._w("q2_b"), act=2)])
-        check(lib.tcar_attn_pool_fwd(C.byref(self.dims), B, T, p(self.x_icp), p(self.x_pt), p(self.pre1), p(self.pre2),
-                                     p(self.q), self._w("m_wres"), self._w("s_wres"), p(self.pooled), p(self.alpha),
-                                     st), "tcar_attn_pool_fwd")
-        # attout = [tanh(pooled_ic W_o + b) | tanh(pooled_t W'_o + b)]   (model_combine.py:119,127,132)
-        self.ggemm(0, [
-            D(B, g.ic, [(p(self.pooled), g.ek, self._w("o_w"), g.ic, g.ic)], p(self.attout), g.ek,
-              bias=self._w("o_b"), act=2),
-            D(B, g.pt, [(p(self.pooled, g.ic), g.ek, self._w("ot_w"), g.pt, g.pt)], p(self.attout, g.ic), g.ek,
-              bias=self._w("ot_b"), act=2)])
-        # logits = attout E^T                              (model_combine.py:138)
-        self.gemm(1, B, g.N, g.ek, p(self.attout), g.ek, p(self.E), g.ek, p(self.logits), g.Npad, tag="score_fwd")
-
-    # -------------------------------------------------------------------------------------------- backward
-    def backward(self, bt: Batch):
-        """Loss (model_combine.py:142-147) and the gradient of its SUM w.r.t. all 23 variables."""
-        self.backward_local(bt)
-        lib, st, p = self.lib, self._stream(), self._p
-        # clip norm of the dense item block BEFORE the sparse rows are scattered in (DESIGN.md S5)
-        self._sqnorm_item()
-        tab, gr = self._tables(), self._grads()
-        check(lib.tcar_gather_clip_bwd(C.byref(self.dims), C.byref(tab), C.byref(bt), p(self.dx_icp), p(self.dx_pt),
-                                       p(self.dx_act), p(self.dclick), C.byref(gr), st), "tcar_gather_clip_bwd")
-        self._cand_time_bwd()
-        self._sqnorm_dense()
-
-    def _sqnorm_item(self):
-        g = self.geo
-        one = Segments()
-        one.nseg = 1
-        one.off[0], one.len[0], one.slot[0] = 0, g.N * g.ldh, SLOT["item_emb"]
-        check(self.lib.tcar_sqnorm(self._p(self.Gi), C.byref(one), self._p(self.sqn_dense), self._stream()), "tcar_sqnorm")
-
-    def _cand_time_bwd(self):
-        gr = self._grads()
-        check(self.lib.tcar_cand_time_bwd_indexed(C.byref(self.dims), C.byref(self._time_ptrs()), self._p(self.inv_n),
-                                                  self._p(self.inv_off), self._p(self.d_et), int(self.scoring_code != 0),
-                                                  self._p(self.ct_ws), C.byref(gr), self._stream()),
-              "tcar_cand_time_bwd_indexed")
-
-    def _sqnorm_dense(self):
-        check(self.lib.tcar_sqnorm(self._p(self.G), C.byref(self.segs_dense), self._p(self.sqn_dense), self._stream()),
-              "tcar_sqnorm")
-
-    def backward_local(self, bt: Batch):
-        """Everything of the backward pass that needs no other rank: loss, dlogits, dE, input / weight gradients."""
-        g, lib, st = self.geo, self.lib, self._stream()
-        B, T, K = bt.B, bt.T, bt.K
-        BT = B * T
-        p = self._p
-        self.Gx.zero_()               # tables, bias, weight gradients and norm pieces are accumulated with atomics
-        self.sqn_dense.zero_()
-        ev = self._tick("softmax_ce")
-        check(lib.tcar_softmax_ce(B, g.N, p(self.logits), g.Npad, C.c_void_p(bt.label), p(self.ce), st), "tcar_softmax_ce")
-        self._tock(ev)
-        # d attout = dlogits E  (contraction over the catalog: split-K slabs + reduce)
-        S = lib.tcar_gemm_splitk_effective(g.Npad, self.splitk)
-        self.gemm(0, B, g.ek, g.Npad, p(self.logits), g.Npad, p(self.E), g.ek, p(self.slabs), g.ek, splitk=self.splitk,
-                  tag="score_dx")
-        check(lib.tcar_splitk_reduce(p(self.slabs), S, B, g.ek, g.ek, p(self.dattout), st), "tcar_splitk_reduce")
-        # dE = dlogits^T attout: item columns -> Gi, time columns -> d_et (content is frozen); one launch, both
-        # problems stream the same dlogits tiles
-        D = self.desc
-        self.ggemm(2, [
-            D(g.N, g.ldh, [(p(self.logits), g.Npad, p(self.attout), g.ek, B)], p(self.Gi), g.ldh),
-            D(g.N, g.pt, [(p(self.logits), g.Npad, p(self.attout, g.ic), g.ek, B)], p(self.d_et), g.pt)], tag="score_dE")
-        if K:
-            check(lib.tcar_neg_term(C.byref(self.dims), B, K, p(self.E), C.c_void_p(bt.neg), p(self.attout),
-                                    self.neg_weight, p(self.neg_fb), p(self.dattout), p(self.Gi), p(self.ce), p(self.loss),
-                                    st), "tcar_neg_term")
-        else:
-            self.neg_fb[:B].zero_()
-        # output transforms (linear_2d + tanh) backward
-        check(lib.tcar_dact_colsum(B, g.ic, g.ek, p(self.attout), p(self.dattout), self._g("o_b"), 2, st), "dact")
-        check(lib.tcar_dact_colsum(B, g.pt, g.ek, p(self.attout, g.ic), p(self.dattout, g.ic), self._g("ot_b"), 2, st), "dact")
-        self.ggemm(1, [
-            D(B, g.ic, [(p(self.dattout), g.ek, self._w("o_w"), g.ic, g.ic)], p(self.dpooled), g.ek),
-            D(B, g.pt, [(p(self.dattout, g.ic), g.ek, self._w("ot_w"), g.pt, g.pt)], p(self.dpooled, g.ic), g.ek)])
-        check(lib.tcar_attn_pool_bwd(C.byref(self.dims), B, T, p(self.x_icp), p(self.x_pt), p(self.pre1), p(self.pre2),
-                                     p(self.q), self._w("m_wres"), self._w("s_wres"), p(self.alpha), p(self.dpooled),
-                                     p(self.dx_icp), p(self.dx_pt), p(self.dq), p(self.dpre1), p(self.dpre2),
-                                     self._g("m_wres"), self._g("s_wres"), st), "tcar_attn_pool_bwd")
-        # query MLP backward (modules.py:138-139)
-        check(lib.tcar_dact_colsum(B, g.ic, g.ic, p(self.q), p(self.dq), self._g("q2_b"), 2, st), "dact")
-        self.ggemm(1, [D(B, g.ldh, [(p(self.dq), g.ic, self._w("q2_w"), g.ic, g.ic)], p(self.dq1), g.ldh)])
-        check(lib.tcar_dact_colsum(B, g.ldh, g.ldh, p(self.q1), p(self.dq1), self._g("q1_b"), 1, st), "dact")
-        # input gradients: click query rows and the projections (only the ITEM half of dX_ic is needed: content
-        # is frozen)
-        self.ggemm(1, [
-            D(B, g.ct, [(p(self.dq1), g.ldh, self._w("q1_w"), g.ldh, g.ldh)], p(self.dclick), g.ct),
-            D(BT, g.ldh, [(p(self.dpre1), g.ldh, self._w("m_win"), g.ldh, g.ldh)], p(self.dx_icp), g.ic, beta=1),
-            D(BT, g.ldt, [(p(self.dpre1), g.ldh, self._w("m_wint"), g.ldh, g.ldh)], p(self.dx_act), g.ldt),
-            D(BT, g.pt, [(p(self.dpre2), g.ldh, self._w("s_win"), g.ldh, g.ldh)], p(self.dx_pt), g.pt, beta=1)])
-        # all nine weight gradients (x^T dy, K = batch rows) in one launch, split-K with fp32 atomics into the
-        # zeroed gradient arena
-        kb = max(1, min(16, (B + 1023) // 1024))
-        kr = max(1, min(16, (BT + 1023) // 1024))
-        x_c = p(self.x_icp, g.ldh)
-        W = lambda M, N, A, lda, Bm, ldb, K, name, ks: D(M, N, [(A, lda, Bm, ldb, K)], self._g(name), N, splitk=max(ks, 2),
-                                                          atomic=1)
-        self.ggemm(2, [
-            W(g.ic, g.ic, p(self.pooled), g.ek, p(self.dattout), g.ek, B, "o_w", kb),
-            W(g.pt, g.pt, p(self.pooled, g.ic), g.ek, p(self.dattout, g.ic), g.ek, B, "ot_w", kb),
-            W(g.ldh, g.ic, p(self.q1), g.ldh, p(self.dq), g.ic, B, "q2_w", kb),
-            W(g.ct, g.ldh, p(self.click_t), g.ct, p(self.dq1), g.ldh, B, "q1_w", kb),
-            W(g.ic, g.ldh, p(self.x_icp), g.ic, p(self.dpre1), g.ldh, BT, "m_win", kr),
-            W(g.ldh, g.ldh, x_c, g.ic, p(self.dpre1), g.ldh, BT, "m_wc", kr),
-            W(g.ldt, g.ldh, p(self.x_act), g.ldt, p(self.dpre1), g.ldh, BT, "m_wint", kr),
-            W(g.pt, g.ldh, p(self.x_pt), g.pt, p(self.dpre2), g.ldh, BT, "s_win", kr),
-            W(g.ldh, g.ldh, x_c, g.ic, p(self.dpre2), g.ldh, BT, "s_wc", kr)], tag="weight_grads")
-
-    # ---------------------------------------------------------------------------------------------- update
-    def update(self):
-        """model_combine.py:157-163: per-variable clip_by_norm(max_grad) + TF-1 Adam."""
-        g, lib, st, p = self.geo, self.lib, self._stream(), self._p
-        lr_t = self._lr_t()
-        clip = float(self.max_grad) if self.max_grad else 0.0
-        check(lib.tcar_clip_adam(p(self.W), p(self.G), p(self.M), p(self.V), C.byref(self.segs_all), p(self.sqn_dense),
-                                 p(self.sqn_pieces), p(self.use_dense), clip, lr_t, self.b1, self.b2, self.eps, st),
-              "tcar_clip_adam")
-        ev = self._tick("adam_item")
-        check(lib.tcar_clip_adam_2d(p(self.E), g.ek, p(self.Gi), p(self.Mi), p(self.Vi), g.N, g.ldh, SLOT["item_emb"],
-                                    p(self.sqn_dense), p(self.sqn_pieces), p(self.use_dense), clip, lr_t, self.b1,
-                                    self.b2, self.eps, st), "tcar_clip_adam_2d")
-        self._tock(ev)
-        self._after_update()
-
     # ------------------------------------------------------------------------------ native (C++) step driver
-    overlap = os.environ.get("TCAR_NO_OVERLAP", "") == ""      # second HIP stream for the independent dE / candidate-time chains (C++ driver only)
-    native = True        # drive the step from libtcar_hip.so (tcar_train_step / tcar_eval_step); False = Python
+    # second HIP stream for the independent dE / candidate-time chains (C++ driver only).  None: from TCAR_NO_OVERLAP when the engine
+    # is constructed; a class or an instance may set True / False
+    overlap = None
+    native = True        # drive the step from libtcar_hip.so (tcar_train_step / tcar_eval_step); False = Python (oplevel.py)
+    slot_item = SLOT["item_emb"]
+    _ctx_key = None      # what the cached tcar_ctx_t was built for; None forces a rebuild (set_tuning; bench.py after changing _ev)
+
+    def _form(self) -> StepForm:
+        """switches + geometry + scoring mode -> the form of this engine's step (nothing else derives it).  The one-hot forms need the
+        whole catalog on this engine; the forward one does not need the backward one (ldt != 64)."""
+        sw, g, bf, ov = self.sw, self.geo, bool(self.scoring_code), bool(self.overlap)
+        ce = bf and self.scoring_bwd == 1
+        oh = ce and self.shard == (0, g.N) and not sw.no_onehot
+        ohb = oh and g.ldt == 64 and not sw.no_onehot_bwd
+        wks = max(1, int((self.tune if self.tune is not None else _lib.tuning()).wgrad_ks))
+        return StepForm(ScoreForm(planes=bf, fused_ce=ce, onehot_fwd=oh, onehot_bwd=ohb, anchored=ohb and not sw.no_ce_anchor),
+                        det_colsums=bf and not sw.atomic_colsums, wgrad_ks=wks if self.work_rows > wks and not sw.atomic_wgrad else 0,
+                        sorted_rows=ov, stream3=ov and not sw.no_stream3,
+                        flag_forks=ov and self.flag_forks and not sw.no_flag_fork, fold_scratch=not sw.no_fold_scratch)
+
+    def _optional_specs(self, f: StepForm) -> List[Spec]:
+        """the optional workspaces of tcar_ctx_t outside the scoring family (sizes: the comments of their fields in include/tcar_hip.h)"""
+        g, r, B, out = self.geo, self.work_rows, self.work_B, []
+        u = lambda k: (k + 127) // 128
+        if f.wgrad_ks:            # wgrad_slabs: one slab of the nine weight gradients per K split, at most 16
+            per = g.ic * g.ic + g.pt * g.pt + g.ldh * g.ic + g.ct * g.ldh + g.ic * g.ldh + 2 * g.ldh * g.ldh + g.ldt * g.ldh + g.pt * g.ldh
+            out.append(Spec("_wgrad_slabs", (min(16, (r + f.wgrad_ks - 1) // f.wgrad_ks) * per,), F32, None, "wgrad_slabs"))
+        if f.score.planes:        # proj_slabs: one slab per 128-deep K chunk of the forward projections; the backward reuses it
+            out.append(Spec("_proj_slabs", (max((u(g.ic) + 2 * u(g.ldh) + u(g.ldt) + u(g.pt)) * r * g.ldh, max(u(g.ic), u(g.pt)) * B * g.ek),),
+                            F32, None, "proj_slabs"))
+        if f.score.anchored:      # ce_form: ONE host int
+            out.append(Spec("_ce_form", (1,), HOST_I32, None, "ce_form"))
+        if f.sorted_rows:         # segsum_ws: sized for the workspace's largest batch; small_det_ws: fixed
+            out += [Spec("_segsum_ws", (int(self.lib.tcar_segsum_ws_bytes(C.byref(self.dims), max(1, r + B * 64))),), U8, None, "segsum_ws"),
+                    Spec("_small_det_ws", (int(self.lib.tcar_small_det_ws_floats()),), F32, None, "small_det_ws")]
+        if f.fold_scratch:        # fold_scratch: zeroed words of the order-fixed last-arrival fold
+            out.append(Spec("_fold_scratch", (128,), I32, 0, "fold_scratch"))
+        return out
 
     def _ctx(self) -> "_lib.Ctx":
-        """tcar_ctx_t for the current workspace (rebuilt when a buffer is re-allocated)."""
-        key = (self.work_rows, self.work_B, self.topk.data_ptr() if hasattr(self, "topk") else 0, id(self._ev))
-        if getattr(self, "_ctx_key", None) == key:
+        """tcar_ctx_t for the current workspace: rebuilt when a buffer was (re-)allocated (Workspace.version), when the timing state
+        or the tuning copy changed, or when _ctx_key was cleared — and only then"""
+        if self._ctx_key == (self.ws.version, id(self._ev), id(self.tune)):
             return self._ctx_obj
-        g, c = self.geo, _lib.Ctx()
-        c.d = self.dims
-        c.splitk = self.splitk
+        c, form = _lib.Ctx(), self._form()
+        specs = self.ws.ensure(self._scoring_specs(form.score) + self._optional_specs(form))
+        c.d, c.splitk, c.arena_n = self.dims, self.splitk, self.arena_n
         for i, (short, sg) in enumerate(self.seg.items()):
             c.slot_of[i], c.off[i] = sg["slot"], sg["off"]
-        c.slot_item = SLOT["item_emb"]
-        c.b1, c.b2, c.eps = self.b1, self.b2, self.eps
+        c.slot_item = self.slot_item
+        c.b1, c.b2, c.eps, c.neg_weight = self.b1, self.b2, self.eps, self.neg_weight
         c.clip = float(self.max_grad) if self.max_grad else 0.0
-        c.neg_weight = self.neg_weight
-        for n, t in (("E", self.E), ("W", self.W), ("Gx", self.Gx), ("M", self.M), ("V", self.V), ("big", self.big),
-                     ("Mi", self.Mi), ("Vi", self.Vi), ("sqn_dense", self.sqn_dense), ("use_dense", self.use_dense),
-                     ("mwdhm", self.mwdhm), ("inv_n", self.inv_n), ("inv_off", self.inv_off), ("ct_ws", self.ct_ws),
-                     ("rank", self.rank), ("topk", self.topk)):
-            setattr(c, n, t.data_ptr())
-        c.arena_n = self.arena_n
         c.segs_all, c.segs_dense = self.segs_all, self.segs_dense
-        for n in _lib._WS:
+        c.scoring, c.scoring_bwd = self.scoring_code, self.scoring_bwd
+        for n in CTX_STATE + _lib._WS + ["rank", "topk"] + (["e16h", "e16l"] if self.scoring_code else []):
             setattr(c, n, getattr(self, n).data_ptr())
-        c.scoring = self.scoring_code
-        c.et_perm = self.et_perm.data_ptr()
-        c.adam_bitmap = self.adam_bitmap.data_ptr()
-        c.scoring_bwd = self.scoring_bwd
-        if self.scoring_code and not os.environ.get("TCAR_ATOMIC_COLSUMS"):
+        self.ws.bind(c, specs, CTX_SIZES)
+        if form.det_colsums:
             c.gw_rows = self.gw_rows.data_ptr()
-        wks = max(1, int((self.tune if self.tune is not None else _lib.tuning()).wgrad_ks))
-        if self.work_rows > wks and not os.environ.get("TCAR_ATOMIC_WGRAD"):
-            # batches of more than TCAR_WGRAD_KS (1,536) rows split the K of the weight gradients: slabs folded in split order (order-fixed)
-            per = g.ic * g.ic + g.pt * g.pt + g.ldh * g.ic + g.ct * g.ldh + g.ic * g.ldh + 2 * g.ldh * g.ldh + g.ldt * g.ldh + g.pt * g.ldh
-            need = min(16, (self.work_rows + wks - 1) // wks) * per
-            if getattr(self, "_wgrad_slabs", None) is None or self._wgrad_slabs.numel() < need:
-                self._wgrad_slabs = torch.empty(need, dtype=torch.float32, device=self.dev)
-            c.wgrad_slabs, c.wgrad_slab_floats = self._wgrad_slabs.data_ptr(), self._wgrad_slabs.numel()
-        if self.scoring_code:
-            for n in ("e16h", "e16l", "a16h", "a16l", "ap16h", "ap16l", "dl16h", "dl16l"):
-                setattr(c, n, getattr(self, n).data_ptr())
-            # slab workspace of the split session-side GEMMs (forward projections: one slab per 128-deep K chunk; backward:
-            # the input gradient of the output transforms)
-            u = lambda k: (k + 127) // 128
-            need = max((u(g.ic) + 2 * u(g.ldh) + u(g.ldt) + u(g.pt)) * self.work_rows * g.ldh,
-                       max(u(g.ic), u(g.pt)) * self.work_B * g.ek)
-            if getattr(self, "_proj_slabs", None) is None or self._proj_slabs.numel() < need:
-                self._proj_slabs = torch.empty(need, dtype=torch.float32, device=self.dev)
-            c.proj_slabs, c.proj_slab_floats = self._proj_slabs.data_ptr(), self._proj_slabs.numel()
-            if self.scoring_bwd == 1:
-                # softmax epilogue of the logits GEMM (training steps): per-group (max, sum) pairs, label scores, row statistics
-                need = self.work_B * ((g.N + 63) // 64 + 8) * 2 + 4 * self.work_B + 8
-                if getattr(self, "_ce_ws", None) is None or self._ce_ws.numel() < need:
-                    self._ce_ws = torch.empty(need, dtype=torch.float32, device=self.dev)
-                    self._ce_geo = (C.c_int32 * 2)(0, 0)
-                c.ce_ws, c.ce_ws_floats, c.ce_geo = self._ce_ws.data_ptr(), self._ce_ws.numel(), C.cast(self._ce_geo, C.c_void_p)
-                # one-hot form of the candidate-side time scores: static OH plane of publish_time_MWDHM, per-step score planes
-                if self.shard == (0, g.N) and not os.environ.get("TCAR_NO_ONEHOT"):
-                    if getattr(self, "_oh16", None) is None:
-                        self._oh16 = torch.empty(g.Npad * 160, dtype=torch.bfloat16, device=self.dev)
-                        check(self.lib.tcar_time_onehot(C.byref(self.dims), self._p(self.mwdhm), self._p(self._oh16), 160,
-                                                        self._stream()), "tcar_time_onehot")
-                    Bp = _ru(self.work_B, 128)
-                    if getattr(self, "_p16h", None) is None or self._p16h.numel() < Bp * 160:
-                        self._p16h = torch.zeros(Bp * 160, dtype=torch.bfloat16, device=self.dev)
-                        self._p16l = torch.zeros(Bp * 160, dtype=torch.bfloat16, device=self.dev)
-                    c.oh16, c.p16h, c.p16l = self._oh16.data_ptr(), self._p16h.data_ptr(), self._p16l.data_ptr()
-                    # one-hot form of the scoring gradients: clipped time rows, dP = dlogits OH, per-candidate (q, z) pairs
-                    if g.ldt == 64 and not os.environ.get("TCAR_NO_ONEHOT_BWD"):
-                        if getattr(self, "_tclip", None) is None:
-                            self._tclip = torch.zeros(160 * g.ldt + 320, dtype=torch.float32, device=self.dev)
-                            self._qz = torch.zeros(5 * g.N * 2, dtype=torch.float32, device=self.dev)
-                        if getattr(self, "_dP", None) is None or self._dP.numel() < self.work_B * 160:
-                            self._dP = torch.zeros(self.work_B * 160, dtype=torch.float32, device=self.dev)
-                        c.tclip, c.dP, c.qz = self._tclip.data_ptr(), self._dP.data_ptr(), self._qz.data_ptr()
-                        # anchored softmax form (tcar_hip.h: ce_rowscale ...): row scales, the scaled attout plane of dE, and the
-                        # host int that carries the form from the forward to the backward half of a step
-                        if not os.environ.get("TCAR_NO_CE_ANCHOR"):
-                            Bp = _ru(self.work_B, 128)
-                            if getattr(self, "_ce_rowscale", None) is None or self._ce_rowscale.numel() < 2 * Bp:
-                                self._ce_rowscale = torch.zeros(2 * Bp, dtype=torch.float32, device=self.dev)
-                                self._aps16h = torch.zeros(Bp, g.ldh + g.pt, dtype=torch.bfloat16, device=self.dev)
-                                self._ce_form = (C.c_int32 * 1)(0)
-                            c.ce_rowscale, c.aps16h = self._ce_rowscale.data_ptr(), self._aps16h.data_ptr()
-                            c.ce_form = C.cast(self._ce_form, C.c_void_p)
-        if self.overlap:
+        if form.sorted_rows:
             if not hasattr(self, "_aux"):
                 self._aux = torch.cuda.Stream(self.dev)
                 self._aux_ev = [torch.cuda.Event() for _ in range(6)]
@@ -854,58 +635,43 @@ class TcarEngine:
             c.stream2 = self._aux.cuda_stream
             for i, e in enumerate(self._aux_ev):
                 c.ev[i] = e.cuda_event
-            # workspace of the deterministic item-row scatter (sort + segmented sum), sized for the workspace's largest batch
-            need = int(self.lib.tcar_segsum_ws_bytes(C.byref(self.dims), max(1, self.work_rows + self.work_B * 64)))
-            if getattr(self, "_segsum_ws", None) is None or self._segsum_ws.numel() < need:
-                self._segsum_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-            c.segsum_ws, c.segsum_bytes = self._segsum_ws.data_ptr(), self._segsum_ws.numel()
-            # row pieces + chunk partials of the order-fixed small-table backward (long buckets: a workgroup per ~1,024 sources)
-            if getattr(self, "_small_det_ws", None) is None:
-                self._small_det_ws = torch.empty(int(self.lib.tcar_small_det_ws_floats()), dtype=torch.float32, device=self.dev)
-            c.small_det_ws, c.small_det_ws_floats = self._small_det_ws.data_ptr(), self._small_det_ws.numel()
-            if not os.environ.get("TCAR_NO_STREAM3"):
-                if not hasattr(self, "_aux3"):
-                    self._aux3 = torch.cuda.Stream(self.dev)
-                    self._aux3_ev = torch.cuda.Event()
-                    self._aux3_ev.record(torch.cuda.current_stream(self.dev))
-                c.stream3 = self._aux3.cuda_stream
-                c.ev3 = self._aux3_ev.cuda_event
-            # flag forks (tcar_ctx_t.sig_dev): a polling kernel must never sit in FRONT of the work it waits for in a hardware queue.
-            # Every poll of the step is enqueued BEHIND its producer's launch, and a producer depends only on work enqueued before
-            # it — so whatever shares the poll's queue ahead of it (another of our streams, a collective's stream) never waits for
-            # the poll: the single-process engine and the catalog-sharded one (whose pieces between the collectives fork and join
-            # our own streams only) use them; DPEngine, whose exchange is enqueued in the middle of the fused backward, keeps events
-            if self.flag_forks and not os.environ.get("TCAR_NO_FLAG_FORK"):
-                if not hasattr(self, "_sig"):
-                    self._sig = torch.zeros(80, dtype=torch.int32, device=self.dev)
-                    # the driver's fork slots and epoch counter: host memory owned by THIS engine (nothing per thread / process)
-                    self._fork_host = (C.c_uint8 * int(self.lib.tcar_fork_state_bytes()))()
-                    # time-outs are mirrored into a pinned, device-visible host word: poll_fork_errors() reads it without a sync
-                    self._sig_err = torch.zeros(16, dtype=torch.int32).pin_memory()
-                    self._sig_err_np = self._sig_err.numpy()
-                    # one probe: do the side streams run BESIDE the main stream here?  (Not under a counter-collecting
-                    # profiler or with serialised kernels: every poll would sit out its time-out — events then.)
-                    if not self._probe_flag_forks():
-                        import warnings
-                        warnings.warn("tcar: kernels of different streams do not run concurrently here (profiler counter "
-                                      "collection / serialised kernels / shared hardware queue): flag forks off, events instead")
-                        self._sig = None
-                if self._sig is not None:
-                    c.sig_dev, c.fork_host = self._sig.data_ptr(), C.cast(self._fork_host, C.c_void_p)
-                    c.sig_err_host = self._sig_err.data_ptr()
+        if form.stream3:
+            if not hasattr(self, "_aux3"):
+                self._aux3 = torch.cuda.Stream(self.dev)
+                self._aux3_ev = torch.cuda.Event()
+                self._aux3_ev.record(torch.cuda.current_stream(self.dev))
+            c.stream3, c.ev3 = self._aux3.cuda_stream, self._aux3_ev.cuda_event
+        # flag forks (tcar_ctx_t.sig_dev): a polling kernel must never sit in FRONT of the work it waits for in a hardware queue.
+        # Every poll of the step is enqueued BEHIND its producer's launch, and a producer depends only on work enqueued before
+        # it — so whatever shares the poll's queue ahead of it (another of our streams, a collective's stream) never waits for
+        # the poll: the single-process engine and the catalog-sharded one (whose pieces between the collectives fork and join
+        # our own streams only) use them; DPEngine, whose exchange is enqueued in the middle of the fused backward, keeps events
+        if form.flag_forks:
+            if not hasattr(self, "_sig"):
+                self._sig = torch.zeros(80, dtype=torch.int32, device=self.dev)
+                # the driver's fork slots and epoch counter: host memory owned by THIS engine (nothing per thread / process)
+                self._fork_host = (C.c_uint8 * int(self.lib.tcar_fork_state_bytes()))()
+                # time-outs are mirrored into a pinned, device-visible host word: poll_fork_errors() reads it without a sync
+                self._sig_err = torch.zeros(16, dtype=torch.int32).pin_memory()
+                self._sig_err_np = self._sig_err.numpy()
+                # one probe: do the side streams run BESIDE the main stream here?  (Not under a counter-collecting
+                # profiler or with serialised kernels: every poll would sit out its time-out — events then.)
+                if not self._probe_flag_forks():
+                    import warnings
+                    warnings.warn("tcar: kernels of different streams do not run concurrently here (profiler counter "
+                                  "collection / serialised kernels / shared hardware queue): flag forks off, events instead")
+                    self._sig = None
+            if self._sig is not None:
+                c.sig_dev, c.fork_host = self._sig.data_ptr(), C.cast(self._fork_host, C.c_void_p)
+                c.sig_err_host = self._sig_err.data_ptr()
         if self.tune is not None:
             c.tune = C.cast(C.pointer(self.tune), C.c_void_p)
-        if not os.environ.get("TCAR_NO_FOLD_SCRATCH"):
-            # zeroed words of the order-fixed last-arrival fold (dense-weight norms of the fused step: several workgroups per variable)
-            if getattr(self, "_fold_scratch", None) is None:
-                self._fold_scratch = torch.zeros(128, dtype=torch.int32, device=self.dev)
-            c.fold_scratch, c.fold_scratch_words = self._fold_scratch.data_ptr(), self._fold_scratch.numel()
         if self._ev is not None:
             c.ev_start = C.cast(self._ev["start_arr"], C.c_void_p)
             c.ev_stop = C.cast(self._ev["stop_arr"], C.c_void_p)
             c.ev_n = self._ev["n"]
             c.ev_cursor = C.cast(self._ev["cursor"], C.c_void_p)
-        self._ctx_key, self._ctx_obj = key, c
+        self._ctx_key, self._ctx_obj = (self.ws.version, id(self._ev), id(self.tune)), c
         return c
 
     flag_forks = True    # may this engine class fork / join its streams through device flags (see _ctx)
@@ -975,12 +741,25 @@ class TcarEngine:
 
     _pending_lr = None        # bias-corrected rate of an optimizer update that has been deferred (train_step(defer_update=True))
 
+    _update_ctx = _ctx        # the context an optimizer update covers (the sharded engine: its shard's)
+
     def flush(self):
         """Apply a deferred optimizer update now (no-op otherwise).  Every entry point except train_step(defer_update=True)
         calls it first, so a deferred update is never observable."""
         if self._pending_lr is not None:
             lr, self._pending_lr = self._pending_lr, None
-            check(self.lib.tcar_step_update(C.byref(self._ctx()), lr, self._stream()), "tcar_step_update")
+            check(self.lib.tcar_step_update(C.byref(self._update_ctx()), lr, self._stream()), "tcar_step_update")
+
+    def _step_deferred(self, enqueue, defer_update: bool):
+        """The deferred-update protocol: enqueue(lr) runs one step WITHOUT its optimizer update, applying the owed update of the step
+        before (rate lr; None: nothing owed) at its start; this step's update is then owed in turn — to the next step or to flush()."""
+        lr_owed, self._pending_lr = self._pending_lr, None
+        enqueue(lr_owed)
+        self._pending_lr = self._lr_t()
+        self._after_update()              # step count / beta powers advance now; the device work is owed
+        self.poll_fork_errors()
+        if not defer_update:
+            self.flush()
 
     def train_step(self, batch: Dict[str, np.ndarray], bt: Optional[Batch] = None, defer_update: bool = False) -> torch.Tensor:
         """One sess.run([loss, global_step, train_op]) (model_combine.py:231); returns loss[B] on device.
@@ -989,18 +768,12 @@ class TcarEngine:
         (tcar_train_step_deferred) — or by flush(); results are identical, the HBM-bound pass over the item table leaves
         the critical path."""
         bt = bt or self.upload(batch)
-        if self.native and self.timing is None:
+        if self.native:
             self._ensure_work(bt.B, bt.T)
             if defer_update or self._pending_lr is not None:
-                pend, lr_p = (1, self._pending_lr) if self._pending_lr is not None else (0, 0.0)
-                self._pending_lr = None
-                check(self.lib.tcar_train_step_deferred(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), pend, lr_p,
-                                                        self._stream()), "tcar_train_step_deferred")
-                self._pending_lr = self._lr_t()
-                self._after_update()              # step count / beta powers advance now; the device work is owed
-                self.poll_fork_errors()
-                if not defer_update:
-                    self.flush()
+                self._step_deferred(lambda lr: check(self.lib.tcar_train_step_deferred(
+                    C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), int(lr is not None), 0.0 if lr is None else lr,
+                    self._stream()), "tcar_train_step_deferred"), defer_update)
             else:
                 check(self.lib.tcar_train_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), self._lr_t(),
                                                self._stream()), "tcar_train_step")
@@ -1016,7 +789,7 @@ class TcarEngine:
     def loss_and_grads(self, batch, bt: Optional[Batch] = None) -> torch.Tensor:
         self.flush()
         bt = bt or self.upload(batch)
-        if self.native and self.timing is None:
+        if self.native:
             self._ensure_work(bt.B, bt.T)
             ctx, st = self._ctx(), self._stream()
             check(self.lib.tcar_step_forward(C.byref(ctx), C.byref(bt), int(self._time_dirty), st), "tcar_step_forward")
@@ -1063,8 +836,7 @@ class TcarEngine:
         bt = bt or self.upload(batch)
         B = bt.B
         self._ensure_work(B, bt.T)
-        if k != self.topk.shape[1] or self.topk.shape[0] < B:
-            self.topk = torch.empty(max(B, self.work_B), k, dtype=torch.int32, device=self.dev)
+        self.ws.get(Spec("topk", (self.work_B, k), I32))           # (another k: a new buffer, and with it a new context)
         if self.native and not keep_logits:
             check(self.lib.tcar_eval_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), k, self._stream()),
                   "tcar_eval_step")

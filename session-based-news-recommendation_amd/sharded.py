@@ -32,16 +32,15 @@ tcar_shard_finish / tcar_step_session_backward), the collectives in between from
 from __future__ import annotations
 
 import ctypes as C
-import math
-import os
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from . import _lib, dp
-from ._lib import Batch, Dims, GemmDesc, Segments, check
-from .engine import SLOT, TcarEngine, _ru
+from ._lib import Batch, Dims, check
+from .engine import Switches, TcarEngine, _ru
+from .workspace import F32, I32, ScoreForm, Spec, scoring_specs
 
 
 def shard_rows(n_items: int, world: int):
@@ -201,24 +200,26 @@ class ShardedEngine(TcarEngine):
             raise ValueError("more ranks than 128-row catalog blocks")
         # dX of a shard contracts over N / W catalog rows for W * B sessions: W times more output tiles and a W times shorter
         # K than the single-rank GEMM, so the split that fills the chip (and the slab bytes it writes) shrinks with W
-        if "splitk" not in kw and "TCAR_SPLITK" not in os.environ:
+        sw = Switches.read()
+        if "splitk" not in kw and not sw.splitk:
             kw["splitk"] = max(2, -(-36 // self.world))
         if self.xch.collective:
             self.priority_stream = False          # (TcarEngine.priority_stream: no priority stream beside live collectives)
         super().__init__(params, content_emb, mwdhm, lr=lr, max_grad=max_grad, neg_weight=neg_weight, device=device,
-                         scoring=scoring, shard=(n0, nl), **kw)
+                         scoring=scoring, shard=(n0, nl), switches=sw, **kw)
         self.n0, self.nl = n0, nl
-        self.nlpad = _ru(nl, 128)
         self.n_local_items = nl
         self.backend = self.xch.backend
-        if self.xch.collective and self.tune is None and not os.environ.get("TCAR_SHARD_ALL_FLAGS"):
+        if self.xch.collective and self.tune is None and not sw.shard_all_flags:
             # Flag forks whose PRODUCER sits behind a collective: the gather behind the item-row all-gather of the
             # previous update (FK_GATHER), the slab reduce and the input-gradient launch behind the dX reduce-scatter (FK_REDUCE,
             # FK_INGRAD).  A peer whose host stalls holds those producers back for as long as it likes, and a poll gives up after
             # 1 s — so these three fork through events whenever collectives are live; the others depend on local work only.
             mask = int(_lib.tuning().flag_fork) & ~((1 << 3) | (1 << 4) | (1 << 6))
             self.set_tuning(TCAR_FLAG_FORK=mask)
-        self.cap = 0
+        self.cap, self._kcap, self._rows_cap = 0, 0, 0
+        self.score_form = self._score_form()
+        self.onehot = self.score_form.fused_ce
         self._stage = torch.zeros(self.world, self.S, self.geo.ldh, dtype=torch.float32, device=self.dev)
         self.bytes_moved = self.xch.bytes_moved
 
@@ -241,52 +242,33 @@ class ShardedEngine(TcarEngine):
                         "gradient and the candidate-time block stay local"}
 
     # -------------------------------------------------------------------------------------------- workspace
+    s_logits = None          # (the one-hot schedule keeps no fp32 logits of the shard)
+
+    def _score_form(self) -> ScoreForm:
+        """switches + geometry + scoring mode -> the form of the shard pieces (nothing else derives it): the benchmarked single-GPU
+        schedule on the shard (tcar_hip.h: tcar_shard_score) — softmax epilogue + both one-hot forms, no fp32 logits — or all of it
+        materialised; the anchored softmax form on top of the former"""
+        sw = self.sw
+        oh = (self.scoring_code == 3 and self.scoring_bwd == 1 and self.geo.ldt == 64
+              and not (sw.shard_materialised or sw.no_onehot or sw.no_onehot_bwd))
+        return ScoreForm(planes=True, logits=not oh, fused_ce=oh, onehot_fwd=oh, onehot_bwd=oh, anchored=oh and not sw.no_ce_anchor)
+
+    def _score_specs(self) -> List[Spec]:
+        """the scoring family of the shard: the world * cap session rows of the exchange against the n_loc candidate rows, under
+        `s_` names (the row scales of the anchored form: tcar_shard_t.scale2)"""
+        return scoring_specs(self.geo, self.world * self.cap, self.nl, self.splitk, self.score_form,
+                             lambda f: "s_scale2" if f == "ce_rowscale" else "s_" + f, self._fill_onehot)
+
     def _ensure_score(self, cap: int, K: int):
-        g = self.geo
-        if cap > self.cap or K > getattr(self, "_kcap", 0):
-            cap = max(cap, self.cap)
-            Bq = self.world * cap
-            f32 = dict(dtype=torch.float32, device=self.dev)
-            bf = dict(dtype=torch.bfloat16, device=self.dev)
-            Bp = _ru(Bq, 128)
-            kc = max(K, getattr(self, "_kcap", 0), 1)
+        if cap > self.cap or K > self._kcap:
+            g = self.geo
+            self.cap, self._kcap = max(cap, self.cap), max(K, self._kcap, 1)
+            cap, kc, Bq = self.cap, self._kcap, self.world * self.cap
             self.ld_head = _ru(g.ek + 2 + kc, 4)
-            self.head_loc = torch.zeros(cap, self.ld_head, **f32)          # [attout | label | neg coefficient | negatives | pad]
-            self.s_lab = torch.full((Bq,), -1, dtype=torch.int32, device=self.dev)      # unpacked by tcar_shard_score
-            self.s_neg = torch.full((Bq, kc), -1, dtype=torch.int32, device=self.dev)
-            self.s_coef = torch.zeros(Bq, **f32)
-            # the benchmarked single-GPU schedule on the shard (tcar_hip.h: tcar_shard_score): softmax epilogue + one-hot forms —
-            # no fp32 logits; their workspaces are sized for the W * cap session rows of the exchange
-            self.onehot = (self.scoring_code == 3 and self.scoring_bwd == 1 and g.ldt == 64
-                           and not os.environ.get("TCAR_SHARD_MATERIALISED") and not os.environ.get("TCAR_NO_ONEHOT")
-                           and not os.environ.get("TCAR_NO_ONEHOT_BWD"))
-            if self.onehot:
-                self.s_logits = None
-                need = Bq * ((self.nl + 63) // 64 + 8) * 2 + 4 * Bq + 8
-                self.s_ce_ws = torch.empty(need, **f32)
-                self.s_ce_geo = (C.c_int32 * 2)(0, 0)
-                if getattr(self, "s_oh16", None) is None:
-                    self.s_oh16 = torch.empty(self.nlpad * 160, dtype=torch.bfloat16, device=self.dev)
-                    check(self.lib.tcar_time_onehot(C.byref(self.dims_cand), self._p(self.mwdhm), self._p(self.s_oh16), 160,
-                                                    self._stream()), "tcar_time_onehot")
-                    self.s_tclip = torch.zeros(160 * g.ldt + 320, **f32)
-                    self.s_qz = torch.zeros(5 * self.nl * 2, **f32)
-                self.s_p16h, self.s_p16l = torch.zeros(Bp * 160, **bf), torch.zeros(Bp * 160, **bf)
-                self.s_dP = torch.zeros(Bq * 160, **f32)
-            else:
-                self.s_logits = torch.empty(Bq, self.nlpad, **f32)
-            self._sctx_src = None            # the shard context carries these pointers
-            self.s_stats = torch.empty(Bq, 3, **f32)
-            self.s_lse, self.s_ce = torch.empty(Bq, **f32), torch.empty(Bq, **f32)
-            self.s_a16h, self.s_a16l = torch.zeros(Bp, g.ek, **bf), torch.zeros(Bp, g.ek, **bf)
-            self.s_ap16h, self.s_ap16l = torch.zeros(Bp, g.ldh + g.pt, **bf), torch.zeros(Bp, g.ldh + g.pt, **bf)
-            self.s_dl16h, self.s_dl16l = torch.zeros(Bp, self.nlpad, **bf), torch.zeros(Bp, self.nlpad, **bf)
-            self.s_slabs = torch.empty(self.splitk, Bq, g.ek, **f32)
-            self.s_dx = torch.empty(Bq, g.ek, **f32)
-            # anchored softmax form on the shard (tcar_shard_t.aps16h / scale2): the per-row scaled attout plane of dE, the row scales
-            self.s_aps16h = torch.zeros(Bp, g.ldh + g.pt, **bf) if getattr(self, "onehot", False) and not os.environ.get("TCAR_NO_CE_ANCHOR") else None
-            self.s_scale2 = torch.zeros(2 * Bp, **f32) if self.s_aps16h is not None else None
-            self.cap, self._kcap = cap, kc
+            self.ws.ensure([Spec("head_loc", (cap, self.ld_head), F32, 0),        # [attout | label | neg coefficient | negatives | pad]
+                            Spec("s_lab", (Bq,), I32, -1), Spec("s_neg", (Bq, kc), I32, -1), Spec("s_coef", (Bq,), F32, 0),   # unpacked by tcar_shard_score
+                            Spec("s_stats", (Bq, 3), F32), Spec("s_lse", (Bq,), F32), Spec("s_ce", (Bq,), F32), Spec("s_dx", (Bq, g.ek), F32)]
+                           + self._score_specs())
 
     # two composite spans instead of the three GEMMs of the fused step: the C++ pieces between the exchanges
     TIMED_KERNELS = ("shard_score", "shard_backward")
@@ -330,15 +312,15 @@ class ShardedEngine(TcarEngine):
         self._ensure_score(cap, K)
         nr = cap * T
         ldr = g.ldh + 4
-        if getattr(self, "_rows_cap", 0) < nr:
-            self._rows_buf = torch.zeros(nr, ldr, dtype=torch.float32, device=self.dev)
+        if self._rows_cap < nr:
+            self.ws.get(Spec("_rows_buf", (nr, ldr), F32, 0))
             self._rows_cap = nr
         # (the one-hot schedule reads the shard's time planes nowhere; eval_step rebuilds the fp32 time columns itself)
         refresh = 0 if self.onehot else int(self._time_dirty)
         ctx, sctx = self._ctx(), self._shard_ctx()
         sh = self._shard_desc(cap)
         if (bt is not None and not self.xch.collective and self.world == 1 and getattr(self, "_tm", None) is None
-                and not os.environ.get("TCAR_SHARD_PY_STEP")):
+                and not self.sw.shard_py_step):
             sh.att_all, sh.ld_att, sh.head_K = self.head_loc.data_ptr(), self.ld_head, K
             lr_u = -1.0
             if update:
@@ -359,53 +341,56 @@ class ShardedEngine(TcarEngine):
         pc.arm(bt, cap, K, nr, ldr, refresh, lr_pending, ctx, sctx, sh)
         self.xch.step(pc, cap, update)
 
+    # tcar_shard_t pointer fields <- attribute, beside those of the scoring family
+    SHARD_OWN = (("stats", "s_stats"), ("lse", "s_lse"), ("ce", "s_ce"), ("dx", "s_dx"), ("lab_all", "s_lab"), ("neg_all", "s_neg"),
+                 ("coef_all", "s_coef"))
+    SHARD_FAMILY = ("logits", "a16h", "a16l", "ap16h", "ap16l", "dl16h", "dl16l", "slabs", "aps16h")
+    # fields of the shard's tcar_ctx_t that take the shard's own buffers of the one-hot schedule
+    SCTX_FAMILY = ("ce_ws", "ce_geo", "oh16", "p16h", "p16l", "tclip", "dP", "qz")
+
     def _shard_desc(self, cap: int) -> "_lib.Shard":
-        key = (cap, self.s_dl16h.data_ptr())
+        key = (cap, self.ws.version)
         if getattr(self, "_sh_key", None) != key:
             sh = _lib.Shard()
             sh.world, sh.cap, sh.n0, sh.n_loc = self.world, cap, self.n0, self.nl
-            if self.s_logits is not None:
-                sh.logits = self.s_logits.data_ptr()
-            for n, t in (("stats", self.s_stats), ("lse", self.s_lse), ("ce", self.s_ce),
-                         ("a16h", self.s_a16h), ("a16l", self.s_a16l), ("ap16h", self.s_ap16h), ("ap16l", self.s_ap16l),
-                         ("dl16h", self.s_dl16h), ("dl16l", self.s_dl16l), ("slabs", self.s_slabs), ("dx", self.s_dx),
-                         ("lab_all", self.s_lab), ("neg_all", self.s_neg), ("coef_all", self.s_coef)):
-                setattr(sh, n, t.data_ptr())
-            if getattr(self, "s_aps16h", None) is not None:
-                sh.aps16h, sh.scale2, sh.n_total = self.s_aps16h.data_ptr(), self.s_scale2.data_ptr(), self.geo.N
+            for f, a in self.SHARD_OWN:
+                setattr(sh, f, getattr(self, a).data_ptr())
+            self.ws.bind(sh, self._score_specs(), only=self.SHARD_FAMILY)
+            if self.score_form.anchored:
+                sh.scale2, sh.n_total = self.s_scale2.data_ptr(), self.geo.N
             self._sh, self._sh_key = sh, key
         return self._sh
 
     def shard_form(self, cap: int) -> Dict[str, bool]:
         """the form the C++ shard pieces take at a capacity of `cap` sessions per rank (tcar_shard_form: their own predicates)"""
-        self._ensure_score(cap, getattr(self, "_kcap", 0) or 0)
+        self._ensure_score(cap, self._kcap)
         out = (C.c_int32 * 2)()
         check(self.lib.tcar_shard_form(C.byref(self._shard_ctx()), C.byref(self._shard_desc(cap)), out), "tcar_shard_form")
         return {"onehot": bool(out[0]), "ce_anchored": bool(out[1])}
 
     def _shard_ctx(self):
-        """tcar_ctx_t whose candidate side is this rank's shard (tcar_step_update: arena + the owned item rows + planes)"""
+        """tcar_ctx_t whose candidate side is this rank's shard (tcar_step_update: arena + the owned item rows + planes); follows the
+        rank's context, which is rebuilt whenever a buffer of the engine was (re-)allocated"""
         c = self._ctx()
         if getattr(self, "_sctx_src", None) is not c:
             s = _lib.Ctx()
             C.memmove(C.byref(s), C.byref(c), C.sizeof(_lib.Ctx))
             s.d = self.dims_cand
             s.E = self.E.data_ptr() + 4 * self.n0 * self.geo.ek
-            if getattr(self, "onehot", False):
-                s.ce_ws, s.ce_ws_floats = self.s_ce_ws.data_ptr(), self.s_ce_ws.numel()
-                s.ce_geo = C.cast(self.s_ce_geo, C.c_void_p)
-                s.oh16, s.p16h, s.p16l = self.s_oh16.data_ptr(), self.s_p16h.data_ptr(), self.s_p16l.data_ptr()
-                s.tclip, s.dP, s.qz = self.s_tclip.data_ptr(), self.s_dP.data_ptr(), self.s_qz.data_ptr()
+            if self.onehot:
+                self.ws.bind(s, self._score_specs(), {"ce_ws": "ce_ws_floats"}, only=self.SCTX_FAMILY)
             else:
                 s.oh16 = s.tclip = s.dP = s.qz = None
             self._sctx, self._sctx_src = s, c
         return self._sctx
 
+    _update_ctx = _shard_ctx
+
     def _update_local(self):
         """clip + Adam: arena on every rank, the item rows of the shard by their owner; returns the staging buffer of collective 6
         (this rank's updated rows in its slot) and the installer that copies the gathered table into E"""
         g = self.geo
-        check(self.lib.tcar_step_update(C.byref(self._shard_ctx()), self._lr_t(), self._stream()), "tcar_step_update")
+        check(self.lib.tcar_step_update(C.byref(self._update_ctx()), self._lr_t(), self._stream()), "tcar_step_update")
         self._after_update()
         if not self.xch.collective:
             return None
@@ -415,17 +400,10 @@ class ShardedEngine(TcarEngine):
             self.E[:g.N, :g.ldh].copy_(stage.view(-1, g.ldh)[:g.N])
         return self._stage, install
 
-    def _update_and_share(self):
-        out = self._update_local()
-        if out is not None:
-            self.xch.share_rows(*out)
-
     def flush(self):
         """a deferred update (one rank, train_step(defer_update=True)) applied now + the pending item-row all-gather of the last
         update (every reader of the item table calls flush)"""
-        if self._pending_lr is not None:
-            lr, self._pending_lr = self._pending_lr, None
-            check(self.lib.tcar_step_update(C.byref(self._shard_ctx()), lr, self._stream()), "tcar_step_update")
+        super().flush()
         self.xch.wait_rows()
 
     @property
@@ -458,13 +436,7 @@ class ShardedEngine(TcarEngine):
         if cap is None:
             cap = (cap_rows // max(T, 1)) if cap_rows else (bt.B if bt is not None else 1)
         if bt is not None and self.can_defer and (defer_update or self._pending_lr is not None):
-            lr_p, self._pending_lr = (self._pending_lr if self._pending_lr is not None else -1.0), None
-            self._step(bt, cap, K, False, T, lr_pending=lr_p)
-            self._pending_lr = self._lr_t()
-            self._after_update()                  # step count / beta powers advance now; the device work is owed
-            self.poll_fork_errors()
-            if not defer_update:
-                self.flush()
+            self._step_deferred(lambda lr: self._step(bt, cap, K, False, T, lr_pending=-1.0 if lr is None else lr), defer_update)
             return self._loss_rows(bt, cap, K)
         self.flush()
         self._step(bt, cap, K, True, T)
@@ -489,7 +461,9 @@ class ShardedEngine(TcarEngine):
         return self._loss_rows(bt, cap, K)
 
     def update(self):
-        self._update_and_share()
+        out = self._update_local()
+        if out is not None:
+            self.xch.share_rows(*out)
 
     def eval_step(self, batch, k: int = 20, bt: Optional[Batch] = None, keep_logits: bool = False):
         """local sessions against the WHOLE catalog on the fp32 GEMM (evaluation runs once per epoch)"""
@@ -498,10 +472,7 @@ class ShardedEngine(TcarEngine):
         g, lib, st, p = self.geo, self.lib, self._stream(), self._p
         B = bt.B
         self._ensure_work(B, bt.T)
-        if not hasattr(self, "ev_logits") or self.ev_logits.shape[0] < B:
-            self.ev_logits = torch.empty(max(B, self.work_B), g.Npad, dtype=torch.float32, device=self.dev)
-        if k != self.topk.shape[1] or self.topk.shape[0] < B:
-            self.topk = torch.empty(max(B, self.work_B), k, dtype=torch.int32, device=self.dev)
+        self.ws.ensure([Spec("ev_logits", (self.work_B, g.Npad), F32), Spec("topk", (self.work_B, k), I32)])
         full = Dims(g.N, g.H, g.Ht, g.ldh, g.ldt)
         if getattr(self, "_ev_mw", None) is None:
             self._ev_mw = torch.tensor(np.ascontiguousarray(self._mwdhm_full, dtype=np.int32), device=self.dev)
@@ -515,9 +486,11 @@ class ShardedEngine(TcarEngine):
         return out + (self.ev_logits[:B, :g.N].clone(),) if keep_logits else out
 
     # ------------------------------------------------------------------------------ inspection (tests, export)
-    def _gather_shard_rows(self, local: torch.Tensor) -> np.ndarray:
+    def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:
         """this rank's [nl, ldh] rows of a candidate-side table -> the whole [N + 1, H] table in the reference's shape (row 0
-        = the pad row, zero).  A COLLECTIVE: every rank calls it."""
+        = the pad row, zero).  A COLLECTIVE: every rank calls it — and so export_state and export_grads are collectives here
+        (the Adam moments and the gradient of the item table live on their owners; every rank gets the full state,
+        host/model.py lets rank 0 write the file).  load_state: every rank reads the same file and keeps the rows of its shard."""
         g = self.geo
         mine = torch.zeros(self.S, g.ldh, dtype=torch.float32, device=self.dev)
         mine[:self.nl] = local
@@ -526,44 +499,4 @@ class ShardedEngine(TcarEngine):
         item[1:] = full.view(-1, g.ldh)[:g.N, :g.H].cpu().numpy()
         return item
 
-    def export_state(self):
-        """TcarEngine.export_state for a sharded catalog: the Adam moments of the item table live on their owners, so this is
-        a COLLECTIVE — every rank calls it (and gets the full state); host/model.py lets rank 0 write the file."""
-        from .engine import VAR_ORDER
-        self.flush()
-        out = {"var/" + k: v for k, v in self.export_params().items()}         # E is whole on every rank
-        for tag, arena, item in (("m/", self.M, self.Mi), ("v/", self.V, self.Vi)):
-            d = self._unpack_arena(arena.cpu().numpy())
-            d["item_emb"] = self._gather_shard_rows(item)
-            out.update({tag + k: d[k] for k in VAR_ORDER})
-        out["meta/step"] = np.asarray(self.step, dtype=np.int64)
-        out["meta/beta_pow"] = np.asarray([self.b1_pow, self.b2_pow], dtype=np.float32)
-        return out
-
-    def load_state(self, st) -> None:
-        """inverse of export_state: every rank reads the same file and keeps the moment rows [n0, n0 + nl) of its shard"""
-        from .engine import VAR_ORDER
-        self.load_params({k[4:]: np.asarray(st[k]) for k in st if k.startswith("var/")})
-        g = self.geo
-        if all(("m/" + k) in st and ("v/" + k) in st for k in VAR_ORDER):
-            for tag, arena, item in (("m/", self.M, self.Mi), ("v/", self.V, self.Vi)):
-                vals = {k: np.asarray(st[tag + k]) for k in VAR_ORDER}
-                arena.copy_(torch.from_numpy(self._pack_arena(vals)))
-                it = np.zeros((self.nl, g.ldh), dtype=np.float32)
-                it[:, :g.H] = vals["item_emb"][1 + self.n0:1 + self.n0 + self.nl]
-                item.copy_(torch.from_numpy(it))
-        if "meta/step" in st:
-            self.step = int(np.asarray(st["meta/step"]))
-        if "meta/beta_pow" in st:
-            bp = np.asarray(st["meta/beta_pow"], dtype=np.float32)
-            self.b1_pow, self.b2_pow = np.float32(bp[0]), np.float32(bp[1])
-
-    def export_grads(self):
-        """summed dense gradients of the last backward, reference shapes (the item rows of every shard are all-gathered)"""
-        g = self.geo
-        out = self._unpack_arena(self.G.cpu().numpy())
-        out["item_emb"] = self._gather_shard_rows(self.Gi)
-        from collections import OrderedDict
-        from .engine import VAR_ORDER
-        return OrderedDict((k, out[k]) for k in VAR_ORDER)
 

@@ -31,6 +31,30 @@ def test_library_exports_every_declared_symbol():
     assert lib.tcar_gemm_splitk_effective(64, 16) == 2
 
 
+def _header_struct_fields(header: str, name: str):
+    """field names of `typedef struct { ... } name;` in declaration order: comments stripped, declarators split"""
+    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    body = re.search(r"typedef struct \{([^{}]*)\}\s*%s\s*;" % name, header).group(1)
+    out = []
+    for decl in body.split(";"):
+        for d in decl.split(","):
+            m = re.search(r"(\w+)\s*(?:\[[^\]]*\])?\s*$", d.strip())
+            if m:
+                out.append(m.group(1))
+    return out
+
+
+def test_struct_mirrors_have_the_header_field_names_in_order():
+    """The engines fill tcar_ctx_t / tcar_shard_t BY NAME from tables of (field, buffer): the ctypes mirrors must name every field
+    as the header does, in its order (the size check of _lib.load() passes two swapped pointers)."""
+    header = open(os.path.join(ROOT, "include", "tcar_hip.h")).read()
+    for name, mirror, n in (("tcar_ctx_t", _lib.Ctx, 104), ("tcar_shard_t", _lib.Shard, 25), ("tcar_batch_t", _lib.Batch, None),
+                            ("tcar_grads_t", _lib.Grads, None)):
+        got = _header_struct_fields(header, name)
+        assert got == [f[0] for f in mirror._fields_], name
+        assert n is None or len(got) == n, (name, len(got))
+
+
 def test_tuning_switch_defaults():
     """Every TCAR_* switch of tcar_tuning_t (include/tcar_hip.h) is reachable by name and holds its documented default (one
     table in step.hip: name, field, default).  The library keeps NO mutable switch: tcar_tuning_set writes the caller's copy
