@@ -199,11 +199,8 @@ int tcar_cand_time_fwd(const tcar_dims_t* d, const float* const time_tab[5], con
 int tcar_cand_time_fwd_bf16(const tcar_dims_t* d, const float* const time_tab[5], const int32_t* mwdhm, float* E,
                             void* e16_hi, void* e16_lo, void* stream);
 
-/* tcar_cand_time_bwd: gradient of the above; d_et [N, pt] (ld = pt) is the time-column block of dE. */
-int tcar_cand_time_bwd(const tcar_dims_t* d, const float* const time_tab[5], const int32_t* mwdhm,
-                       const float* d_et, const tcar_grads_t* g, void* stream);
-
-/* Same result through a static inverted index (deterministic, no atomics): inv_n [5N] lists, per table row
+/* Gradient of tcar_cand_time_fwd from d_et [N, pt] (ld = pt), the time-column block of dE, through a static inverted index
+ * (deterministic, no atomics): inv_n [5N] lists, per table row
  * r = rowoff(k)+v (month 0..12, day 13..44, week 45..52, hour 53..77, minute 78..138), the candidates n with
  * mwdhm[n,k] == v; inv_off [140] are the list offsets; ws holds tcar_cand_time_ws_floats(d) floats.
  * permuted != 0: d_et is stored IN LIST ORDER (segment i of ldt floats belongs to list entry i — the layout
@@ -344,8 +341,8 @@ int tcar_ce_finish(int B, int N, int group_width, int ngroups, const float* stat
  * S_b of the exponentials (ce = log S_b - lab_logit) and S_r of the plane's rounded entries (the gradient's scale: plane / S_r sums to one
  * exactly — S_b below is S_r wherever a gradient is scaled); writes
  * rowstat[b] = (0, 1 / S_b) (may be NULL); puts the label's -1 into the plane as v = bf16(e_l - S_b); writes
- * scale2[b] = (1 / S_b, ((e_l - S_b) - v) / S_b) for the consumer that is linear in the plane's rows (the slab reduce of dX,
- * tcar_reduce_dact_onehot_scaled: softmax part scaled exactly, the one-hot's rounding residual added back in fp32); and writes
+ * scale2[b] = (1 / S_b, ((e_l - S_b) - v) / S_b) for the consumer that is linear in the plane's rows (the step's slab reduce of dX:
+ * softmax part scaled exactly, the one-hot's rounding residual added back in fp32); and writes
  * aps = bf16((ap_hi + ap_lo)[b, :] / S') with S' = e_l - v, the per-row scaled copy of the packed attout planes [B, ap_cols]
  * (inner ap_inner) that the dE GEMM contracts the UNSCALED plane with — v / S' = e_l / S' - 1 exactly: the one-hot part of dE is
  * exact, the rounding of v becomes a common factor 1 +- 2^-8 on the row's softmax part.  S_b >= ~1 by construction of the anchor; the
@@ -361,20 +358,11 @@ int tcar_gemm_bf16_ce_anchor(int M, int N, int K, const void* A_hi, const void* 
                              const void* A2_lo, const void* B2_hi, int64_t inner2, void* p_hi, int64_t p_inner, int64_t p_rows,
                              float* stats, int64_t stats_floats, const int32_t* label, float* lab_logit, int nsplit,
                              int32_t* group_width, int32_t* ngroups, void* stream);
-/* tcar_reduce_dact_onehot for the anchored form: the slab sums (and dP) of row m times scale2[m].x, plus scale2[m].y times
- * [E[label[m], 0 .. ic) | onehot(mwdhm[label[m]])] (E: fp32 candidate rows [n_items, ldE]), in front of the addend; no bias column sums */
-int tcar_reduce_dact_onehot_scaled(const float* slabs, int splitk, int M, int ic, int64_t ld, const float* addend, int64_t ld_add,
-                                   const float* y, int64_t ldy, const float* tclip, float* out, int64_t ldo, float* dP,
-                                   const float* scale2, const int32_t* label, const float* E, int64_t ldE, const int32_t* mwdhm,
-                                   int n_items, void* stream);
-/* The two halves of tcar_ce_finish for the catalog-sharded step (sharded.py), where the row statistics cross the ranks in between:
- *   tcar_ce_shard_stats  out3[b] = (max, sum exp(x - max), label score) of THIS shard's columns from the epilogue's per-group pairs;
- *                        the label score is 0 unless label[b] lies in [n0, n0 + n_loc)  (= tcar_softmax_stats without the logits)
+/* The second half of tcar_ce_finish for the catalog-sharded step (sharded.py), where the row statistics cross the ranks in between
+ * (tcar_shard_score folds the epilogue's per-group pairs into the shard's (max, sum exp(x - max), label score) rows itself):
  *   tcar_ce_rescale      plane[b, n] = e[b, n] exp(m_g - rowstat[b].x) rowstat[b].y - [n == label[b] - lab_off]; lab_window != 0: a
  *                        label outside [lab_off, lab_off + N) belongs to another shard, nothing is subtracted (0: clamped, as
  *                        tcar_ce_finish).  rowstat = (lse, 1) from tcar_softmax_combine_rowstat. */
-int tcar_ce_shard_stats(int B, int ngroups, const float* stats, const float* lab_logit, const int32_t* label, int n0, int n_loc,
-                        float* out3, void* stream);
 int tcar_ce_rescale(int B, int N, int group_width, int ngroups, const float* stats, const float* rowstat, const int32_t* label,
                     int lab_off, int lab_window, void* dl_hi, int64_t inner, void* stream);
 /* ---- one-hot form of the two scoring GRADIENT GEMMs (training steps, hi planes only) -------------------------------------------
@@ -711,7 +699,7 @@ int tcar_shard_pack_ids(int64_t n_live, int64_t n_total, int ldh, const int32_t*
                         const float* ce, const float* neg_fb, float weight, float* loss, void* stream);
 
 /* bumped whenever a struct layout or a signature in this header changes; the loader refuses a mismatch */
-#define TCAR_ABI_VERSION 29
+#define TCAR_ABI_VERSION 30
 int tcar_abi_version(void);
 /* hex digest of the sources this binary was compiled from (every .hip and .h under csrc, and this header): loaders compare it with the
  * digest of the sources they sit next to, so a stale binary is detected ("unknown" when built without the in-tree builder) */

@@ -793,57 +793,6 @@ __global__ __launch_bounds__(256) void attout_finish_kernel(const FinishArgs a) 
   }
 }
 
-// gradient of the candidate-side lookups: for every (n, k) clip-backward of d_et[n, k*ldt ...]
-__global__ __launch_bounds__(256) void cand_time_bwd_kernel(const CandArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // [139, ldt] accumulators + [5] norms
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int ldt = a.d.ldt, pt = 5 * ldt;
-  const int sub = ldt >> 2, gpw = 64 / sub;
-  const int grp = lane / sub, lin = lane - grp * sub;
-  float* acc = lds;
-  float* sq_acc = lds + 139 * ldt;
-  for (int i = tid; i < 139 * ldt + 8; i += 256) lds[i] = 0.f;
-  __syncthreads();
-  float sq[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  const long npairs = (long)a.d.n_items * 5;
-  const long wave_g = (long)blockIdx.x * 4 + (tid >> 6);
-  const long nwaves = (long)gridDim.x * 4;
-  for (long p0 = wave_g * gpw; p0 < npairs; p0 += nwaves * gpw) {
-    const long p = p0 + grp;
-    const bool valid = p < npairs;
-    const long pp = valid ? p : 0;
-    const int k = (int)(pp % 5);
-    const long n = pp / 5;
-    const int id = clampi(a.mwdhm[pp], 0, time_vocab(k) - 1);
-    float4 x = valid ? ld4(pick5(a.tab, k) + (long)id * ldt + lin * 4) : zero4();
-    float4 gy = valid ? ld4(a.d_et + n * pt + k * ldt + lin * 4) : zero4();
-    const float ss = group_sum(dot4(x, x), sub), dd = group_sum(dot4(x, gy), sub);
-    float ca, cb;
-    clip_bwd_coef(ss, dd, ca, cb);
-    if (valid) {
-      float4 gx = fma4(x, -cb, scale4(gy, ca));
-      const float q = dot4(gx, gx);
-#pragma unroll
-      for (int s = 0; s < 5; ++s) sq[s] += (s == k) ? q : 0.f;
-      atomic_add4(acc + (time_rowoff(k) + id) * ldt + lin * 4, gx);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    const float s = wave_sum(sq[i]);
-    if (lane == 0 && s != 0.f) atomicAdd(sq_acc + i, s);
-  }
-  __syncthreads();
-  for (int i = tid; i < 139 * ldt; i += 256) {
-    const float v = acc[i];
-    if (v != 0.f) atomicAdd(a.g.g_time[0] + i, v);
-  }
-  if (tid < 5) {
-    const float v = sq_acc[tid];
-    if (v != 0.f) atomicAdd(a.g.sqn + a.g.slot_time[tid], v);
-  }
-}
-
 // ---- candidate-side time gradient through a STATIC inverted index (deterministic, no atomics) ---------------
 // publish_time_MWDHM never changes, so the candidates that share table row (k, v) are listed once on the host:
 // inv_n[inv_off[r] .. inv_off[r+1]) for r = rowoff(k) + v.  The clip Jacobian depends only on the table row x, so
@@ -1524,25 +1473,6 @@ extern "C" int tcar_cand_time_fwd_bf16(const tcar_dims_t* d, const float* const 
   if (grid > 1024) grid = 1024;
   TCAR_SET_LDS_ONCE(cand_time_fwd_kernel, 160 * 1024);
   TCAR_LAUNCH(cand_time_fwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
-  TCAR_CHECK_LAUNCH();
-  return TCAR_OK;
-}
-
-extern "C" int tcar_cand_time_bwd(const tcar_dims_t* d, const float* const time_tab[5], const int32_t* mwdhm,
-                                  const float* d_et, const tcar_grads_t* g, void* stream) {
-  if (check_dims(d) || !time_tab || !mwdhm || !d_et || !g) return TCAR_E_ARG;
-  CandArgs a{};
-  a.d = *d;
-  for (int k = 0; k < 5; ++k) a.tab[k] = time_tab[k];
-  a.mwdhm = mwdhm; a.d_et = d_et; a.g = *g;
-  const size_t lds = ((size_t)139 * d->ldt + 8) * sizeof(float);
-  long npairs = (long)d->n_items * 5;
-  const int gpw = 64 / (d->ldt >> 2);
-  int grid = (int)((npairs / gpw + 4 * 16 - 1) / (4 * 16));   // >= 16 passes per wave
-  if (grid < 1) grid = 1;
-  if (grid > 512) grid = 512;
-  TCAR_SET_LDS_ONCE(cand_time_bwd_kernel, 160 * 1024);
-  TCAR_LAUNCH(cand_time_bwd_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
 }

@@ -1342,10 +1342,7 @@ extern "C" int tcar_ce_rescale(int B, int N, int group_width, int ngroups, const
   return tcar_ce_rescale_o(B, N, group_width, ngroups, stats, rowstat, label, lab_off, lab_window, dl_hi, inner, stream, nullptr);
 }
 
-extern "C" int tcar_ce_shard_stats(int B, int ngroups, const float* stats, const float* lab_logit, const int32_t* label, int n0,
-                                   int n_loc, float* out3, void* stream) {
-  return tcar_ce_shard_stats_a(B, ngroups, stats, lab_logit, label, n0, n_loc, out3, 0, stream);
-}
+// the epilogue's per-group pairs -> out3[b] = (max, sum exp(x - max), label score) of this shard's columns (tcar_softmax_stats without the logits);
 // anchored != 0: the pairs of the anchored epilogue -> out3[b] = (sum of the plane's rounded entries, sum of the exponentials, label's
 // accumulator), to be combined by tcar_softmax_combine_anchored
 int tcar_ce_shard_stats_a(int B, int ngroups, const float* stats, const float* lab_logit, const int32_t* label, int n0, int n_loc,
@@ -1447,18 +1444,6 @@ int tcar_reduce_dact_onehot_o(const float* slabs, int splitk, int M, int ic, int
               o ? o->wait : TcarWait{}, (o && o->rowfix) ? *o->rowfix : TcarRowFix{});
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
-}
-// ... of the anchored softmax form: scale2 [M, 2] = (1 / S_m, residual) as tcar_ce_anchor_fold leaves them, label [M], E fp32
-// candidate rows [n_items, ldE], mwdhm [n_items, 5] (TcarRowFix); no bias column sums
-extern "C" int tcar_reduce_dact_onehot_scaled(const float* slabs, int splitk, int M, int ic, int64_t ld, const float* addend,
-                                              int64_t ld_add, const float* y, int64_t ldy, const float* tclip, float* out, int64_t ldo,
-                                              float* dP, const float* scale2, const int32_t* label, const float* E, int64_t ldE,
-                                              const int32_t* mwdhm, int n_items, void* stream) {
-  if (!scale2 || !label || !E || !mwdhm || n_items <= 0 || ldE < ic || (ldE & 3) || !tcar_aligned16(E)) return TCAR_E_ARG;
-  const TcarRowFix fix{scale2, label, E, (long)ldE, mwdhm, n_items};
-  TcarOpt o;
-  o.rowfix = &fix;
-  return tcar_reduce_dact_onehot_o(slabs, splitk, M, ic, ld, addend, ld_add, y, ldy, tclip, out, ldo, dP, nullptr, nullptr, stream, &o);
 }
 extern "C" int tcar_reduce_dact_onehot(const float* slabs, int splitk, int M, int ic, int64_t ld, const float* addend, int64_t ld_add,
                                        const float* y, int64_t ldy, const float* tclip, float* out, int64_t ldo, float* dP,

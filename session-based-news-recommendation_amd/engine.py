@@ -166,6 +166,8 @@ WORK = ([(n, "r", c, F32, None) for n, c in (("x_icp", "ic"), ("x_pt", "pt"), ("
 # tcar_ctx_t fields that take the engine attribute of the same name: parameters / optimizer state, then the workspace
 CTX_STATE = ["E", "W", "Gx", "M", "V", "big", "Mi", "Vi", "sqn_dense", "use_dense", "mwdhm", "inv_n", "inv_off", "ct_ws", "et_perm",
              "adam_bitmap"]
+CTX_WS = ["x_icp", "x_pt", "x_act", "click_t", "pre1", "pre2", "q1", "q", "alpha", "pooled", "attout", "logits", "ce", "neg_fb", "loss",
+          "neg_coef", "negpart", "dattout", "dpooled", "dq", "dq1", "dclick", "slabs", "dx_icp", "dx_pt", "dx_act", "dpre1", "dpre2"]
 # the element-count field that goes with a pointer field
 CTX_SIZES = {"wgrad_slabs": "wgrad_slab_floats", "proj_slabs": "proj_slab_floats", "ce_ws": "ce_ws_floats", "segsum_ws": "segsum_bytes",
              "small_det_ws": "small_det_ws_floats", "fold_scratch": "fold_scratch_words"}
@@ -621,7 +623,7 @@ class TcarEngine(OpLevelStep):
         c.clip = float(self.max_grad) if self.max_grad else 0.0
         c.segs_all, c.segs_dense = self.segs_all, self.segs_dense
         c.scoring, c.scoring_bwd = self.scoring_code, self.scoring_bwd
-        for n in CTX_STATE + _lib._WS + ["rank", "topk"] + (["e16h", "e16l"] if self.scoring_code else []):
+        for n in CTX_STATE + CTX_WS + ["rank", "topk"] + (["e16h", "e16l"] if self.scoring_code else []):
             setattr(c, n, getattr(self, n).data_ptr())
         self.ws.bind(c, specs, CTX_SIZES)
         if form.det_colsums:

@@ -195,11 +195,8 @@ def test_order_fixed_pool_backward_and_column_sums():
     _need_gpu()
     import ctypes as C
     from tcar_amd import _lib
-    from tcar_amd._lib import Dims
+    from tcar_amd._lib import Colsum, Dims
     lib = _lib.load()
-
-    class Colsum(C.Structure):
-        _fields_ = [("x", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32), ("dst", C.c_void_p)]
     rng = np.random.RandomState(11)
     B, T, H, ldh, pt = 301, 5, 250, 256, 320
     ic = 2 * ldh

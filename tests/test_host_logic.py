@@ -16,6 +16,16 @@ from tcar_amd.host.synth import SynthFold
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+REMOVED_IN_ABI_30 = ("tcar_cand_time_bwd", "tcar_reduce_dact_onehot_scaled", "tcar_ce_shard_stats")
+# every prototype of the header: return type, name, parameter list (kept independent of the parser in _lib.py)
+PROTOTYPE = r"^(int|int64_t|float\*|const char\*) (tcar_\w+)\(([^()]*)\);"
+
+
+def _header() -> str:
+    """include/tcar_hip.h without its comments"""
+    return re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "tcar_hip.h")).read(), flags=re.S)
+
+
 def test_library_exports_every_declared_symbol():
     _lib.build()
     lib = _lib.load()
@@ -24,35 +34,66 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.SYMBOLS)
     for s in declared:
         assert hasattr(lib, s)
-    assert lib.tcar_abi_version() == _lib.ABI_VERSION == 29
+    for s in REMOVED_IN_ABI_30:
+        assert s not in declared and not hasattr(lib, s), s
+    assert lib.tcar_abi_version() == _lib.ABI_VERSION == 30
     # the binary carries the digest of the sources it was built from; the loader refuses a stale one
     assert lib.tcar_build_id().decode() == _lib.source_build_id() == _lib.binary_build_id()
     assert lib.tcar_gemm_splitk_effective(46080, 16) == 16
     assert lib.tcar_gemm_splitk_effective(64, 16) == 2
 
 
-def _header_struct_fields(header: str, name: str):
-    """field names of `typedef struct { ... } name;` in declaration order: comments stripped, declarators split"""
-    header = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
-    body = re.search(r"typedef struct \{([^{}]*)\}\s*%s\s*;" % name, header).group(1)
-    out = []
-    for decl in body.split(";"):
-        for d in decl.split(","):
-            m = re.search(r"(\w+)\s*(?:\[[^\]]*\])?\s*$", d.strip())
-            if m:
-                out.append(m.group(1))
-    return out
+def test_struct_mirrors_have_the_layout_the_compiler_gives_the_header(tmp_path):
+    """The ctypes mirrors are generated from include/tcar_hip.h (_lib._bind) and the engines fill tcar_ctx_t / tcar_shard_t BY NAME
+    from tables of (field, buffer).  A host-only C++ program that includes the header prints sizeof of every struct and offsetof /
+    sizeof of every field the parser named: a wrong name does not compile, a wrong type or order moves an offset."""
+    import subprocess
+    structs = re.findall(r"typedef struct \{[^{}]*\}\s*(tcar_\w+_t)\s*;", _header())
+    public = {"tcar_gemm_desc_t": "GemmDesc", "tcar_negsrc_t": "NegSrc"}
+    mirrors = {c: getattr(_lib, public.get(c) or c[5:-2].capitalize()) for c in structs}
+    assert len(structs) == 13 and len(mirrors["tcar_ctx_t"]._fields_) == 104 and len(mirrors["tcar_shard_t"]._fields_) == 25
+    lines = ['#include <cstddef>', '#include <cstdio>', '#include "tcar_hip.h"', 'int main() {']
+    for c, m in mirrors.items():
+        lines.append('  printf("%%zu\\n", sizeof(%s));' % c)
+        lines += ['  printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (c, f[0], c, f[0]) for f in m._fields_]
+    lines.append('  return 0;\n}')
+    src, exe = tmp_path / "layout.cpp", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([_lib._hipcc(), "-x", "c++", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = iter(subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.decode().split("\n"))
+    for c, m in mirrors.items():
+        assert int(next(got)) == C.sizeof(m), c
+        last = 0
+        for f in m._fields_:
+            d = getattr(m, f[0])
+            assert next(got).split() == [str(d.offset), str(d.size)], (c, f[0])
+            assert d.offset >= last, (c, f[0])              # offsets never decrease in declaration order
+            last = d.offset
 
 
-def test_struct_mirrors_have_the_header_field_names_in_order():
-    """The engines fill tcar_ctx_t / tcar_shard_t BY NAME from tables of (field, buffer): the ctypes mirrors must name every field
-    as the header does, in its order (the size check of _lib.load() passes two swapped pointers)."""
-    header = open(os.path.join(ROOT, "include", "tcar_hip.h")).read()
-    for name, mirror, n in (("tcar_ctx_t", _lib.Ctx, 104), ("tcar_shard_t", _lib.Shard, 25), ("tcar_batch_t", _lib.Batch, None),
-                            ("tcar_grads_t", _lib.Grads, None)):
-        got = _header_struct_fields(header, name)
-        assert got == [f[0] for f in mirror._fields_], name
-        assert n is None or len(got) == n, (name, len(got))
+def test_every_prototype_of_the_header_is_bound():
+    """argtypes / restype come from the declarations: every function has as many argtypes as the header gives it parameters (a
+    missing list would let ctypes truncate an int64_t), and a handful are pinned type for type."""
+    lib = _lib.load()
+    i32, i64, u64, vp, P = C.c_int32, C.c_int64, C.c_uint64, C.c_void_p, C.POINTER
+    protos = re.findall(PROTOTYPE, _header(), flags=re.M)
+    assert {name for _, name, _ in protos} == set(_lib.SYMBOLS) and len(protos) == len(_lib.SYMBOLS) == 112
+    for ret, name, params in protos:
+        f = getattr(lib, name)
+        n = 0 if params.strip() == "void" else params.count(",") + 1
+        assert f.argtypes is not None and len(f.argtypes) == n, (name, n)
+        assert f.restype is {"int": C.c_int, "int64_t": i64, "float*": vp, "const char*": C.c_char_p}[ret], name
+    assert lib.tcar_gemm_f32.argtypes == [i32, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, i32, i32, i32, vp]
+    assert lib.tcar_form_batch.argtypes == [P(_lib.Dims), P(_lib.Store), P(_lib.NegSrc), vp, i32, i32, i32, i32, u64, u64, vp, vp]
+    assert lib.tcar_cand_time_fwd.argtypes == [P(_lib.Dims), P(vp * 5), vp, vp, vp]
+    assert lib.tcar_gather_clip_bwd_sqnorm.argtypes == [P(_lib.Dims), P(_lib.Tables), P(_lib.Batch), vp, vp, vp, vp, P(_lib.Grads), vp,
+                                                        i64, vp, i64, vp]
+    assert lib.tcar_segsum_rows_buffer.restype is vp
+    assert lib.tcar_segsum_ws_bytes.restype is i64
+    assert lib.tcar_build_id.restype is C.c_char_p
+    # pointers to the tuning / column-sum / fold structs stay untyped: callers pass arrays cast to c_void_p and integer addresses
+    assert lib.tcar_tuning_defaults.argtypes == [vp] and lib.tcar_colsum_det.argtypes == [i32, vp, vp] == lib.tcar_fold_slabs.argtypes
+    assert _lib.TUNING_FIELDS == [f[0] for f in _lib.Tuning._fields_] and (_lib.NSLOT, _lib.NVAR) == (32, 22)
 
 
 def test_tuning_switch_defaults():
