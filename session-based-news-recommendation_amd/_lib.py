@@ -20,7 +20,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 #  it must carry the same source digest and ABI, and it is never built or overwritten by build())
 LIB_PATH = os.environ.get("TCAR_LIB") or os.path.join(PKG_DIR, "libtcar_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "embed.hip", "pool.hip", "score.hip", "optim.hip", "step.hip", "mha.hip",
-           "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "buildid.hip"]
+           "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "select.hip", "buildid.hip"]
 BUILD_ID_TU = "buildid.hip"        # the one translation unit that carries the digest of all sources
 
 
@@ -32,7 +32,8 @@ def _hipcc() -> str:
 
 
 HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_hip.h")       # the C ABI: compiled into the library AND read by _bind() below
-HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), HEADER]
+SERVE_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_serve.h")  # streamed score-and-select, layered on HEADER (read by _bind() too)
+HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), HEADER, SERVE_HEADER]
 _ID_MARK = b"TCAR_BUILD_ID="
 
 
@@ -47,7 +48,7 @@ def _digest(paths) -> str:
 
 
 def source_build_id() -> str:
-    """Digest of every source the library is compiled from (csrc/*.hip, the two csrc headers, include/tcar_hip.h) and of the
+    """Digest of every source the library is compiled from (csrc/*.hip, the two csrc headers, include/*.h) and of the
     code-generation flags every translation unit must be built with (SAFE_FLAGS): a binary built without them is stale."""
     import hashlib
     base = _digest([os.path.join(CSRC, s) for s in SOURCES] + HEADERS)
@@ -140,24 +141,22 @@ _OPAQUE = ("tcar_tuning_t", "tcar_colsum_t", "tcar_fold_t")
 _TYPE = re.compile(r"\s*(?:const\s+)?(\w+)")         # the type word a declaration starts with, `const` aside
 
 
-def _bind() -> None:
-    """Read the C ABI from the header: the constants, one ctypes.Structure per `typedef struct` (header order, so nested structs
-    resolve) and (restype, argtypes) of every declared function.  Defines them as attributes of this module, once."""
-    g = globals()
-    if "SYMBOLS" in g:
-        return
+def _read_header(path: str, const: dict, structs: dict):
+    """One header of the C ABI -> its constants and structs (added to `const` / `structs`, which may hold those of a header it
+    includes) and {function: (restype, argtypes)}.  Returns (public struct classes by name, prototypes)."""
     try:
-        with open(HEADER) as f:
+        with open(path) as f:
             text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
     except OSError as e:
-        raise TcarError("the bindings are generated from %s, which cannot be read (%s)" % (os.path.normpath(HEADER), e))
-    const = {k: int(v) for k, v in re.findall(r"^#define (TCAR_\w+) (\d+)\s*$", text, flags=re.M)}
+        raise TcarError("the bindings are generated from %s, which cannot be read (%s)" % (os.path.normpath(path), e))
+    const.update({k: int(v) for k, v in re.findall(r"^#define (TCAR_\w+) (\d+)\s*$", text, flags=re.M)})
     v = -1
-    for item in re.search(r"enum \{([^}]*)\}", text).group(1).split(","):
+    enum = re.search(r"enum \{([^}]*)\}", text)
+    for item in enum.group(1).split(",") if enum else ():
         name, _, val = item.partition("=")
         const[name.strip()] = v = int(val) if val.strip() else v + 1
 
-    structs = {}
+    classes = {}
     for body, cname in re.findall(r"typedef struct \{([^{}]*)\}\s*(tcar_\w+_t)\s*;", text):
         fields = []
         for decl in filter(str.strip, body.split(";")):
@@ -168,7 +167,7 @@ def _bind() -> None:
                 t = C.c_void_p if "*" in d else _SCALARS.get(base) or structs[base]
                 fields.append((name, t * (int(dim) if dim.isdigit() else const[dim]) if dim else t))
         pub = _CLASS_NAMES.get(cname) or "".join(w.capitalize() for w in cname[5:-2].split("_"))
-        structs[cname] = g[pub] = type(pub, (C.Structure,), {"_fields_": fields, "__doc__": "mirror of " + cname, "__module__": __name__})
+        structs[cname] = classes[pub] = type(pub, (C.Structure,), {"_fields_": fields, "__doc__": "mirror of " + cname, "__module__": __name__})
 
     def ctype(decl: str, ret: bool = False):
         base = _TYPE.match(decl).group(1)
@@ -184,8 +183,26 @@ def _bind() -> None:
     for ret, name, params in re.findall(r"^((?:const )?\w+\*?) (tcar_\w+)\(([^)]*)\)\s*;", text, flags=re.M):
         params = [] if params.strip() == "void" else params.split(",")
         protos[name] = (ctype(ret, True), [ctype(p) for p in params])
+    return classes, protos
+
+
+def _bind() -> None:
+    """Read the C ABI from the headers: the constants, one ctypes.Structure per `typedef struct` (header order, so nested structs
+    resolve) and (restype, argtypes) of every declared function.  Defines them as attributes of this module, once.  tcar_hip.h
+    gives SYMBOLS / ABI_VERSION / the struct mirrors; tcar_serve.h, which builds on it, its own names: SERVE_SYMBOLS,
+    SERVE_ABI_VERSION and the mirror Serve."""
+    g = globals()
+    if "SYMBOLS" in g:
+        return
+    const, structs = {}, {}
+    classes, protos = _read_header(HEADER, const, structs)
+    serve_const, serve_structs = dict(const), dict(structs)
+    serve_classes, serve_protos = _read_header(SERVE_HEADER, serve_const, serve_structs)
+    g.update(classes)
+    g.update(serve_classes)
     g.update(ABI_VERSION=const["TCAR_ABI_VERSION"], NSLOT=const["TCAR_NSLOT"], NVAR=const["TCAR_NVAR"], SYMBOLS=list(protos),
-             _PROTOTYPES=protos, TUNING_FIELDS=[f[0] for f in g["Tuning"]._fields_])
+             _PROTOTYPES=protos, TUNING_FIELDS=[f[0] for f in classes["Tuning"]._fields_],
+             SERVE_ABI_VERSION=serve_const["TCAR_SERVE_ABI_VERSION"], SERVE_SYMBOLS=list(serve_protos), _SERVE_PROTOTYPES=serve_protos)
 
 
 def __getattr__(name: str):
@@ -233,15 +250,17 @@ def load() -> C.CDLL:
         raise TcarError("libtcar_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + SERVE_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise TcarError("libtcar_hip.so lacks symbols: %s" % missing)
-    for s, (restype, argtypes) in _PROTOTYPES.items():
+    for s, (restype, argtypes) in list(_PROTOTYPES.items()) + list(_SERVE_PROTOTYPES.items()):
         f = getattr(lib, s)
         f.restype, f.argtypes = restype, argtypes
     if lib.tcar_abi_version() != ABI_VERSION:
         raise TcarError("libtcar_hip.so has ABI %d, these bindings expect %d: rebuild (python -c 'import __graft_entry__ "
                         "as g; g.build()')" % (lib.tcar_abi_version(), ABI_VERSION))
+    if lib.tcar_serve_abi_version() != SERVE_ABI_VERSION:
+        raise TcarError("libtcar_hip.so has serve ABI %d, these bindings expect %d: rebuild" % (lib.tcar_serve_abi_version(), SERVE_ABI_VERSION))
     # a binary built from other sources than the ones next to it is stale (the build is digest-gated, not mtime-gated)
     if have_sources():
         got, want = lib.tcar_build_id().decode(), source_build_id()

@@ -1,0 +1,370 @@
+// Streamed selection (include/tcar_serve.h): the catalog's scores arrive in column panels; every panel is folded into a small running
+// state per session — the k best (score, index) entries so far in list order, the count of scores strictly above the label's, and the
+// online softmax pair (max, sum exp) — and one finishing launch turns the state into top-k / rank / cross entropy.  No [B, N] matrix.
+//
+// List order: score descending, then index descending (np.argsort(x)[::-1], rank_topk_rows_kernel of score.hip).  It is a TOTAL order
+// over (score, item id), and a fold computes the exact k best of (state entries + panel columns) under it, so the list after the last
+// panel is the k best of the catalog whatever the partition and whatever order candidates arrive in LDS.
+#include "tcar_common.h"
+#include "tcar_bf16_layout.h"
+#include "../../include/tcar_serve.h"
+
+namespace {
+
+constexpr int SEL_NT = 512;             // threads of a fold workgroup
+constexpr int SEL_MAX_N = 512 * 4 * 24; // columns of a fold (row slice in registers: 24 float4 per thread)
+constexpr int SEL_MAX_K = 64;
+
+// state row of one session, 2k + 4 words: score[k] | index[k] (-1: empty) | count, max, sum, pad
+__host__ __device__ inline int sel_row_words(int k) { return 2 * k + 4; }
+
+__global__ __launch_bounds__(256) void select_reset_kernel(int B, int k, float* __restrict__ state) {
+  const int rw = sel_row_words(k);
+  const long n = (long)B * rw;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int w = (int)(i % rw);
+    if (w < k) state[i] = -INFINITY;
+    else if (w < 2 * k) reinterpret_cast<int*>(state)[i] = -1;
+    else if (w == 2 * k) reinterpret_cast<int*>(state)[i] = 0;
+    else state[i] = (w == 2 * k + 1) ? -INFINITY : 0.f;
+  }
+}
+
+// key order: a above b?
+__device__ __forceinline__ bool key_gt(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai > bi); }
+
+// One workgroup per session.  The row slice is read ONCE into registers (as in rank_topk_rows_kernel<512, R>); columns outside the
+// slice and excluded items become NaN after the statistics: a NaN compares false with everything, so it is never a candidate.
+template <int R>
+__global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int k,
+                                                              const int32_t* __restrict__ label, const float* __restrict__ lab_score,
+                                                              const int32_t* __restrict__ excl, int X, float* __restrict__ state) {
+  constexpr int NT = SEL_NT, NWV = NT / 64, CAP = 2 * NT;
+  __shared__ float shv[NWV];
+  __shared__ int shi[NWV];
+  __shared__ float shs[NWV];
+  __shared__ int shc[NWV];
+  __shared__ float candv[CAP];
+  __shared__ int candi[CAP];
+  __shared__ int ncand;
+  __shared__ int any_excl;
+  __shared__ unsigned exb[SEL_MAX_N / 32];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const float* row = panel + (long)b * ld;
+  float* st = state + (long)b * sel_row_words(k);
+  int* sti = reinterpret_cast<int*>(st);
+  const float ninf = -INFINITY, dead = __builtin_nanf("");
+  // ---- load: the slice, this thread's entry of the running list, the running statistics
+  float4 v[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int c = (tid + r * NT) * 4;
+    v[r] = (c < n) ? ld4(row + c) : make_float4(ninf, ninf, ninf, ninf);     // (c + 3 < ld: ld % 4 == 0 and n <= ld)
+  }
+  float sv = dead;                  // state entry `tid` of the list (tid < k), NaN when empty
+  int si = -1;
+  if (tid < k) {
+    si = sti[k + tid];
+    if (si >= 0) sv = st[tid];
+  }
+  const int old_cnt = sti[2 * k];
+  const float old_m = st[2 * k + 1], old_s = st[2 * k + 2];
+  const bool full = sti[2 * k - 1] >= 0;          // k entries so far: the last one bounds what can still enter
+  const float lastv = st[k - 1];
+  const int lasti = sti[2 * k - 1];
+  // exclusion bitmap of this slice (integer LDS atomics; idempotent)
+  if (tid == 0) any_excl = 0;
+  if (excl) {
+    for (int i = tid; i < (n + 31) / 32; i += NT) exb[i] = 0u;
+  }
+  __syncthreads();
+  if (excl) {
+    for (int i = tid; i < X; i += NT) {
+      const int e = excl[(long)b * X + i] - n0;
+      if (e >= 0 && e < n) { atomicOr(&exb[e >> 5], 1u << (e & 31)); any_excl = 1; }
+    }
+  }
+  // ---- statistics of the slice: strict-greater count (the label's own column left out by index), max, sum exp
+  const bool counting = lab_score != nullptr;
+  const float xl = counting ? lab_score[b] : 0.f;
+  const int labc = counting ? label[b] - n0 : -1;
+  int cnt = 0;
+  float m = ninf;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int c = (tid + r * NT) * 4;
+    if (c + 0 >= n) v[r].x = ninf;
+    if (c + 1 >= n) v[r].y = ninf;
+    if (c + 2 >= n) v[r].z = ninf;
+    if (c + 3 >= n) v[r].w = ninf;
+    if (counting)
+      cnt += (v[r].x > xl && c + 0 != labc) + (v[r].y > xl && c + 1 != labc) + (v[r].z > xl && c + 2 != labc) +
+             (v[r].w > xl && c + 3 != labc);
+    m = fmaxf(m, fmaxf(fmaxf(v[r].x, v[r].y), fmaxf(v[r].z, v[r].w)));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  m = wave_max(m);
+  if (lane == 0) { shc[w] = cnt; shv[w] = m; }
+  __syncthreads();
+  int tot = 0;
+  float gm = old_m;
+#pragma unroll
+  for (int i = 0; i < NWV; ++i) { tot += shc[i]; gm = fmaxf(gm, shv[i]); }
+  const int has_excl = any_excl;
+  __syncthreads();
+  {
+    // online softmax: m' = max(m, slice max), s = s exp(m - m') + sum exp(x - m'); fixed order within a launch
+    float se = 0.f;
+#pragma unroll
+    for (int r = 0; r < R; ++r) se += (expf(v[r].x - gm) + expf(v[r].y - gm)) + (expf(v[r].z - gm) + expf(v[r].w - gm));
+    se = wave_sum(se);
+    if (lane == 0) shs[w] = se;
+    __syncthreads();
+    if (tid == 0) {
+      float gs = 0.f;
+#pragma unroll
+      for (int i = 0; i < NWV; ++i) gs += shs[i];
+      if (gm > ninf) {
+        st[2 * k + 1] = gm;
+        st[2 * k + 2] = (old_m > ninf ? old_s * expf(old_m - gm) : 0.f) + gs;
+      }
+      sti[2 * k] = old_cnt + tot;
+    }
+    __syncthreads();
+  }
+  // ---- from here on the registers hold CANDIDATES: padding columns and excluded items die
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int c = (tid + r * NT) * 4;
+    unsigned bits = 0u;
+    if (has_excl && c < n) bits = exb[c >> 5] >> (c & 31);
+    if (c + 0 >= n || (bits & 1u)) v[r].x = dead;
+    if (c + 1 >= n || (bits & 2u)) v[r].y = dead;
+    if (c + 2 >= n || (bits & 4u)) v[r].z = dead;
+    if (c + 3 >= n || (bits & 8u)) v[r].w = dead;
+  }
+  // best of this thread's candidates (its columns + its state entry) strictly below the key (pv, pi)
+  auto scan = [&](float pv, int pi, float& bv, int& bi) __attribute__((always_inline)) {
+    bv = ninf; bi = -1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int c = n0 + (tid + r * NT) * 4;
+      const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = c + j;
+        if (key_gt(pv, pi, e[j], i) && key_gt(e[j], i, bv, bi)) { bv = e[j]; bi = i; }
+      }
+    }
+    if (key_gt(pv, pi, sv, si) && key_gt(sv, si, bv, bi)) { bv = sv; bi = si; }
+  };
+  // block-wide arg-max of one key per thread; (-inf, -1) = nothing.  Result to every thread.
+  auto block_best = [&](float bv, int bi, float& fv, int& fi) __attribute__((always_inline)) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) { shv[w] = bv; shi[w] = bi; }
+    __syncthreads();
+    fv = shv[0]; fi = shi[0];
+#pragma unroll
+    for (int j = 1; j < NWV; ++j)
+      if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; }
+    __syncthreads();
+  };
+  // Threshold L = (lv, li): at least k candidates are at or above it, so the k best are.  A full list gives one for free (its last
+  // entry: the k entries themselves are at or above it); else — or when too many columns pass it — the k-th largest of the
+  // per-thread bests (phase A of rank_topk_rows_kernel).
+  float lv = lastv;
+  int li = lasti;
+  float cbv = ninf;
+  int cbi = -1;
+  bool scanned = false;
+  auto phase_a = [&]() __attribute__((always_inline)) {
+    scan(INFINITY, 0x7fffffff, cbv, cbi);
+    scanned = true;
+    float av = cbv;
+    int ai = cbi;
+    lv = ninf; li = -1;
+    for (int r = 0; r < k; ++r) {
+      float fv; int fi;
+      block_best(av, ai, fv, fi);
+      if (fi < 0) { lv = ninf; li = -1; break; }        // fewer than k threads hold anything: every candidate qualifies
+      lv = fv; li = fi;
+      if (ai == fi) { av = ninf; ai = -1; }
+    }
+  };
+  auto compact = [&]() __attribute__((always_inline)) -> int {
+    if (tid == 0) ncand = 0;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int c = n0 + (tid + r * NT) * 4;
+      const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int i = c + j;
+        if (e[j] > lv || (e[j] == lv && i >= li)) {
+          const int pos = atomicAdd(&ncand, 1);
+          if (pos < CAP) { candv[pos] = e[j]; candi[pos] = i; }
+        }
+      }
+    }
+    if (sv > lv || (sv == lv && si >= li)) {
+      const int pos = atomicAdd(&ncand, 1);
+      if (pos < CAP) { candv[pos] = sv; candi[pos] = si; }
+    }
+    __syncthreads();
+    const int nc = ncand;
+    __syncthreads();
+    return nc;
+  };
+  if (!full) phase_a();
+  int nc = compact();
+  if (nc > CAP && full) {
+    phase_a();
+    nc = compact();
+  }
+  if (nc <= CAP) {
+    // k rounds over <= 2 candidates per thread
+    float c0v = tid < nc ? candv[tid] : ninf, c1v = tid + NT < nc ? candv[tid + NT] : ninf;
+    int c0i = tid < nc ? candi[tid] : -1, c1i = tid + NT < nc ? candi[tid + NT] : -1;
+    for (int r = 0; r < k; ++r) {
+      const bool first = key_gt(c0v, c0i, c1v, c1i);
+      float fv; int fi;
+      block_best(first ? c0v : c1v, first ? c0i : c1i, fv, fi);
+      if (tid == 0) { st[r] = fv; sti[k + r] = fi; }
+      if (c0i == fi) { c0v = ninf; c0i = -1; }
+      if (c1i == fi) { c1v = ninf; c1i = -1; }
+    }
+    return;
+  }
+  // Fallback (more than CAP candidates tie with or exceed L, e.g. a constant row): one entry per round; only the owner of the
+  // extracted entry rescans its registers
+  if (!scanned) scan(INFINITY, 0x7fffffff, cbv, cbi);
+  for (int r = 0; r < k; ++r) {
+    float fv; int fi;
+    block_best(cbv, cbi, fv, fi);
+    if (tid == 0) { st[r] = fv; sti[k + r] = fi; }
+    if (fi >= 0 && cbi == fi) scan(fv, fi, cbv, cbi);
+  }
+}
+
+__global__ __launch_bounds__(64) void select_finish_kernel(int k, const float* __restrict__ state, const float* __restrict__ lab_score,
+                                                           int32_t* __restrict__ topk, float* __restrict__ score,
+                                                           int32_t* __restrict__ rank, float* __restrict__ ce) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const float* st = state + (long)b * sel_row_words(k);
+  const int* sti = reinterpret_cast<const int*>(st);
+  if (t < k) {
+    const int i = sti[k + t];
+    if (topk) topk[(long)b * k + t] = i;
+    if (score && i >= 0) score[(long)b * k + t] = st[t];
+  }
+  if (t == 0) {
+    if (rank) rank[b] = 1 + sti[2 * k];
+    if (ce) ce[b] = st[2 * k + 1] + logf(st[2 * k + 2]) - lab_score[b];
+  }
+}
+
+// lab_score[b] = attout[b] . E[label[b]] over K columns, from the operands the panel GEMM contracts: one wave per session
+__global__ __launch_bounds__(64) void label_score_f32_kernel(int N, int K, const float* __restrict__ att, long ld_att,
+                                                             const float* __restrict__ E, long ldE, const int32_t* __restrict__ label,
+                                                             float* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int lab = clampi(label[b], 0, N - 1);
+  const float* a = att + (long)b * ld_att;
+  const float* e = E + (long)lab * ldE;
+  float s = 0.f;
+  for (int c = lane * 4; c < K; c += 256) s += dot4(ld4(a + c), ld4(e + c));
+  s = wave_sum(s);
+  if (lane == 0) out[b] = s;
+}
+__global__ __launch_bounds__(64) void label_score_bf16_kernel(int N, int K, const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo,
+                                                              int a_in32, const __bf16* __restrict__ e_hi,
+                                                              const __bf16* __restrict__ e_lo, int e_in32, int nsplit,
+                                                              const int32_t* __restrict__ label, float* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int lab = clampi(label[b], 0, N - 1);
+  float s = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    const long oa = kb32_off(b, c, a_in32), oe = kb32_off(lab, c, e_in32);
+    const float ah = (float)a_hi[oa], eh = (float)e_hi[oe];
+    float p = ah * eh;
+    if (nsplit == 3) p += ah * (float)e_lo[oe] + (float)a_lo[oa] * eh;       // the three products of the split-bf16 GEMM
+    s += p;
+  }
+  s = wave_sum(s);
+  if (lane == 0) out[b] = s;
+}
+
+}  // namespace
+
+extern "C" int tcar_serve_abi_version(void) { return TCAR_SERVE_ABI_VERSION; }
+
+extern "C" int64_t tcar_select_state_bytes(int B, int k) {
+  if (B < 0 || k < 1 || k > SEL_MAX_K) return -1;
+  return (int64_t)B * sel_row_words(k) * 4;
+}
+
+extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) {
+  if (B < 0 || k < 1 || k > SEL_MAX_K) return TCAR_E_ARG;
+  if (B == 0) return TCAR_OK;
+  if (!state || ((uintptr_t)state & 3)) return TCAR_E_ARG;
+  long blocks = ((long)B * sel_row_words(k) + 255) / 256;
+  if (blocks > 1024) blocks = 1024;
+  TCAR_LAUNCH(select_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, k, (float*)state);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+
+extern "C" int tcar_select_panel(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
+                                 const float* lab_score, const int32_t* excl, int X, void* state, void* stream) {
+  if (B < 0 || k < 1 || k > SEL_MAX_K || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
+  if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
+  if (B == 0 || n == 0) return TCAR_OK;
+  if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  float* st = (float*)state;
+  if (n <= SEL_NT * 4 * 2)
+    TCAR_LAUNCH((select_panel_kernel<2>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
+  else if (n <= SEL_NT * 4 * 8)
+    TCAR_LAUNCH((select_panel_kernel<8>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
+  else
+    TCAR_LAUNCH((select_panel_kernel<24>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+
+extern "C" int tcar_select_finish(int B, int k, const void* state, const float* lab_score, int32_t* topk, float* score, int32_t* rank,
+                                  float* ce, void* stream) {
+  if (B < 0 || k < 1 || k > SEL_MAX_K || (ce && !lab_score)) return TCAR_E_ARG;
+  if (B == 0) return TCAR_OK;
+  if (!state || !topk) return TCAR_E_ARG;
+  TCAR_LAUNCH(select_finish_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, k, (const float*)state, lab_score, topk, score, rank, ce);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+
+// planes: hi / lo KB32 of attout [ceil128(B), a_inner] and of E [ceil128(N), e_inner] (nsplit 1: hi only); NULL a_hi: fp32 operands
+int tcar_label_scores(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
+                      const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
+                      const int32_t* label, float* out, void* stream) {
+  if (B <= 0) return TCAR_OK;
+  if (N <= 0 || K <= 0 || !label || !out) return TCAR_E_ARG;
+  if (a_hi) {
+    if (!e_hi || (nsplit == 3 && (!a_lo || !e_lo)) || (nsplit != 1 && nsplit != 3) || (a_inner & 31) || (e_inner & 31) ||
+        a_inner < K || e_inner < K)
+      return TCAR_E_ARG;
+    TCAR_LAUNCH(label_score_bf16_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, N, K, (const __bf16*)a_hi, (const __bf16*)a_lo,
+                (int)(a_inner >> 5), (const __bf16*)e_hi, (const __bf16*)e_lo, (int)(e_inner >> 5), nsplit, label, out);
+  } else {
+    if (!att || !E || (K & 3) || (ld_att & 3) || (ldE & 3) || !tcar_aligned16(att) || !tcar_aligned16(E)) return TCAR_E_ARG;
+    TCAR_LAUNCH(label_score_f32_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, N, K, att, (long)ld_att, E, (long)ldE, label, out);
+  }
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}

@@ -3,6 +3,7 @@
 // aux stream joined by events — no host synchronisation, no allocation.  tcar_train_step == sess.run([loss, global_step, train_op]) (model_combine.py:231);
 // tcar_eval_step == sess.run([softmax_input, cross_loss]) + util.cau_metrics + top-k (model_combine.py:283,296,301).
 #include "tcar_common.h"
+#include "../../include/tcar_serve.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -517,7 +518,17 @@ int backward_prologue(const tcar_ctx_t* c, const tcar_batch_t* bt, hipStream_t s
   return TCAR_OK;
 }
 
-int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, void* stream, float rest_lr, bool train_index) {
+// Everything of a forward pass in front of the logits GEMM: the session forward -> c->attout (+ planes), the candidate-time refresh /
+// the rest pass of a pending split update on the aux stream, and the join of that stream into `stream`.  What the scoring launch
+// behind it needs to know comes back in `h`.  (forward_impl scores the whole catalog into c->logits or the softmax epilogue;
+// tcar_serve_step scores it panel by panel.)
+struct Head {
+  int ei = -1;                  // timing slot of this step (-1: none)
+  bool ce_epi = false, onehot = false, anchored = false, anchor_done = false;
+  CeWs w{};
+  hipStream_t s2 = nullptr;
+};
+int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, void* stream, float rest_lr, bool train_index, Head& h) {
   RET(check_ctx(c, bt));
   const Geo g(c->d);
   const int B = bt->B, BT = bt->B * bt->T;
@@ -591,7 +602,7 @@ int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
     ei = c->ev_cursor[0]++ % c->ev_n;
     c->ev_cursor[1] = ei;
   }
-  CeWs w;
+  CeWs w{};
   const bool ce_epi = c->scoring && train_index && fused_ce(c, B, &w);
   const bool onehot = ce_epi && onehot_fwd(c, B);
   ScoreOut so{c->p16h, c->p16l, oh_bwd ? c->tclip : nullptr, false};
@@ -623,6 +634,18 @@ int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
     RET(tcar_time_scores_clip(&c->d, tt, B, c->attout, g.ek, c->p16h, c->p16l, 160, oh_bwd ? c->tclip : nullptr, stream));
   }
   if (!joined && hipStreamWaitEvent(s1, (hipEvent_t)c->ev[1], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  h.ei = ei; h.ce_epi = ce_epi; h.onehot = onehot; h.anchored = anchored; h.anchor_done = so.anchor_done; h.w = w; h.s2 = s2;
+  return TCAR_OK;
+}
+
+int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, void* stream, float rest_lr, bool train_index) {
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, rest_lr, train_index, h));
+  const Geo g(c->d);
+  const int B = bt->B, ei = h.ei;
+  const bool ce_epi = h.ce_epi, onehot = h.onehot, anchored = h.anchored;
+  const CeWs& w = h.w;
+  hipStream_t s2 = h.s2;
   // logits = attout E^T (model_combine.py:138).  Optional HIP events bracket exactly the GEMM launch (bench.py roofline).
   auto start_timer = [&]() {
     if (ei >= 0) (void)hipEventRecord((hipEvent_t)c->ev_start[ei], (hipStream_t)stream);
@@ -635,7 +658,7 @@ int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
     start_timer();
     if (ce_epi && s2) ol.sig = fork_arm(c, FK_LOGITS);       // backward_prologue releases the aux stream behind this launch
     // the form the backward half of this step finds: anchored only when the finishing launch did leave the anchor partials
-    const bool anch = anchored && onehot && so.anchor_done;
+    const bool anch = anchored && onehot && h.anchor_done;
     if (c->ce_form) *c->ce_form = anch ? 1 : 0;
     ol.anchored = anch;
     if (ce_epi) {
@@ -1226,6 +1249,44 @@ extern "C" int tcar_eval_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
     return tcar_eval_rows(bt->B, g.N, c->logits, g.Npad, bt->label, k, c->rank, c->topk, c->ce, stream);
   RET(tcar_rank_topk(bt->B, g.N, c->logits, g.Npad, bt->label, k, c->rank, c->topk, stream));
   return tcar_softmax_ce(bt->B, g.N, c->logits, g.Npad, bt->label, c->ce, stream);
+}
+
+// Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, then the catalog in column
+// panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel while the panel is cache-warm.
+// A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row blocks).
+extern "C" int tcar_serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s, void* stream) {
+  if (!c || !bt || !s || bt->B < 0) return TCAR_E_ARG;
+  if (s->k < 1 || s->k > 64 || s->panel <= 0 || (s->panel & 127) || s->panel > 512 * 4 * 24) return TCAR_E_ARG;
+  if (!s->panel_buf || !s->state || !s->topk || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0)) return TCAR_E_ARG;
+  if (s->state_bytes < tcar_select_state_bytes(bt->B, s->k)) return TCAR_E_ARG;
+  if (bt->label && !s->lab_score) return TCAR_E_ARG;
+  if (bt->B == 0) return TCAR_OK;
+  RET(check_ctx(c, bt));
+  if (c->scoring ? (!c->a16h || !c->e16h || (c->scoring == 3 && (!c->a16l || !c->e16l))) : !c->attout) return TCAR_E_ARG;
+  const Geo g(c->d);
+  const int B = bt->B, k = s->k;
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
+  const float* lab = bt->label ? s->lab_score : nullptr;
+  if (lab)
+    RET(tcar_label_scores(B, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l,
+                          g.ek, c->scoring, bt->label, s->lab_score, stream));
+  RET(tcar_select_reset(B, k, s->state, stream));
+  for (int n0 = 0; n0 < g.N; n0 += s->panel) {
+    const int n = g.N - n0 < s->panel ? g.N - n0 : s->panel;
+    if (c->scoring) {
+      TcarOpt ol = opt_of(c);
+      const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
+      RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, c->a16h, c->a16l, g.ek, B, (const char*)c->e16h + off,
+                                c->e16l ? (const char*)c->e16l + off : nullptr, g.ek, g.Npad - n0, s->panel_buf, s->panel, nullptr, 0, 0,
+                                nullptr, 0, c->scoring, 1, stream, &ol));
+    } else {
+      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, s->panel_buf, s->panel, nullptr, 0, 0, 1, stream));
+    }
+    RET(tcar_select_panel(B, n0, n, s->panel_buf, s->panel, k, bt->label, lab, s->excl, s->X, s->state, stream));
+  }
+  return tcar_select_finish(B, k, s->state, lab, s->topk, s->score, lab ? s->rank : nullptr, lab ? s->ce : nullptr, stream);
 }
 
 

@@ -241,6 +241,11 @@ int tcar_clip_adam_rest_keep_o(float* w2d, int64_t ldw, const float* g2d, float*
                                uint32_t* bitmap, void* stream, int rest_grid);
 int tcar_softmax_ce_bf16_o(int B, int N, float* logits, int64_t ld, const int32_t* label, float* ce, void* dl_hi, void* dl_lo,
                            void* stream);
+// select.hip: out[b] = attout[b] . E[label[b]] over K columns from the operands a panel of the logits GEMM contracts — the KB32 planes
+// (a_hi != NULL; nsplit 3: hi hi + hi lo + lo hi, nsplit 1: hi only) or the fp32 matrices; labels are clamped to [0, N)
+int tcar_label_scores(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
+                      const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
+                      const int32_t* label, float* out, void* stream);
 
 // 16-byte write-through store (sc1): the bytes bypass the write-back state of this XCD's L2, so a consumer behind a completion
 // flag needs no release fence / L2 write-back from the producer (cdna_hip_programming.md Guideline 16, R1).  The compiler does not

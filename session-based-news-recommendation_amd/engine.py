@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Dims, Grads, Segments, Tables, check
+from ._lib import Batch, Dims, Grads, Segments, Serve, Tables, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -858,3 +858,88 @@ class TcarEngine(OpLevelStep):
         check(lib.tcar_softmax_ce(B, g.N, p(self.logits), g.Npad, C.c_void_p(bt.label), p(self.ce), st), "tcar_softmax_ce")
         out = (self.rank[:B], self.topk[:B], self.ce[:B])
         return out + (logits,) if keep_logits else out
+
+    # ---- streamed score-and-select (include/tcar_serve.h): evaluation and recommendation without the [B, N] logits
+    SERVE_MAX_PANEL = 49152        # columns one fold keeps in registers (tcar_select_panel)
+
+    def default_panel(self) -> int:
+        """Columns per panel when the caller names none: 49,152, the widest a fold takes (at most Npad) — at B = 512, k = 20 the
+        fastest of {4096, 8192, 16384, 32768, 49152} at both measured catalog sizes (N = 46,033: 0.306 ms per evaluation step against
+        0.322 at 16,384; N = 2^20: 4.13 against 5.02 ms; docs/EXPERIMENTS.md, streamed evaluation).  The panel buffer is then
+        work_B x 49,152 floats (96 MiB at B = 512); other batch sizes were not measured."""
+        return int(max(128, min(self.SERVE_MAX_PANEL, self.geo.Npad)))
+
+    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool):
+        """one tcar_serve_step; returns (rank, topk, ce, scores) views of the workspace (rank / ce only when `labelled`)"""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
+        if not 1 <= k <= 64:
+            raise ValueError("k must be in [1, 64]")
+        B = bt.B
+        self._ensure_work(B, bt.T)
+        panel = self.default_panel() if not panel else int(panel)
+        if panel <= 0 or panel % 128 or panel > self.SERVE_MAX_PANEL:
+            raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
+        panel = min(panel, g.Npad)
+        wb = self.work_B
+        state_words = 2 * k + 4                  # tcar_select_state_bytes(B, k) / (4 B)
+        specs = [Spec("panel_buf", (wb, panel), F32), Spec("sel_state", (wb, state_words), I32), Spec("lab_score", (wb,), F32),
+                 Spec("sel_score", (wb, k), F32), Spec("sel_topk", (wb, k), I32), Spec("sel_rank", (wb,), I32), Spec("sel_ce", (wb,), F32)]
+        if excl is not None:
+            specs.append(Spec("excl", (wb, int(excl.shape[1])), I32))
+        self.ws.ensure(specs)
+        assert self.lib.tcar_select_state_bytes(B, k) <= self.sel_state.numel() * 4
+        s = Serve()
+        s.k, s.panel = k, panel
+        s.panel_buf, s.state, s.state_bytes = self.panel_buf.data_ptr(), self.sel_state.data_ptr(), self.sel_state.numel() * 4
+        s.lab_score = self.lab_score.data_ptr()
+        if excl is not None:
+            self.excl[:B].copy_(excl)
+            s.excl, s.X = self.excl.data_ptr(), int(excl.shape[1])
+        s.topk, s.score, s.rank, s.ce = (t.data_ptr() for t in (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
+        if not labelled:
+            bt = self._without_label(bt)
+        check(self.lib.tcar_serve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), self._stream()),
+              "tcar_serve_step")
+        self._time_dirty = False
+        self.poll_fork_errors()
+        return self.sel_rank[:B], self.sel_topk[:B], self.sel_ce[:B], self.sel_score[:B]
+
+    @staticmethod
+    def _without_label(bt: Batch) -> Batch:
+        nb = Batch()
+        C.memmove(C.byref(nb), C.byref(bt), C.sizeof(Batch))
+        nb.label, nb.neg, nb.K = None, None, 0
+        nb._keep = getattr(bt, "_keep", None)
+        return nb
+
+    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None):
+        """eval_step without the [B, N] score matrix: the catalog is scored `panel` columns at a time and folded into a running
+        top-k / rank / softmax state per session.  Returns (rank[B] int32, topk[B,k] int32, ce[B] f32) — views of the workspace,
+        valid until the next streamed call.  `last_scores` holds the fp32 scores of the lists."""
+        self.flush()
+        bt = bt or self.upload(batch)
+        rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True)
+        return rank, topk, ce
+
+    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None):
+        """The k best next items of every session: (topk [B,k] int32, scores [B,k] f32), best first (score, then item id,
+        descending); -1 where fewer than k items remain.  `batch` needs no "label" and no "neg".  exclude_seen drops the items of
+        the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot)."""
+        self.flush()
+        if "label" not in batch:
+            batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
+        if "neg" in batch:
+            batch = {n: v for n, v in batch.items() if n != "neg"}
+        bt = self.upload(batch)
+        parts = []
+        if exclude_seen:                 # built on the device from the uploaded ids: 1-based, so id 0 (a pad) becomes -1
+            parts.append(bt._seq_t.view(bt.B, bt.T) - 1)
+        if exclude is not None:
+            ex = np.ascontiguousarray(np.asarray(exclude, dtype=np.int32).reshape(bt.B, -1))
+            if ex.shape[1]:
+                parts.append(torch.from_numpy(ex).to(self.dev))
+        excl = torch.cat(parts, dim=1).contiguous() if parts else None
+        _, topk, _, scores = self._serve(bt, k, panel, excl, False)
+        return topk, scores

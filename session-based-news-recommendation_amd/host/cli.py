@@ -68,11 +68,23 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dp_mode", default="replica", choices=["replica", "sharded"],
                     help="multi-GPU exchange: replica = all-reduce of the dense item gradient (dp.py); sharded = catalog-sharded "
                          "scoring (sharded.py: the item gradient stays on the rank that owns the rows)")
+    ap.add_argument("--eval_panel", default=0, type=int,
+                    help="P > 0: evaluation scores the catalog P columns at a time and selects while it streams (no [B, N] score matrix, "
+                         "any catalog size; P % 128 == 0, P <= 49152).  0: the materialised evaluation.  Not with --dp_mode sharded")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
     ap.add_argument("--seed", default=2020, type=int)
     return ap
+
+
+def check_eval_panel(eval_panel, dp_mode):
+    """--eval_panel is the single-engine streamed evaluation: the catalog-sharded engine keeps its own evaluation"""
+    if eval_panel and dp_mode == "sharded":
+        raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded "
+                         "(the catalog-sharded engine evaluates with its own exchange)")
+    if eval_panel and (eval_panel < 0 or eval_panel % 128 or eval_panel > 49152):
+        raise ValueError("--eval_panel must be a multiple of 128 in [128, 49152] (0: off)")
 
 
 def load_datas(args):
@@ -130,6 +142,7 @@ def main(argv=None):
     random.seed(args.seed)                       # main.py:10-12
     np.random.seed(args.seed)
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
+    check_eval_panel(args.eval_panel, args.dp_mode)
     dp_group = None
     if args.gpus > 1:
         import torch

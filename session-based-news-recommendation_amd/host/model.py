@@ -137,6 +137,9 @@ class Seq2SeqAttNN():
         self.neg_fast = bool(args.get('neg_fast', 0))
         self.device_sampler = bool(args.get('device_sampler', 0))   # form batches + draw negatives on the GPU
         self.seed = int(args.get('seed', 2020))
+        self.eval_panel = int(args.get('eval_panel', 0) or 0)       # > 0: test() selects while the catalog streams by in panels
+        if self.eval_panel and args.get('dp_mode', 'replica') == 'sharded':
+            raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded")
         self._ds_cache = {}
         self.curEpoch = 0
         self.error_during_train = False
@@ -327,13 +330,19 @@ class Seq2SeqAttNN():
             eng.set_categories(cat)
             self._cat_on_engine = cat
         eng.reset_coverage()
+        panel = int(args.get('eval_panel', self.eval_panel) or 0)
+        if panel and args.get('dp_mode', 'replica') == 'sharded':
+            raise ValueError("eval_panel cannot be combined with dp_mode sharded")
         for feed in prefetch_batches(sampler):
             batch += 1
             feed, _cap = self._shard(feed)           # data parallel: every rank scores its shard of the batch
             if feed is None:
                 continue
             bt = eng.upload(feed)
-            rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
+            if panel:            # streamed: no [B, N] score matrix (engine.eval_step_streamed)
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel)
+            else:
+                rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
             ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)
             pending.append((feed, rank.clone(), topk.clone() if args.get('is_print') else None, ce.clone(), ild_c, unexp_c, n_rec))     # device results; drained below
             if batch < 3:
@@ -373,3 +382,10 @@ class Seq2SeqAttNN():
         self.last_metrics = {"mrr": m_mrr, "recall": m_hit, "ndcg": m_ndcg, "loss": m_loss, "ild": m_ild,
                              "unexp": m_unexp, "coverage": n_covered}
         return m_hit
+
+    # ---------------------------------------------------------------------------------------- recommend
+    def recommend(self, sessions, k=20, **kw):
+        """The k best next items of every session of `sessions` — a feed dict as the samplers build it (seq, pm, pd, pw, ph, pmi,
+        gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
+        has already read are left out (engine.TcarEngine.recommend has the options)."""
+        return self.engine.recommend(sessions, k=k, **kw)

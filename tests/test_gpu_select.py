@@ -1,0 +1,152 @@
+"""Streamed selection at the op level (include/tcar_serve.h: tcar_select_reset / _panel / _finish) against numpy, exactly.
+
+One fp32 matrix x [B, ldn] per catalog size, built as in test_eval_rows_rank_topk_ce; the panels are pointer views into it.  The
+list, its scores and the rank follow a total order, so they must be the same bits for every partition and on every run."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import tcar_amd  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-3
+# N -> panel sizes: the largest allowed (ceil128(N), at most 49,152) and a smaller one
+PANELS = {7: (128,), 1003: (1024, 128), 20001: (20096, 4096), 49200: (49152, 8192), 70001: (49152, 8192)}
+KS = (1, 20, 64)
+
+
+def _need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+def close(got, want, rtol=RTOL, atol_scale=2e-5, name=""):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    scale = max(float(np.abs(want).max()), 1e-30)
+    err = np.abs(got - want)
+    bad = err > rtol * np.abs(want) + atol_scale * scale + 1e-9
+    assert not bad.any(), "%s: %d/%d off, max err %.3e (scale %.3e)" % (name, bad.sum(), bad.size, err.max(), scale)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    _need_gpu()
+    from tcar_amd import _lib
+    return _lib.load()
+
+
+def ptr(t, off=0):
+    return C.c_void_p(t.data_ptr() + 4 * off)
+
+
+_CASES = {}
+
+
+def case(N):
+    """inputs and the numpy reference of one catalog size: computed once, shared by every k and partition, never written"""
+    if N in _CASES:
+        return _CASES[N]
+    from oracle.metrics_oracle import topk_list
+    rng = np.random.RandomState(N)
+    B = 6
+    ldn = (N + 127) // 128 * 128
+    x = (rng.standard_normal((B, ldn)) * 2).astype(np.float32)      # rows 0 and 4: random
+    x[1, :N] = -0.75                                      # all-tie row: top-k is the highest indices
+    x[2, : N // 2] = x[2, 0]                              # half the row tied at one value
+    x[3, N - 1] = 50.0                                    # the winner sits in the last column
+    P = min(PANELS[N])
+    if N > P:                                             # the 20 largest values straddle the first panel boundary
+        x[5, P - 10:P + 10] = 100.0 + rng.permutation(20).astype(np.float32)
+    if N > 49152:                                         # and the next 20 the boundary of the largest panel
+        x[5, 49152 - 10:49152 + 10] = 60.0 + rng.permutation(20).astype(np.float32)
+    x[:, N:] = 1e9                                        # padding columns must never be picked
+    lab = np.array([0, N - 1, N // 3, N - 1, min(5, N - 1), N // 2], np.int32)
+    xv = x[:, :N].astype(np.float64)
+    ref = {"x": x, "lab": lab, "B": B, "ldn": ldn,
+           "top": [topk_list(x[b, :N], 64) for b in range(B)],
+           "rank": ((xv > xv[np.arange(B), lab][:, None]).sum(1) + 1).astype(np.int32),
+           "ce": np.log(np.exp(xv - xv.max(1, keepdims=True)).sum(1)) + xv.max(1) - xv[np.arange(B), lab]}
+    for v in ref.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    _CASES[N] = ref
+    return ref
+
+
+def run(lib, ref, N, k, P, excl=None):
+    """reset, one tcar_select_panel per panel of P columns (the last one partial), finish -> numpy outputs"""
+    B, ldn = ref["B"], ref["ldn"]
+    d = torch.tensor(ref["x"]).cuda()
+    dl = torch.tensor(ref["lab"]).cuda()
+    ls = d[torch.arange(B), dl.long()].contiguous()       # gathered from x: exact
+    state = torch.empty(int(lib.tcar_select_state_bytes(B, k)) // 4, dtype=torch.int32, device="cuda")
+    topk = torch.full((B, k), -7, dtype=torch.int32, device="cuda")
+    score = torch.full((B, k), -7.0, device="cuda")
+    rank = torch.empty(B, dtype=torch.int32, device="cuda")
+    ce = torch.empty(B, device="cuda")
+    de, X = (torch.tensor(excl).cuda(), excl.shape[1]) if excl is not None else (None, 0)
+    assert lib.tcar_select_reset(B, k, ptr(state), None) == 0
+    for n0 in range(0, N, P):
+        assert lib.tcar_select_panel(B, n0, min(P, N - n0), ptr(d, n0), ldn, k, ptr(dl), ptr(ls), ptr(de) if X else None, X,
+                                     ptr(state), None) == 0
+    assert lib.tcar_select_finish(B, k, ptr(state), ptr(ls), ptr(topk), ptr(score), ptr(rank), ptr(ce), None) == 0
+    torch.cuda.synchronize()
+    assert (d.cpu().numpy() == ref["x"]).all()            # the scores are left untouched
+    return topk.cpu().numpy(), score.cpu().numpy(), rank.cpu().numpy(), ce.cpu().numpy()
+
+
+def check_lists(ref, N, k, tk, sc, want_lists):
+    x = ref["x"]
+    for b in range(ref["B"]):
+        want = want_lists[b][:k]
+        assert tk[b].tolist() == want + [-1] * (k - len(want)), (b, tk[b].tolist(), want)
+        n = len(want)
+        assert (sc[b, :n].view(np.int32) == x[b, want].view(np.int32)).all(), b           # bit for bit
+        assert (sc[b, n:] == -7.0).all(), b                                               # untouched where the list ends
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("N", sorted(PANELS))
+def test_streamed_selection_is_exact_for_every_partition(lib, N, k):
+    ref = case(N)
+    outs = []
+    for P in PANELS[N] + (PANELS[N][0],):                 # every partition, the first one twice (two runs)
+        tk, sc, rank, ce = run(lib, ref, N, k, P)
+        check_lists(ref, N, k, tk, sc, ref["top"])
+        assert (rank == ref["rank"]).all(), (P, rank, ref["rank"])
+        close(ce, ref["ce"], name="ce P=%d" % P)
+        outs.append((tk, sc, rank))
+    for o in outs[1:]:
+        for a, b in zip(outs[0], o):
+            assert a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("N", sorted(PANELS))
+def test_excluded_items_leave_the_list_only(lib, N, k):
+    from oracle.metrics_oracle import topk_list
+    ref = case(N)
+    B, x = ref["B"], ref["x"]
+    P = min(PANELS[N])
+    X = 8
+    excl = np.full((B, X), -1, np.int32)
+    for b in range(B):
+        top1 = ref["top"][b][0]
+        if N == 7:
+            excl[b, :6] = [top1, (top1 + 1) % 7, (top1 + 2) % 7, (top1 + 3) % 7, (top1 + 4) % 7, top1]     # five of the seven, one twice
+        else:
+            other = (top1 + P) % N if N > P else (top1 + 3) % N       # an item of another panel
+            excl[b, [0, 2, 5, 6]] = [top1, other, top1, ref["top"][b][min(3, N - 1)]]                     # slots 1, 3, 4, 7 stay empty
+    want = []
+    for b in range(B):
+        keep = np.setdiff1d(np.arange(N), excl[b][excl[b] >= 0])        # ascending ids of the items that stay
+        want.append([int(keep[j]) for j in topk_list(x[b, keep], k)])
+    plain = {Pp: run(lib, ref, N, k, Pp) for Pp in PANELS[N]}
+    for Pp in PANELS[N]:
+        tk, sc, rank, ce = run(lib, ref, N, k, Pp, excl)
+        check_lists(ref, N, k, tk, sc, want)
+        assert (rank == plain[Pp][2]).all() and ce.tobytes() == plain[Pp][3].tobytes()      # count and softmax see every item

@@ -1,25 +1,62 @@
-"""Evaluation-step throughput (forward + rank / top-20 + CE) at the Globo shape.  Usage: python tools/eval_bench.py [iters]"""
-import os, sys, time
+"""Evaluation-step throughput (forward + rank / top-20 + CE), B = 512, k = 20.
+Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]]] [--rounds R]
+
+Without --streamed: eval_step (materialised [B, N] scores) at the Globo shape, as before.  With --streamed: eval_step and
+eval_step_streamed at every panel size named (default: the engine's default panel), alternating in the same process for `rounds`
+rounds so that the spread between rounds is visible; the streamed results are compared with eval_step's at the timed size."""
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import tcar_amd  # noqa
 from tcar_amd.host.synth import SynthFold
 from tcar_amd.host.model import initial_variables
 from tcar_amd.engine import TcarEngine
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import build_batches, CONFIGS
-iters = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-fold = SynthFold(n_items=46033, dim=250, n_train=60000, n_test=1000, seed=2020)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("iters", nargs="?", type=int, default=100)
+ap.add_argument("--n_items", type=int, default=46033)
+ap.add_argument("--streamed", action="store_true")
+ap.add_argument("--panel", type=str, default="", help="comma-separated panel sizes (multiples of 128, <= 49152); empty: the default panel")
+ap.add_argument("--rounds", type=int, default=2)
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("eval_bench needs the GPU: nothing is measured without it")
+N, B, iters = a.n_items, 512, a.iters
+fold = SynthFold(n_items=N, dim=250, n_train=60000, n_test=1000, seed=2020, **(dict(lean=True) if N > 200000 else {}))
 np.random.seed(2020)
-eng = TcarEngine(initial_variables(46033, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
-batches = build_batches(fold, 16, 512, 0, np.random.RandomState(1), CONFIGS["globo"])
+eng = TcarEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
+batches = build_batches(fold, 16, B, 0, np.random.RandomState(1), CONFIGS["globo"])
 res = [eng.make_resident(b) for b in batches]
-for i in range(5):
-    eng.eval_step(None, bt=res[i % len(res)])
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for i in range(iters):
-    eng.eval_step(None, bt=res[i % len(res)])
-torch.cuda.synchronize()
-dt = (time.perf_counter() - t0) / iters
-print("eval step: %.3f ms  = %.0f sessions/s" % (dt * 1e3, 512 / dt))
+
+
+def timed(step):
+    for i in range(5):
+        step(res[i % len(res)])
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(iters):
+        step(res[i % len(res)])
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
+
+
+plain = lambda bt: eng.eval_step(None, bt=bt)
+if not a.streamed:
+    dt = timed(plain)
+    print("eval step: %.3f ms  = %.0f sessions/s" % (dt * 1e3, B / dt))
+    sys.exit(0)
+panels = [int(p) for p in a.panel.split(",") if p] or [0]
+# same results?  (the panel GEMM may take another tile than the whole-catalog launch: the scores may differ in the last bits)
+r0, t0, c0 = [x.clone() for x in eng.eval_step(None, bt=res[0])]
+for P in panels:
+    r1, t1, c1 = eng.eval_step_streamed(None, bt=res[0], panel=P or None)
+    print("N=%d panel=%s: rank equal %.4f, top-20 rows equal %.4f, max |ce diff| %.2e" % (
+        N, P or eng.default_panel(), (r0 == r1).float().mean().item(), (t0 == t1).all(1).float().mean().item(), (c0 - c1).abs().max().item()))
+for rnd in range(a.rounds):
+    dt = timed(plain)
+    print("N=%d round %d eval_step (materialised): %.3f ms = %.0f sessions/s" % (N, rnd, dt * 1e3, B / dt))
+    for P in panels:
+        dt = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None))
+        print("N=%d round %d eval_step_streamed panel=%d: %.3f ms = %.0f sessions/s" % (N, rnd, P or eng.default_panel(), dt * 1e3, B / dt))
+    sys.stdout.flush()
