@@ -103,6 +103,12 @@ void grads_of(const tcar_ctx_t* c, tcar_grads_t& g) {
   g.slot_item = c->slot_item; g.slot_pos = c->slot_of[TCAR_V_POS]; g.slot_dur = c->slot_of[TCAR_V_DUR];
   g.rows_out = nullptr; g.norms_out = nullptr; g.rows_ld = 0; g.skip_small = 0;
 }
+// the five time tables (month, day, week, hour, minute) as the candidate-side launchers take them
+inline void time_tables(const tcar_ctx_t* c, const float* (&tt)[5]) {
+  for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+}
+// does this step carry the sampled negative term?
+inline bool has_negatives(const tcar_ctx_t* c, const tcar_batch_t* bt) { return bt->K > 0 && bt->neg && c->neg_coef && c->negpart; }
 
 // the small contractions follow the scoring precision: exact fp32 MFMA in "f32" mode, split-bf16 otherwise
 // `o`: launch options (context tuning; the completion flag this launch is to carry — split-bf16 form only)
@@ -211,29 +217,25 @@ inline const ForkSlot* fork_live(const tcar_ctx_t* c, int slot) {
   ForkHost* f = fork_host(c);
   return (f && f->slot[slot].live) ? &f->slot[slot] : nullptr;
 }
-inline int fork_go(const tcar_ctx_t* c, int slot, hipStream_t from, hipStream_t to, void* ev, int delay_us = 0) {
-  if (const ForkSlot* s = fork_live(c, slot)) {
-    TCAR_LAUNCH(poll_flag_kernel, dim3(1), dim3(64), 0, to, (const unsigned*)s->sig.flag, s->sig.epoch, c->sig_dev + TCAR_SIG_ERR,
-                c->sig_err_host, POLL_TICKS, (const unsigned*)nullptr, 0u, delay_us * 100);
-    TCAR_CHECK_LAUNCH();
-    return TCAR_OK;
-  }
-  if (hipEventRecord((hipEvent_t)ev, from) != hipSuccess || hipStreamWaitEvent(to, (hipEvent_t)ev, 0) != hipSuccess) return TCAR_E_LAUNCH;
+// ---- the ordering vocabulary of the drivers: every event record / wait and every poll of the step is one of these four
+inline int record(hipStream_t on, void* ev) { return hipEventRecord((hipEvent_t)ev, on) == hipSuccess ? TCAR_OK : TCAR_E_LAUNCH; }
+inline int wait_for(hipStream_t s, void* ev) { return hipStreamWaitEvent(s, (hipEvent_t)ev, 0) == hipSuccess ? TCAR_OK : TCAR_E_LAUNCH; }
+// `to` behind everything `from` holds so far
+inline int order(hipStream_t from, hipStream_t to, void* ev) {
+  RET(record(from, ev));
+  return wait_for(to, ev);
+}
+// one polling wave on `to`: waits for the epoch of `a` (and of `b` first, when it names a flag: the join of two streams), then
+// holds `to` back for `delay_ticks` of the wall clock
+inline int poll(const tcar_ctx_t* c, hipStream_t to, const TcarSignal& a, const TcarSignal& b = TcarSignal{}, int delay_ticks = 0) {
+  TCAR_LAUNCH(poll_flag_kernel, dim3(1), dim3(64), 0, to, (const unsigned*)a.flag, a.epoch, c->sig_dev + TCAR_SIG_ERR, c->sig_err_host,
+              POLL_TICKS, (const unsigned*)b.flag, b.epoch, delay_ticks);
+  TCAR_CHECK_LAUNCH();
   return TCAR_OK;
 }
-
-// join of TWO producers into `to`: one polling kernel when both forks are flag forks, else each on its own (poll or event)
-inline int fork_go2(const tcar_ctx_t* c, int slot_a, hipStream_t from_a, void* ev_a, int slot_b, hipStream_t from_b, void* ev_b, hipStream_t to) {
-  const ForkSlot* a = fork_live(c, slot_a);
-  const ForkSlot* b = fork_live(c, slot_b);
-  if (a && b) {
-    TCAR_LAUNCH(poll_flag_kernel, dim3(1), dim3(64), 0, to, (const unsigned*)a->sig.flag, a->sig.epoch, c->sig_dev + TCAR_SIG_ERR,
-                c->sig_err_host, POLL_TICKS, (const unsigned*)b->sig.flag, b->sig.epoch, 0);
-    TCAR_CHECK_LAUNCH();
-    return TCAR_OK;
-  }
-  RET(fork_go(c, slot_a, from_a, to, ev_a));
-  return fork_go(c, slot_b, from_b, to, ev_b);
+inline int fork_go(const tcar_ctx_t* c, int slot, hipStream_t from, hipStream_t to, void* ev, int delay_us = 0) {
+  if (const ForkSlot* s = fork_live(c, slot)) return poll(c, to, s->sig, TcarSignal{}, delay_us * 100);
+  return order(from, to, ev);
 }
 
 __global__ void set_flag_kernel(unsigned* flag, unsigned epoch) {
@@ -301,8 +303,7 @@ int forward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
 // does the fused step add the item-row gradients through the sorted segmented sum?
 bool sorted_rows(const tcar_ctx_t* c, const tcar_batch_t* bt) {
   if (!aux_stream(c) || !c->segsum_ws || !tn(c).sort_scatter || c->d.ldh > 512) return false;
-  const bool has_neg = bt->K > 0 && bt->neg && c->neg_coef && c->negpart;
-  return c->segsum_bytes >= tcar_segsum_ws_bytes(&c->d, (int64_t)bt->B * (bt->T + (has_neg ? bt->K : 0)));
+  return c->segsum_bytes >= tcar_segsum_ws_bytes(&c->d, (int64_t)bt->B * (bt->T + (has_negatives(c, bt) ? bt->K : 0)));
 }
 }  // namespace
 
@@ -450,7 +451,7 @@ int session_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const Geo& g, v
     p[1] = prob1(B, g.pt, c->pooled + g.ic, g.ek, W(c, TCAR_V_OT_W), g.pt, g.pt, c->proj_slabs + g.ic, g.ek, nullptr, 0, 0, na_pt);
     RET(small_gemm(c, 0, 2, p, stream));
     const float* tt[5];
-    for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+    time_tables(c, tt);
     RET(tcar_attout_finish_scores_a(&c->d, tt, B, c->proj_slabs, na_ic, na_pt, astride, W(c, TCAR_V_O_B), W(c, TCAR_V_OT_B), c->attout,
                                     g.ek, planes ? c->a16h : nullptr, planes ? c->a16l : nullptr, g.ek, planes ? c->ap16h : nullptr,
                                     planes ? c->ap16l : nullptr, g.ldh + g.pt, so ? so->p_hi : nullptr, so ? so->p_lo : nullptr, 160,
@@ -499,6 +500,22 @@ int zero_arena(const tcar_ctx_t* c, hipStream_t s) {
   return TCAR_OK;
 }
 
+// REST pass of a pending split update on the aux stream `s2`: every item row the early pass left out, then `between()` (what else
+// the aux stream owes the waiter), then `ev` = "aux stream ready", then the clear of the row marks
+template <class Between>
+int rest_pass(const tcar_ctx_t* c, const Geo& g, float lr, hipStream_t s2, void* ev, Between between) {
+  const float* pieces = c->Gx + c->arena_n;
+  RET(tcar_clip_adam_rest_keep_o(c->E, g.ek, c->big, c->Mi, c->Vi, g.N, g.ldh, c->slot_item, c->sqn_dense, pieces, c->use_dense,
+                                 c->clip, lr, c->b1, c->b2, c->eps, c->scoring ? c->e16h : nullptr, c->scoring ? c->e16l : nullptr,
+                                 g.ek, c->adam_bitmap, (void*)s2, tcar_fixed::rest_grid));
+  RET(between());
+  RET(record(s2, ev));
+  // the marks are cleared BEHIND the event the waiter waits for (the clear is a launch of its own)
+  // (the map is allocated in whole 64-byte units, tcar_hip.h: ONE fill kernel — a size that is no multiple of 16 bytes costs a second one)
+  if (hipMemsetAsync(c->adam_bitmap, 0, (size_t)(((g.N + 31) / 32 + 15) & ~15) * sizeof(uint32_t), s2) != hipSuccess) return TCAR_E_LAUNCH;
+  return TCAR_OK;
+}
+
 // zero the gradient arena and the norm slots, and the forward part of the sampled negative term (it needs only attout and E):
 // on the aux stream `sz`, ordered behind everything already on the main stream (the previous update read Gx)
 // (Round 3 A/B: saving this fork's event — arena zeroed on the already-ordered aux stream, the negative term's forward behind the
@@ -511,7 +528,7 @@ int backward_prologue(const tcar_ctx_t* c, const tcar_batch_t* bt, hipStream_t s
     if (f->sig.epoch != fork_host(c)->epoch) fork_disarm(c, FK_LOGITS);
   if (sz != st) RET(fork_go(c, FK_LOGITS, st, sz, c->ev[0], tcar_fixed::fork_delay));
   RET(zero_arena(c, sz));
-  if (bt->K > 0 && bt->neg && c->neg_coef && c->negpart) {
+  if (has_negatives(c, bt)) {
     TcarOpt on = opt_of(c);
     RET(tcar_neg_fwd_o(&c->d, bt->B, bt->K, c->E, bt->neg, c->attout, c->neg_weight, c->neg_fb, c->neg_coef, c->negpart, (void*)sz, &on));
   }
@@ -544,22 +561,9 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
   // anchor — of a pending split update they join the early part, so that the rest pass (aux stream, beside the forward) never
   // writes a row this step's forward reads: no race, the same bits in every run
   const bool anchored = oh_bwd && ce_anchored(c, bt);
-  // REST pass of a pending split update, on the aux stream (behind whatever the main stream has enqueued so far when it is
-  // forked late); ev[1] = "aux stream ready for the logits GEMM"
-  auto launch_rest = [&]() -> int {
-    const float* pieces = c->Gx + c->arena_n;
-    RET(tcar_clip_adam_rest_keep_o(c->E, g.ek, c->big, c->Mi, c->Vi, g.N, g.ldh, c->slot_item, c->sqn_dense, pieces, c->use_dense,
-                                   c->clip, rest_lr, c->b1, c->b2, c->eps, c->scoring ? c->e16h : nullptr,
-                                   c->scoring ? c->e16l : nullptr, g.ek, c->adam_bitmap, (void*)s2, tcar_fixed::rest_grid));
-    if (hipEventRecord((hipEvent_t)c->ev[1], s2) != hipSuccess) return TCAR_E_LAUNCH;
-    // the marks are cleared BEHIND the event the logits GEMM waits for (the clear is a launch of its own)
-    // (the map is allocated in whole 64-byte units, tcar_hip.h: ONE fill kernel — a size that is no multiple of 16 bytes costs a second one)
-    if (hipMemsetAsync(c->adam_bitmap, 0, (size_t)(((g.N + 31) / 32 + 15) & ~15) * sizeof(uint32_t), s2) != hipSuccess) return TCAR_E_LAUNCH;
-    return TCAR_OK;
-  };
   if (refresh_time) {
     const float* tt[5];
-    for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+    time_tables(c, tt);
     if (s2 && rest_lr >= 0.f) {
       // The pending split update (tcar_train_step_deferred): EARLY pass on the main stream (arena + the item rows this batch
       // gathers), then — on the aux stream, beside the session forward — the time refresh and the REST pass over every other
@@ -573,8 +577,7 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
                                  anchored ? bt->label : nullptr, anchored ? (int64_t)B : 0, c->adam_bitmap, stream));
       // (one-hot form: nothing is launched on the aux stream here — the rest pass is forked behind the projection launch, which is
       //  behind the early pass on this stream: no event on the main chain at the top of the step)
-      if (!oh_bwd && (hipEventRecord((hipEvent_t)c->ev[0], s1) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-        return TCAR_E_LAUNCH;
+      if (!oh_bwd) RET(order(s1, s2, c->ev[0]));
       if (!oh_bwd)
         RET(tcar_cand_time_fwd_bf16(&c->d, tt, c->mwdhm, c->scoring ? nullptr : c->E, c->scoring ? c->e16h : nullptr, c->scoring ? c->e16l : nullptr, (void*)s2));
       // the rest pass is forked BEHIND the projection launch: gather and projections run without the 376-MB stream beside
@@ -585,13 +588,12 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
       // (Round 4 re-measured the placement on the shorter head — behind the gather through a second poll of its flag: +11 us; at once
       //  behind an event: equal — and round 5 removed those two forms: profiles/r04_ab_experiments.txt.)
     } else {
-      if (s2 && (hipEventRecord((hipEvent_t)c->ev[0], s1) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-        return TCAR_E_LAUNCH;
+      if (s2) RET(order(s1, s2, c->ev[0]));
       if (!oh_bwd)
         RET(tcar_cand_time_fwd_bf16(&c->d, tt, c->mwdhm, c->scoring ? nullptr : c->E, c->scoring ? c->e16h : nullptr, c->scoring ? c->e16l : nullptr,
                                     s2 ? (void*)s2 : stream));
       if (s2) {
-        if (hipEventRecord((hipEvent_t)c->ev[1], s2) != hipSuccess) return TCAR_E_LAUNCH;
+        RET(record(s2, c->ev[1]));
         joined = false;
       }
     }
@@ -613,15 +615,14 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
     // late fork: the HBM-bound rest pass starts only now, so the launches before this point ran without it
     (void)fork_commit(c, FK_PROJ, *o);
     RET(fork_go(c, FK_PROJ, s1, s2, c->ev[0]));      // (the rest pass reads nothing the projections write: timing only)
-    return launch_rest();
+    // on the aux stream, behind whatever the main stream has enqueued so far; ev[1] = "aux stream ready for the logits GEMM"
+    return rest_pass(c, g, rest_lr, s2, c->ev[1], [] { return (int)TCAR_OK; });
   }, onehot ? &so : nullptr));
   // sort index of the item rows (feed only): on the aux stream BEHIND the rest pass — the logits GEMM does not wait for it (ev[1]
   // was recorded in front of it), the backward does
   if (train_index && sorted_rows(c, bt)) {
     // (with a time refresh the aux stream was already forked from this step's main stream: it is behind the previous backward)
-    if (!refresh_time &&
-        (hipEventRecord((hipEvent_t)c->ev[0], s1) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-      return TCAR_E_LAUNCH;
+    if (!refresh_time) RET(order(s1, s2, c->ev[0]));
     RET(tcar_segsum_index(&c->d, bt, c->segsum_ws, c->segsum_bytes, (void*)s2));
   }
   // candidate-side time scores through the one-hot contraction (embed.hip: tcar_time_scores / tcar_time_onehot): the logits
@@ -630,10 +631,10 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
   // AHEAD of the join with the aux stream.
   if (onehot && !so.done) {
     const float* tt[5];
-    for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+    time_tables(c, tt);
     RET(tcar_time_scores_clip(&c->d, tt, B, c->attout, g.ek, c->p16h, c->p16l, 160, oh_bwd ? c->tclip : nullptr, stream));
   }
-  if (!joined && hipStreamWaitEvent(s1, (hipEvent_t)c->ev[1], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  if (!joined) RET(wait_for(s1, c->ev[1]));
   h.ei = ei; h.ce_epi = ce_epi; h.onehot = onehot; h.anchored = anchored; h.anchor_done = so.anchor_done; h.w = w; h.s2 = s2;
   return TCAR_OK;
 }
@@ -757,9 +758,99 @@ int det_colsums(const tcar_ctx_t* c, const Geo& g, int B, void* stream) {
   det_colsum_list(c, g, B, cs);
   return tcar_colsum_det(6, cs, stream);
 }
-int finish_dense_side(const tcar_ctx_t* c, const Geo& g, void* stream);
-int item_norm(const tcar_ctx_t* c, const Geo& g, void* stream);
-int cand_time_backward(const tcar_ctx_t* c, const Geo& g, void* stream);
+// clip norm of the dense item block (`rows` rows of c->big -> the item slot of `dst`) BEFORE the sparse rows are scattered in
+// (DESIGN.md S5), then the candidate-side time backward (static inverted index)
+int item_norm(const tcar_ctx_t* c, const Geo& g, int64_t rows, float* dst, void* stream) {
+  tcar_segments_t one = {};
+  one.nseg = 1; one.off[0] = 0; one.len[0] = rows * g.ldh; one.slot[0] = c->slot_item;
+  return tcar_sqnorm(c->big, &one, dst, stream);
+}
+int cand_time_backward(const tcar_ctx_t* c, const Geo& g, void* stream) {
+  tcar_grads_t gr;
+  grads_of(c, gr);
+  const float* tt[5];
+  time_tables(c, tt);
+  return tcar_cand_time_bwd_indexed(&c->d, tt, c->inv_n, c->inv_off, c->big + (size_t)g.N * g.ldh,
+                                    (c->scoring && c->et_perm) ? 1 : 0, c->ct_ws, &gr, stream);
+}
+int finish_dense_side(const tcar_ctx_t* c, const Geo& g, void* stream) {
+  RET(item_norm(c, g, g.N, c->sqn_dense, stream));
+  return cand_time_backward(c, g, stream);
+}
+
+// Session-side backward behind dattout, shared by the fused step (backward_impl) and the catalog-sharded one
+// (tcar_step_session_backward): dpooled -> pool backward -> dq1 + the projections' input gradients, all on `stream`.
+//   hi_only:    the small GEMMs on plain bf16 operands (diagnostic builds under the hi-only backward precision)
+//   arm_ingrad: the input-gradient launch carries FK_INGRAD — a side stream of the caller is forked behind it
+struct SessionBwd { bool hi_only; bool arm_ingrad; };
+int session_backward(const tcar_ctx_t* c, const Geo& g, int B, int T, void* stream, const SessionBwd& sb) {
+  const int BT = B * T;
+  const bool fusedq = c->scoring != 0;
+  const bool detc = fusedq && c->gw_rows != nullptr;       // order-fixed bias / residual-weight gradients (as the callers decide it)
+  // dpooled = dattout W_o^T (both output transforms).  Split form (slab workspace + order-fixed pool backward): every 128-deep K
+  // chunk is its own set of workgroups writing its own slab, the pool backward folds them in slab order while it loads dpooled
+  // (round 5: 376 workgroups and one global round trip instead of 104 walking 8 / 5 serial stages — 30 -> 19 us on this chain)
+  const int nd_ic = units(g.ic), nd_pt = units(g.pt);
+  const int64_t dstride = (int64_t)B * g.ek;
+  const bool dsplit = detc && c->proj_slabs && c->proj_slab_floats >= (nd_ic > nd_pt ? nd_ic : nd_pt) * dstride;
+  {
+    tcar_gemm_desc_t p[2];
+    float* dp = dsplit ? c->proj_slabs : c->dpooled;
+    p[0] = prob1(B, g.ic, c->dattout, g.ek, W(c, TCAR_V_O_W), g.ic, g.ic, dp, g.ek, nullptr, 0, 0, dsplit ? nd_ic : 1);
+    p[1] = prob1(B, g.pt, c->dattout + g.ic, g.ek, W(c, TCAR_V_OT_W), g.pt, g.pt, dp + g.ic, g.ek, nullptr, 0, 0, dsplit ? nd_pt : 1);
+    TcarOpt odp = opt_of(c);
+    odp.hi_only = sb.hi_only;
+    RET(small_gemm(c, 1, 2, p, stream, &odp));
+  }
+  // query MLP backward (modules.py:138-139).  Split-bf16 modes: tanh' + bias gradient of query_trans2 ride in the pool
+  // backward, relu' + bias gradient of query_trans1 in the epilogue of the GEMM that produces dq1, and that GEMM shares ONE
+  // launch with the three input-gradient GEMMs of the projections (all four need only the pool backward's outputs); the
+  // click-query input gradient (needs dq1) follows (click_input_grad).  fp32 mode: the op-level sequence.
+  // (The whole click-query MLP backward, dq -> dq1 -> dclick, as ONE launch on the third stream behind the pool backward's flag —
+  //  tcar_query_mlp_bwd with both layers — measured slower in rounds 4 and 5; the drivers run only its layer-1 half.)
+  // (Weight gradients in two launches — eight of the nine problems behind the pool backward's flag — were measured twice, 5 us and
+  //  15 us SLOWER per step: the early launch runs beside the main chain's input-gradient GEMM.  Removed in round 5.)
+  if (detc)
+    RET(tcar_attn_pool_bwd_slabs_o(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES),
+                                   c->alpha, dsplit ? c->proj_slabs : c->dpooled, dsplit ? nd_ic : 1, dsplit ? nd_pt : 1, dstride,
+                                   c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2, c->gw_rows, stream, nullptr));
+  else
+    RET(tcar_attn_pool_bwd_q(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES),
+                             W(c, TCAR_V_S_WRES), c->alpha, c->dpooled, c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2,
+                             G(c, TCAR_V_M_WRES), G(c, TCAR_V_S_WRES), fusedq ? G(c, TCAR_V_Q2_B) : nullptr, stream));
+  if (!fusedq) {       // (fp32 scoring: the fused step only; its input gradients go with dclick, further down in backward_impl)
+    fork_disarm(c, FK_INGRAD);
+    RET(tcar_dact_colsum(B, g.ic, g.ic, c->q, c->dq, G(c, TCAR_V_Q2_B), 2, stream));
+    tcar_gemm_desc_t p = prob1(B, g.ldh, c->dq, g.ic, W(c, TCAR_V_Q2_W), g.ic, g.ic, c->dq1, g.ldh);
+    RET(small_gemm(c, 1, 1, &p, stream));
+    return tcar_dact_colsum(B, g.ldh, g.ldh, c->q1, c->dq1, G(c, TCAR_V_Q1_B), 1, stream);
+  }
+  tcar_gemm_desc_t p[4];
+  p[0] = prob1(B, g.ldh, c->dq, g.ic, W(c, TCAR_V_Q2_W), g.ic, g.ic, c->dq1, g.ldh);
+  p[0].dact = 1; p[0].dact_y = c->q1; p[0].ld_dact_y = g.ldh; p[0].colsum = detc ? nullptr : G(c, TCAR_V_Q1_B);
+  // input gradients (only the ITEM half of dX_ic: content is frozen)
+  p[1] = prob1(BT, g.ldh, c->dpre1, g.ldh, W(c, TCAR_V_M_WIN), g.ldh, g.ldh, c->dx_icp, g.ic, nullptr, 0, 1);
+  p[2] = prob1(BT, g.ldt, c->dpre1, g.ldh, W(c, TCAR_V_M_WINT), g.ldh, g.ldh, c->dx_act, g.ldt);
+  p[3] = prob1(BT, g.pt, c->dpre2, g.ldh, W(c, TCAR_V_S_WIN), g.ldh, g.ldh, c->dx_pt, g.pt, nullptr, 0, 1);
+  TcarOpt oi = opt_of(c);
+  oi.hi_only = sb.hi_only;
+  if (sb.arm_ingrad) oi.sig = fork_arm(c, FK_INGRAD);      // (flagged small-GEMM launches store write-through)
+  else fork_disarm(c, FK_INGRAD);
+  RET(small_gemm(c, 1, 4, p, stream, &oi));
+  (void)fork_commit(c, FK_INGRAD, oi);
+  return TCAR_OK;
+}
+
+// the click-query input gradient dclick = dq1 Wq1^T (it needs dq1 of session_backward; only the small tables consume it).
+// `o`: launch options of the small-GEMM form, the one that can carry a flag — a caller that passes them gets that form at every
+// geometry; without them ldh = 256, ldt = 64 take ONE fp32 launch of whole-row dots (query.hip: the layer-1 half of the click-query
+// backward): 7 us where the 16-workgroup small GEMM walks four serial 64-deep stages (16-20 us)
+int click_input_grad(const tcar_ctx_t* c, const Geo& g, int B, void* stream, TcarOpt* o = nullptr) {
+  if (!o && g.ldh == 256 && g.ldt == 64)
+    return tcar_query_mlp_bwd_o(&c->d, B, nullptr, nullptr, W(c, TCAR_V_Q1_W), nullptr, c->dq1, c->dclick, stream, nullptr);
+  tcar_gemm_desc_t p = prob1(B, g.ct, c->dq1, g.ldh, W(c, TCAR_V_Q1_W), g.ldh, g.ldh, c->dclick, g.ct);
+  return small_gemm(c, 1, 1, &p, stream, o);
+}
 
 // Backward pass.  Three chains follow the softmax gradient (fused single-rank step; `main` is the caller's stream, which the
 // engine makes a high-priority one so that its workgroups are dispatched first):
@@ -782,7 +873,7 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
   // it runs FIRST on the main stream, so that dE is complete early and its all-reduce overlaps chain A (dp.py)
   void* sB = (s2 && fuse_finish) ? (void*)s2 : stream;
   void* sW = s2 ? (void*)s2 : stream;          // the weight-gradient GEMM (third stream below, when there is one)
-  const bool has_neg = K > 0 && bt->neg && c->neg_coef && c->negpart;
+  const bool has_neg = has_negatives(c, bt);
   // zero the gradient arena and the norm slots; with an aux stream this happens beside the softmax, not before it
   // (the aux stream is first ordered behind everything already on the main stream: the previous update read Gx)
   hipStream_t sz = s2 ? s2 : st;
@@ -795,7 +886,7 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
   // ev[1] = "aux prologue done" (arena zeroed, negative term's forward): in the one-hot schedule its only reader on the main chain is
   // the slab reduce (negpart).  Everything else that needs the zeroed arena sits behind dE on its own stream (stream order / ev[4]).
   // (The slab reduce can also wait for the negative term's flag in-kernel — tcar_reduce_dact_onehot_o's wait —: measured no faster.)
-  if (s2 && hipEventRecord((hipEvent_t)c->ev[1], s2) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2) RET(record(s2, c->ev[1]));
   float* Gi = c->big;
   float* d_et = c->big + (size_t)g.N * g.ldh;
   const int S = tcar_gemm_splitk_effective(g.Npad, c->splitk);
@@ -824,11 +915,9 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
   // profiles/r05_main_stream_gaps.txt), no write-through plane (the round-3/4 form that lost: slot 12).  Else: an event.
   TcarSignal dx_start{};
   if (ohb && s2 && sB != stream) dx_start = fork_arm(c, FK_DXSTART);
-  if (!dx_start.flag && s2 &&
-      (hipEventRecord((hipEvent_t)c->ev[2], st) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[2], 0) != hipSuccess))
-    return TCAR_E_LAUNCH;
+  if (!dx_start.flag && s2) RET(order(st, s2, c->ev[2]));
   // ---- chain B  (when it runs on the main stream it is the first user of the aux stream's prologue there)
-  if (s2 && sB == stream && hipStreamWaitEvent(st, (hipEvent_t)c->ev[1], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2 && sB == stream) RET(wait_for(st, c->ev[1]));
   // optional HIP events around exactly the dE and dX launches (slot chosen by the forward pass; kind 1 = dX, 2 = dE)
   const int ei = (c->ev_n > 0 && c->ev_start && c->ev_stop && c->ev_cursor) ? c->ev_cursor[1] : -1;
   auto tick = [&](int kind, bool stop, void* s) {
@@ -858,14 +947,14 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     // Fused single-rank step: the aux stream goes straight on to the candidate-side time backward (it needs only d_et),
     // while the negative rows and the dense item norm (they need Gi) are appended to the MAIN chain, which has slack
     // once dX has been given priority.  Rank-local backward: negative rows here, the rest in tcar_step_finish.
-    if (split_finish && hipEventRecord((hipEvent_t)c->ev[4], s2) != hipSuccess) return TCAR_E_LAUNCH;         // dE done
+    if (split_finish) RET(record(s2, c->ev[4]));         // dE done
     if (has_neg && !split_finish)
       RET(tcar_neg_scatter(&c->d, B, K, bt->neg, c->attout, c->neg_coef, Gi, c->neg_fb, c->ce, c->neg_weight, c->loss, sB));
     // (one-hot form: the candidate-side table gradients need dP of the dX chain too — they follow on this stream further down)
     if (fuse_finish && !ohb) RET(split_finish ? cand_time_backward(c, g, sB) : finish_dense_side(c, g, sB));
     // chain B done (read only where the main stream waits for the whole chain: not in the fused step's split finish — every
     // event record between two kernels costs its stream ~7 us)
-    if (s2 && !split_finish && hipEventRecord((hipEvent_t)c->ev[3], (hipStream_t)sB) != hipSuccess) return TCAR_E_LAUNCH;
+    if (s2 && !split_finish) RET(record((hipStream_t)sB, c->ev[3]));
     return TCAR_OK;
   };
   auto chain_a_dx = [&]() -> int {
@@ -889,9 +978,7 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
   if (dx_start.flag) {
     // dX first (it carries the start flag), then the aux stream's poll in front of dE
     RET(chain_a_dx());
-    TCAR_LAUNCH(poll_flag_kernel, dim3(1), dim3(64), 0, s2, (const unsigned*)dx_start.flag, dx_start.epoch, c->sig_dev + TCAR_SIG_ERR,
-                c->sig_err_host, POLL_TICKS, (const unsigned*)nullptr, 0u, 0);
-    TCAR_CHECK_LAUNCH();
+    RET(poll(c, s2, dx_start));
   }
   RET(chain_b());
   // negative rows of the item gradient (sorted sum) + the loss: they need dE's item block and nothing of the main chain — on
@@ -899,15 +986,15 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
   const bool neg_s3 = split_finish && has_neg && sorted && c->stream3 && c->ev3;
   if (neg_s3) {
     hipStream_t s3n = (hipStream_t)c->stream3;
-    if (hipStreamWaitEvent(s3n, (hipEvent_t)c->ev[4], 0) != hipSuccess) return TCAR_E_LAUNCH;
+    RET(wait_for(s3n, c->ev[4]));
     RET(tcar_segsum_apply(&c->d, bt, c->segsum_ws, c->segsum_bytes, 1, nullptr, c->neg_coef, c->attout, g.ek, Gi, nullptr, nullptr,
                           c->ce, c->neg_fb, c->neg_weight, c->loss, (void*)s3n));
-    if (hipEventRecord((hipEvent_t)c->ev[3], s3n) != hipSuccess) return TCAR_E_LAUNCH;
+    RET(record(s3n, c->ev[3]));
   }
   // ---- chain A
   if (!dx_start.flag) RET(chain_a_dx());
   // first use of the zeroed arena and of the negative term's forward outputs on the main stream
-  if (s2 && hipStreamWaitEvent(st, (hipEvent_t)c->ev[1], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2) RET(wait_for(st, c->ev[1]));
   // (Round 3 A/B: letting the chain of small kernels behind dX wait until dE has finished — every one of them runs ~2x slower
   // beside dE's 106-MB write stream — loses more in idle time than the faster kernels give back: 0.647 vs 0.620 ms per step.)
   // dattout = slabs summed + the negative term's part, through tanh' of both output transforms, + their bias gradients
@@ -936,67 +1023,14 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     RET(tcar_splitk_reduce_dact(c->slabs, S, B, g.ek, g.ek, has_neg ? c->negpart : nullptr, g.ic, g.ic, c->attout, g.ek, 2,
                                 c->dattout, detc ? nullptr : G(c, TCAR_V_O_B), g.ic, detc ? nullptr : G(c, TCAR_V_OT_B), stream));
   if (!has_neg && hipMemsetAsync(c->neg_fb, 0, (size_t)B * sizeof(float), st) != hipSuccess) return TCAR_E_LAUNCH;
-  // dpooled = dattout W_o^T (both output transforms).  Split form (slab workspace + order-fixed pool backward): every 128-deep K
-  // chunk is its own set of workgroups writing its own slab, the pool backward folds them while it loads dpooled
-  const int nd_ic = units(g.ic), nd_pt = units(g.pt);
-  const int64_t dstride = (int64_t)B * g.ek;
   // (diagnostic builds: the session-side backward GEMMs on plain bf16 operands under the hi-only backward precision)
   const bool bwd_hi = tcar_fixed::bwd_small_hi != 0 && c->scoring_bwd == 1 && fuse_finish;
-  const bool dsplit = detc && c->proj_slabs && c->proj_slab_floats >= (nd_ic > nd_pt ? nd_ic : nd_pt) * dstride;
-  {
-    tcar_gemm_desc_t p[2];
-    float* dp = dsplit ? c->proj_slabs : c->dpooled;
-    p[0] = prob1(B, g.ic, c->dattout, g.ek, W(c, TCAR_V_O_W), g.ic, g.ic, dp, g.ek, nullptr, 0, 0, dsplit ? nd_ic : 1);
-    p[1] = prob1(B, g.pt, c->dattout + g.ic, g.ek, W(c, TCAR_V_OT_W), g.pt, g.pt, dp + g.ic, g.ek, nullptr, 0, 0, dsplit ? nd_pt : 1);
-    TcarOpt odp = opt_of(c);
-    odp.hi_only = bwd_hi;
-    RET(small_gemm(c, 1, 2, p, stream, &odp));
-  }
-  // query MLP backward (modules.py:138-139).  Split-bf16 modes: tanh' + bias gradient of query_trans2 ride in the pool
-  // backward, relu' + bias gradient of query_trans1 in the epilogue of the GEMM that produces dq1, and that GEMM shares ONE
-  // launch with the three input-gradient GEMMs of the projections (all four need only the pool backward's outputs); the
-  // click-query input gradient (needs dq1) follows.  fp32 mode: the op-level sequence.
-  // (The whole click-query MLP backward, dq -> dq1 -> dclick, as ONE launch on the third stream behind the pool backward's flag —
-  //  tcar_query_mlp_bwd with both layers — measured slower in rounds 4 and 5; the driver runs only its layer-1 half, further down.)
-  // (Weight gradients in two launches — eight of the nine problems behind the pool backward's flag — were measured twice, 5 us and
-  //  15 us SLOWER per step: the early launch runs beside the main chain's input-gradient GEMM.  Removed in round 5.)
-  if (detc) {
-    TcarOpt opb = opt_of(c);
-    RET(tcar_attn_pool_bwd_slabs_o(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES),
-                                   c->alpha, dsplit ? c->proj_slabs : c->dpooled, dsplit ? nd_ic : 1, dsplit ? nd_pt : 1, dstride,
-                                   c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2, c->gw_rows, stream, &opb));
-  }
-  else
-    RET(tcar_attn_pool_bwd_q(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES),
-                             W(c, TCAR_V_S_WRES), c->alpha, c->dpooled, c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2,
-                             G(c, TCAR_V_M_WRES), G(c, TCAR_V_S_WRES), fusedq ? G(c, TCAR_V_Q2_B) : nullptr, stream));
-  if (fusedq) {
-    tcar_gemm_desc_t p[4];
-    p[0] = prob1(B, g.ldh, c->dq, g.ic, W(c, TCAR_V_Q2_W), g.ic, g.ic, c->dq1, g.ldh);
-    p[0].dact = 1; p[0].dact_y = c->q1; p[0].ld_dact_y = g.ldh; p[0].colsum = detc ? nullptr : G(c, TCAR_V_Q1_B);
-    // input gradients (only the ITEM half of dX_ic: content is frozen)
-    p[1] = prob1(BT, g.ldh, c->dpre1, g.ldh, W(c, TCAR_V_M_WIN), g.ldh, g.ldh, c->dx_icp, g.ic, nullptr, 0, 1);
-    p[2] = prob1(BT, g.ldt, c->dpre1, g.ldh, W(c, TCAR_V_M_WINT), g.ldh, g.ldh, c->dx_act, g.ldt);
-    p[3] = prob1(BT, g.pt, c->dpre2, g.ldh, W(c, TCAR_V_S_WIN), g.ldh, g.ldh, c->dx_pt, g.pt, nullptr, 0, 1);
-    TcarOpt oi = opt_of(c);
-    oi.hi_only = bwd_hi;
-    if (s2 && fuse_finish && c->stream3 && c->ev3) oi.sig = fork_arm(c, FK_INGRAD);     // the third stream's fork below
-    else fork_disarm(c, FK_INGRAD);
-    RET(small_gemm(c, 1, 4, p, stream, &oi));
-    (void)fork_commit(c, FK_INGRAD, oi);
-  } else {
-    fork_disarm(c, FK_INGRAD);
-    RET(tcar_dact_colsum(B, g.ic, g.ic, c->q, c->dq, G(c, TCAR_V_Q2_B), 2, stream));
-    {
-      tcar_gemm_desc_t p = prob1(B, g.ldh, c->dq, g.ic, W(c, TCAR_V_Q2_W), g.ic, g.ic, c->dq1, g.ldh);
-      RET(small_gemm(c, 1, 1, &p, stream));
-    }
-    RET(tcar_dact_colsum(B, g.ldh, g.ldh, c->q1, c->dq1, G(c, TCAR_V_Q1_B), 1, stream));
-  }
+  // the third stream, when the context has one: the input-gradient launch of the session backward carries the flag of its fork below
+  hipStream_t s3 = (s2 && fuse_finish && c->stream3 && c->ev3) ? (hipStream_t)c->stream3 : nullptr;
+  RET(session_backward(c, g, B, T, stream, SessionBwd{bwd_hi, s3 != nullptr}));
   // Everything the weight gradients need exists now; they run beside the main stream's input gradients and row scatter:
   // on the third stream when the context has one (fused step: the aux stream is still busy with the candidate-time
   // backward, which only became ready when dE finished), else on the aux stream behind chain B.
-  hipStream_t s3 = (s2 && fuse_finish && c->stream3 && c->ev3) ? (hipStream_t)c->stream3 : nullptr;
   TcarOpt ow = opt_of(c);
   ow.hi_only = bwd_hi;
   if (s3) {
@@ -1004,9 +1038,9 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     RET(fork_go(c, FK_INGRAD, st, s3, c->ev[0]));        // (flagged small-GEMM launches store write-through)
     // (with the negative rows on this stream it already waited for dE — ev[4], recorded on the aux stream BEHIND the arena zero —
     // and a wait for a completed event still costs the stream a ~6-us barrier packet)
-    if (!neg_s3 && hipStreamWaitEvent(s3, (hipEvent_t)c->ev[1], 0) != hipSuccess) return TCAR_E_LAUNCH;
-  } else if (s2 && (hipEventRecord((hipEvent_t)c->ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-    return TCAR_E_LAUNCH;
+    if (!neg_s3) RET(wait_for(s3, c->ev[1]));
+  } else if (s2)
+    RET(order(st, s2, c->ev[0]));
   // Order-fixed small tables (sorted mode, which implies an aux stream): they — and the click-query input gradient, which only
   // they consume — run on the aux stream behind the candidate-time backward, beside the rest of the main chain
   const bool det_small = sorted && tn(c).det_small != 0;
@@ -1044,17 +1078,16 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     if (!fused_done) RET(tcar_sqnorm_o(c->Gx, &c->segs_dense, c->sqn_dense, sW, &o3));
     if (tail_flags) tail3 = fork_commit(c, FK_TAIL3, o3);
   }
-  if (s3 && hipEventRecord((hipEvent_t)c->ev3, s3) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s3) RET(record(s3, c->ev3));
   // (with the order-fixed small tables the aux stream's "done" event is recorded behind them, below)
-  if (s2 && !det_small && hipEventRecord((hipEvent_t)c->ev[2], s2) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2 && !det_small) RET(record(s2, c->ev[2]));
   if (dclick_aux) {
     // (launched on the aux stream below, in front of the small tables)
-  } else if (fusedq) {   // the click-query input gradient (the projections' input gradients went with dq1)
-    tcar_gemm_desc_t p = prob1(B, g.ct, c->dq1, g.ldh, W(c, TCAR_V_Q1_W), g.ldh, g.ldh, c->dclick, g.ct);
+  } else if (fusedq) {   // the click-query input gradient (the projections' input gradients went with dq1): the small-GEMM form
     TcarOpt od = opt_of(c);
     if (det_small) od.sig = fork_arm(c, FK_DCLICK);
     else fork_disarm(c, FK_DCLICK);
-    RET(small_gemm(c, 1, 1, &p, stream, &od));
+    RET(click_input_grad(c, g, B, stream, &od));
     (void)fork_commit(c, FK_DCLICK, od);
   } else {  // input gradients (only the ITEM half of dX_ic: content is frozen)
     fork_disarm(c, FK_DCLICK);
@@ -1077,14 +1110,7 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     // gradients, the column sums and the dense norms); the final join below waits for ev[2], re-recorded here
     if (dclick_aux) {
       RET(fork_go(c, FK_INGRAD, st, s2, c->ev[5]));       // (the same flag the third stream polled: dq1, dx_* of that launch)
-      if (g.ldh == 256 && g.ldt == 64) {
-        // dclick = dq1 Wq1^T as ONE fp32 launch of whole-row dots (query.hip: the layer-1 half of the click-query backward): 7 us
-        // where the 16-workgroup small GEMM walks four serial 64-deep stages (20 us), on the chain that ends the step
-        RET(tcar_query_mlp_bwd_o(&c->d, B, nullptr, nullptr, W(c, TCAR_V_Q1_W), nullptr, c->dq1, c->dclick, (void*)s2, nullptr));
-      } else {
-        tcar_gemm_desc_t p = prob1(B, g.ct, c->dq1, g.ldh, W(c, TCAR_V_Q1_W), g.ldh, g.ldh, c->dclick, g.ct);
-        RET(small_gemm(c, 1, 1, &p, (void*)s2));
-      }
+      RET(click_input_grad(c, g, B, (void*)s2));          // (whole-row form where the geometry has it: on the chain that ends the step)
     } else {
       RET(fork_go(c, FK_DCLICK, st, s2, c->ev[5]));
     }
@@ -1093,10 +1119,10 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     RET(tcar_small_tables_bwd_det_o(&c->d, &tab, bt, c->dx_icp, c->dx_pt, c->dx_act, c->dclick, &gr, rowq, (void*)s2, &o2,
                                     ohb ? tcar_cand_pieces(&c->d, c->ct_ws) : nullptr, rowq_floats));
     if (tail3) tail2 = fork_commit(c, FK_TAIL2, o2);
-    if (hipEventRecord((hipEvent_t)c->ev[2], s2) != hipSuccess) return TCAR_E_LAUNCH;
+    RET(record(s2, c->ev[2]));
   }
   if (split_finish) {   // Gi is complete once dE has landed: negative rows (+ loss), then its norm BEFORE any row scatter (S5)
-    if (hipStreamWaitEvent(st, (hipEvent_t)(neg_s3 ? c->ev[3] : c->ev[4]), 0) != hipSuccess) return TCAR_E_LAUNCH;
+    RET(wait_for(st, neg_s3 ? c->ev[3] : c->ev[4]));
     if (neg_s3) {
       // (done on the third stream)
     } else if (has_neg && sorted) {
@@ -1107,11 +1133,11 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     }
     // sorted: the block partials of ||Gi||^2 (S5: BEFORE any session row lands) ride in the launch of the item-row gradients
     // below (tcar_gather_clip_bwd_sqnorm); the session-list pass folds them
-    if (!sorted) RET(item_norm(c, g, stream));
+    if (!sorted) RET(item_norm(c, g, g.N, c->sqn_dense, stream));
   }
   // The row scatter needs the item norm (same stream) but NOT the candidate-time backward: both only add (atomically) into
   // the time-table gradients, and the final join below covers the whole aux stream.  Without the split, wait for chain B.
-  if (s2 && !split_finish && hipStreamWaitEvent(st, (hipEvent_t)c->ev[3], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2 && !split_finish) RET(wait_for(st, c->ev[3]));
   if (fuse_finish) {
     // sparse rows and per-row norm pieces (after the dense item norm of chain B), then the dense-weight norms
     tcar_tables_t tab;
@@ -1136,46 +1162,18 @@ int backward_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream, boo
     }
   }
   if (tail2 && tail3) {
-    const ForkSlot& f2 = fork_host(c)->slot[FK_TAIL2];
-    const ForkSlot& f3 = fork_host(c)->slot[FK_TAIL3];
     // light poll (no L2 write-back): the flagged launches publish their OWN results with atomics (norm slots; the small tables'
     // rows) or write-through stores (colsum_sqnorm_kernel: the six bias / residual-weight gradients), and everything else the
     // update reads was written by EARLIER launches of those streams, released when they ended
-    TCAR_LAUNCH(poll_flag_kernel, dim3(1), dim3(64), 0, st, (const unsigned*)f2.sig.flag, f2.sig.epoch, c->sig_dev + TCAR_SIG_ERR,
-                c->sig_err_host, POLL_TICKS, (const unsigned*)f3.sig.flag, f3.sig.epoch, 0);
-    TCAR_CHECK_LAUNCH();
+    RET(poll(c, st, fork_host(c)->slot[FK_TAIL2].sig, fork_host(c)->slot[FK_TAIL3].sig));
   } else {
-    if (s2 && hipStreamWaitEvent(st, (hipEvent_t)c->ev[2], 0) != hipSuccess) return TCAR_E_LAUNCH;    // the aux stream is done
-    if (s3 && hipStreamWaitEvent(st, (hipEvent_t)c->ev3, 0) != hipSuccess) return TCAR_E_LAUNCH;       // weight gradients are in
+    if (s2) RET(wait_for(st, c->ev[2]));    // the aux stream is done
+    if (s3) RET(wait_for(st, c->ev3));      // weight gradients are in
   }
   if (fuse_finish && !s2) RET(tcar_sqnorm(c->Gx, &c->segs_dense, c->sqn_dense, stream));
   return TCAR_OK;
 }
 
-// clip norm of the dense item block BEFORE the sparse rows are scattered in, then the candidate-side
-// time backward (static inverted index)
-int item_norm(const tcar_ctx_t* c, const Geo& g, void* stream) {
-  tcar_segments_t one = {};
-  one.nseg = 1; one.off[0] = 0; one.len[0] = (int64_t)g.N * g.ldh; one.slot[0] = c->slot_item;
-  return tcar_sqnorm(c->big, &one, c->sqn_dense, stream);
-}
-int cand_time_backward(const tcar_ctx_t* c, const Geo& g, void* stream) {
-  tcar_grads_t gr;
-  grads_of(c, gr);
-  const float* tt[5];
-  for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
-  return tcar_cand_time_bwd_indexed(&c->d, tt, c->inv_n, c->inv_off, c->big + (size_t)g.N * g.ldh,
-                                    (c->scoring && c->et_perm) ? 1 : 0, c->ct_ws, &gr, stream);
-}
-int finish_dense_side(const tcar_ctx_t* c, const Geo& g, void* stream) {
-  RET(item_norm(c, g, stream));
-  tcar_grads_t gr;
-  grads_of(c, gr);
-  const float* tt[5];
-  for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
-  return tcar_cand_time_bwd_indexed(&c->d, tt, c->inv_n, c->inv_off, c->big + (size_t)g.N * g.ldh,
-                                    (c->scoring && c->et_perm) ? 1 : 0, c->ct_ws, &gr, stream);
-}
 }  // namespace
 
 extern "C" int tcar_step_backward_local(const tcar_ctx_t* c, const tcar_batch_t* bt, void* stream) {
@@ -1297,7 +1295,7 @@ extern "C" int tcar_step_session_forward(const tcar_ctx_t* c, const tcar_batch_t
   if (!c->scoring) return TCAR_E_ARG;                   // split-bf16 modes only
   const Geo g(c->d);
   RET(session_forward(c, bt, g, stream, false, -1, [](int, TcarOpt*) { return (int)TCAR_OK; }));
-  if (bt->K > 0 && bt->neg && c->neg_coef && c->negpart)
+  if (has_negatives(c, bt))
     RET(tcar_neg_fwd(&c->d, bt->B, bt->K, c->E, bt->neg, c->attout, c->neg_weight, c->neg_fb, c->neg_coef, c->negpart, stream));
   return TCAR_OK;
 }
@@ -1324,33 +1322,24 @@ extern "C" int tcar_shard_begin(const tcar_ctx_t* c, const tcar_batch_t* bt, int
   if ((refresh_time || split_update) && s2) {
     // the candidate-side time planes of the shard depend on the time tables only: rebuilt on the aux stream beside the session
     // forward pass and the first all-gather (tcar_shard_score joins)
-    if (hipEventRecord((hipEvent_t)c->ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess)
-      return TCAR_E_LAUNCH;
+    RET(order(st, s2, c->ev[0]));
     if (refresh_time) {
       tcar_dims_t dc = c->d;
       dc.n_items = n_loc;
       const float* tt[5];
-      for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+      time_tables(c, tt);
       RET(tcar_cand_time_fwd_bf16(&dc, tt, c->mwdhm, nullptr, c->e16h, c->e16l, (void*)s2));
     }
-    if (split_update) {
-      const float* pieces = c->Gx + c->arena_n;
-      RET(tcar_clip_adam_rest_keep_o(c->E, g.ek, c->big, c->Mi, c->Vi, g.N, g.ldh, c->slot_item, c->sqn_dense, pieces, c->use_dense,
-                                     c->clip, lr_pending, c->b1, c->b2, c->eps, c->e16h, c->e16l, g.ek, c->adam_bitmap, (void*)s2,
-                                     tcar_fixed::rest_grid));
-      RET(zero_arena(c, s2));              // (behind the rest pass: it reads the norm slots and pieces the zero clears)
-    }
-    if (hipEventRecord((hipEvent_t)c->ev[5], s2) != hipSuccess) return TCAR_E_LAUNCH;
-    if (split_update &&        // the marks are cleared BEHIND the event the main stream waits for (the clear is a launch of its own)
-        hipMemsetAsync(c->adam_bitmap, 0, (size_t)(((g.N + 31) / 32 + 15) & ~15) * sizeof(uint32_t), s2) != hipSuccess)
-      return TCAR_E_LAUNCH;
+    // (the arena zero behind the rest pass: it reads the norm slots and pieces the zero clears — and in front of ev[5])
+    if (split_update) RET(rest_pass(c, g, lr_pending, s2, c->ev[5], [&] { return zero_arena(c, s2); }));
+    else RET(record(s2, c->ev[5]));
   }
   if (!split_update) RET(zero_arena(c, st));
   if (!bt) return tcar_shard_pack_head(0, cap, g.ek, 0, Kc, nullptr, nullptr, nullptr, nullptr, head, ld_head, stream);
   RET(session_forward(c, bt, g, stream, false, -1, [](int, TcarOpt*) { return (int)TCAR_OK; }));
   // (split update: the negative term gathers item rows the rest pass may still be writing — and the arena is zeroed there)
-  if (split_update && hipStreamWaitEvent(st, (hipEvent_t)c->ev[5], 0) != hipSuccess) return TCAR_E_LAUNCH;
-  const bool has_neg = bt->K > 0 && bt->neg && c->neg_coef && c->negpart;
+  if (split_update) RET(wait_for(st, c->ev[5]));
+  const bool has_neg = has_negatives(c, bt);
   if (has_neg)
     RET(tcar_neg_fwd(&c->d, bt->B, bt->K, c->E, bt->neg, c->attout, c->neg_weight, c->neg_fb, c->neg_coef, c->negpart, stream));
   return tcar_shard_pack_head(bt->B, cap, g.ek, has_neg ? bt->K : 0, Kc, c->attout, bt->label, has_neg ? c->neg_coef : nullptr,
@@ -1398,12 +1387,11 @@ extern "C" int tcar_shard_score(const tcar_ctx_t* c, const tcar_shard_t* s, int 
   tcar_dims_t dc = c->d;
   dc.n_items = nl;
   if (refresh_time) {
-    if (hipStream_t s2 = aux_stream(c)) {      // tcar_shard_begin issued the refresh on the aux stream
-      (void)s2;
-      if (hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)c->ev[5], 0) != hipSuccess) return TCAR_E_LAUNCH;
+    if (aux_stream(c)) {      // tcar_shard_begin issued the refresh on the aux stream
+      RET(wait_for((hipStream_t)stream, c->ev[5]));
     } else {
       const float* tt[5];
-      for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+      time_tables(c, tt);
       RET(tcar_cand_time_fwd_bf16(&dc, tt, c->mwdhm, nullptr, c->e16h, c->e16l, stream));
     }
   }
@@ -1417,7 +1405,7 @@ extern "C" int tcar_shard_score(const tcar_ctx_t* c, const tcar_shard_t* s, int 
     // backward), ONE GEMM over 2 ldh + 160 columns whose epilogue leaves exp(x - group max) as the plane that becomes dlogits and
     // per-group (max, sum) pairs — no [W*cap, n_loc] fp32 logits —, then the shard's row of the statistics exchange
     const float* tt[5];
-    for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+    time_tables(c, tt);
     const int64_t lda = s->ld_att ? s->ld_att : g.ek;
     RET(tcar_time_scores_clip(&dc, tt, Bq, s->att_all, lda, c->p16h, c->p16l, 160, c->tclip, stream));
     TcarOpt ol = opt_of(c);
@@ -1468,8 +1456,7 @@ extern "C" int tcar_shard_backward(const tcar_ctx_t* c, const tcar_shard_t* s, c
     // dE (aux stream) behind the rescale through an EVENT, dE launched first.  (backward_impl orders dE behind dX's START flag instead;
     // here that form — dX first, the poll, then dE — measured 14 us per step SLOWER on the one-rank shard, 0.548 against 0.534 ms in
     // 4 of 4 interleaved rounds, and neutral at the 8-rank shape: profiles/r06_ab_experiments.txt section 13.)
-    if (s2 && (hipEventRecord((hipEvent_t)c->ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-      return TCAR_E_LAUNCH;
+    if (s2) RET(order(st, s2, c->ev[0]));
     TcarOpt ox = opt_of(c);
     TcarOpt ob = opt_of(c);
     // (a short shard leaves the 192-row tiles too few workgroups for the chip: 128-row tiles then)
@@ -1492,7 +1479,7 @@ extern "C" int tcar_shard_backward(const tcar_ctx_t* c, const tcar_shard_t* s, c
     // dP is complete: tcar_shard_finish lets the candidate-side table gradients (aux stream, behind dE) wait for this point — for
     // the launch's own flag when it carries one (a context with flag forks: no event record on this chain, which heads for the dX
     // exchange), else for ev[2]
-    if (s2 && !fork_commit(c, FK_REDUCE, orr) && hipEventRecord((hipEvent_t)c->ev[2], st) != hipSuccess) return TCAR_E_LAUNCH;
+    if (s2 && !fork_commit(c, FK_REDUCE, orr)) RET(record(st, c->ev[2]));
     return TCAR_OK;
   }
   RET(tcar_softmax_combine(s->world, Bq, stats_all, s->lab_all, s->lse, s->ce, stream));
@@ -1501,11 +1488,10 @@ extern "C" int tcar_shard_backward(const tcar_ctx_t* c, const tcar_shard_t* s, c
   float* d_et = c->big + (size_t)nl * g.ldh;
   // dE of the shard on the aux stream beside dX (the caller's stream: dX heads for the reduce-scatter, the critical path)
   hipStream_t st = (hipStream_t)stream, s2 = aux_stream(c);
-  if (s2 && (hipEventRecord((hipEvent_t)c->ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, (hipEvent_t)c->ev[0], 0) != hipSuccess))
-    return TCAR_E_LAUNCH;
+  if (s2) RET(order(st, s2, c->ev[0]));
   RET(tcar_gemm_bf16_perm(2, nl, g.ldh + g.pt, (Bq + 31) & ~31, s->dl16h, s->dl16l, nlpad, Bp, s->ap16h, s->ap16l, g.ldh + g.pt, Bp,
                           Gi, g.ldh, d_et, g.pt, g.ldh, c->et_perm, g.ldt, nsb, 1, s2 ? (void*)s2 : stream));
-  if (s2 && hipEventRecord((hipEvent_t)c->ev[1], s2) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2) RET(record(s2, c->ev[1]));
   const int S = tcar_gemm_splitk_effective(nlpad, c->splitk);
   RET(tcar_gemm_bf16(0, Bq, g.ek, nlpad, s->dl16h, s->dl16l, nlpad, Bp, c->e16h, c->e16l, g.ek, nlpad, s->slabs, g.ek, nullptr, 0,
                      0, nsb, c->splitk, stream));
@@ -1529,25 +1515,23 @@ extern "C" int tcar_shard_finish(const tcar_ctx_t* c, const tcar_shard_t* s, int
     RET(tcar_neg_scatter_range(&c->d, (int64_t)s->world * s->cap, K, s->n0, nl, neg_all, s->att_all, s->ld_att ? s->ld_att : g.ek, coef_all, c->big, sf));
   }
   // the shard's dense item norm, BEFORE any gathered row is scattered in (S5), straight into the item slot of the pieces
-  tcar_segments_t one = {};
-  one.nseg = 1; one.off[0] = 0; one.len[0] = (int64_t)nl * g.ldh; one.slot[0] = c->slot_item;
-  RET(tcar_sqnorm(c->big, &one, c->Gx + c->arena_n, sf));
+  RET(item_norm(c, g, nl, c->Gx + c->arena_n, sf));
   tcar_grads_t gr;
   grads_of(c, gr);
   const float* tt[5];
-  for (int k = 0; k < 5; ++k) tt[k] = W(c, TCAR_V_MONTH + k);
+  time_tables(c, tt);
   if (shard_onehot(c, s, nullptr)) {
     // from the (q, z) pairs of dE (this stream) and dP of the slab reduce (main stream: its flag or ev[2], tcar_shard_backward)
     if (s2) {
       if (fork_live(c, FK_REDUCE)) RET(fork_go(c, FK_REDUCE, (hipStream_t)stream, s2, c->ev[2]));
-      else if (hipStreamWaitEvent(s2, (hipEvent_t)c->ev[2], 0) != hipSuccess) return TCAR_E_LAUNCH;
+      else RET(wait_for(s2, c->ev[2]));
     }
     RET(tcar_cand_time_bwd_onehot_w(&dc, s->world * s->cap, c->inv_off, c->qz, c->dP, s->att_all, s->ld_att ? s->ld_att : g.ek,
                                     c->tclip, c->ct_ws, &gr, sf, TcarWait{}, 1));
   } else {
     RET(tcar_cand_time_bwd_indexed(&dc, tt, c->inv_n, c->inv_off, c->big + (size_t)nl * g.ldh, 1, c->ct_ws, &gr, sf));
   }
-  if (s2 && hipEventRecord((hipEvent_t)c->ev[3], s2) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2) RET(record(s2, c->ev[3]));
   return TCAR_OK;
 }
 
@@ -1555,7 +1539,7 @@ extern "C" int tcar_shard_finish(const tcar_ctx_t* c, const tcar_shard_t* s, int
 // backward, weight gradients): before the gathered rows are scattered into the shard's gradient and the arena is exchanged
 extern "C" int tcar_shard_join(const tcar_ctx_t* c, void* stream) {
   if (!c) return TCAR_E_ARG;
-  if (aux_stream(c) && hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)c->ev[3], 0) != hipSuccess) return TCAR_E_LAUNCH;
+  if (aux_stream(c)) RET(wait_for((hipStream_t)stream, c->ev[3]));
   return TCAR_OK;
 }
 
@@ -1565,70 +1549,29 @@ extern "C" int tcar_step_session_backward(const tcar_ctx_t* c, const tcar_batch_
   if (!c->scoring || !dx_rows || !rows_out || (rows_ld && (rows_ld < c->d.ldh || (rows_ld & 3)))) return TCAR_E_ARG;
   const Geo g(c->d);
   const int B = bt->B, T = bt->T, BT = B * T;
-  const bool has_neg = bt->K > 0 && bt->neg && c->neg_coef && c->negpart;
+  const bool has_neg = has_negatives(c, bt);
+  hipStream_t st = (hipStream_t)stream, s2 = aux_stream(c);
   // dattout = (dX + the negative term's part) * tanh'(attout), + the bias gradients of both output transforms
-  const bool detc = c->gw_rows != nullptr;       // order-fixed bias / residual-weight gradients (see backward_impl)
+  const bool detc = c->gw_rows != nullptr;       // order-fixed bias / residual-weight gradients (see session_backward)
   RET(tcar_splitk_reduce_dact(dx_rows, 1, B, g.ek, g.ek, has_neg ? c->negpart : nullptr, g.ic, g.ic, c->attout, g.ek, 2,
                               c->dattout, detc ? nullptr : G(c, TCAR_V_O_B), g.ic, detc ? nullptr : G(c, TCAR_V_OT_B), stream));
-  // dpooled = dattout W_o^T in the split form of the fused step (backward_impl): every 128-deep K chunk is its own set of workgroups
-  // writing its own slab, the pool backward folds them in slab order while it loads dpooled (round 5: 376 workgroups and one global
-  // round trip instead of 104 walking 8 / 5 serial stages — 30 -> 19 us on this chain)
-  const int nd_ic = units(g.ic), nd_pt = units(g.pt);
-  const int64_t dstride = (int64_t)B * g.ek;
-  const bool dsplit = detc && c->proj_slabs && c->proj_slab_floats >= (nd_ic > nd_pt ? nd_ic : nd_pt) * dstride;
-  {
-    tcar_gemm_desc_t p[2];
-    float* dp = dsplit ? c->proj_slabs : c->dpooled;
-    p[0] = prob1(B, g.ic, c->dattout, g.ek, W(c, TCAR_V_O_W), g.ic, g.ic, dp, g.ek, nullptr, 0, 0, dsplit ? nd_ic : 1);
-    p[1] = prob1(B, g.pt, c->dattout + g.ic, g.ek, W(c, TCAR_V_OT_W), g.pt, g.pt, dp + g.ic, g.ek, nullptr, 0, 0, dsplit ? nd_pt : 1);
-    RET(small_gemm(c, 1, 2, p, stream));
-  }
-  if (detc)
-    RET(tcar_attn_pool_bwd_slabs_o(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES),
-                                   c->alpha, dsplit ? c->proj_slabs : c->dpooled, dsplit ? nd_ic : 1, dsplit ? nd_pt : 1, dstride,
-                                   c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2, c->gw_rows, stream, nullptr));
-  else
-    RET(tcar_attn_pool_bwd_q(&c->d, B, T, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES),
-                             c->alpha, c->dpooled, c->dx_icp, c->dx_pt, c->dq, c->dpre1, c->dpre2, G(c, TCAR_V_M_WRES),
-                             G(c, TCAR_V_S_WRES), G(c, TCAR_V_Q2_B), stream));
-  {
-    tcar_gemm_desc_t p[4];
-    p[0] = prob1(B, g.ldh, c->dq, g.ic, W(c, TCAR_V_Q2_W), g.ic, g.ic, c->dq1, g.ldh);
-    p[0].dact = 1; p[0].dact_y = c->q1; p[0].ld_dact_y = g.ldh; p[0].colsum = detc ? nullptr : G(c, TCAR_V_Q1_B);
-    p[1] = prob1(BT, g.ldh, c->dpre1, g.ldh, W(c, TCAR_V_M_WIN), g.ldh, g.ldh, c->dx_icp, g.ic, nullptr, 0, 1);
-    p[2] = prob1(BT, g.ldt, c->dpre1, g.ldh, W(c, TCAR_V_M_WINT), g.ldh, g.ldh, c->dx_act, g.ldt);
-    p[3] = prob1(BT, g.pt, c->dpre2, g.ldh, W(c, TCAR_V_S_WIN), g.ldh, g.ldh, c->dx_pt, g.pt, nullptr, 0, 1);
-    TcarOpt oi = opt_of(c);
-    if (aux_stream(c)) oi.sig = fork_arm(c, FK_INGRAD);      // the weight-gradient fork below (flagged launches store write-through)
-    else fork_disarm(c, FK_INGRAD);
-    RET(small_gemm(c, 1, 4, p, stream, &oi));
-    (void)fork_commit(c, FK_INGRAD, oi);
-  }
-  {
-    // beside the row gradients on the aux stream (behind tcar_shard_finish there); tcar_shard_join covers it.  Forked IN FRONT of
-    // the click-query input gradient: the weight gradients need dq1 of the launch above, not dclick (round 4 timeline: the aux
-    // chain — weight gradients, column sums — ends the piece; 20 us earlier here is 20 us off the join).  Through the launch's flag
-    // where the context has flag forks (round 5: no event record on the main chain, the aux stream starts ~10 us earlier)
-    hipStream_t st = (hipStream_t)stream, s2 = aux_stream(c);
-    if (s2) RET(fork_go(c, FK_INGRAD, st, s2, c->ev[0]));
-    RET(weight_grads(c, g, B, BT, s2 ? (void*)s2 : stream));
-    if (detc) RET(det_colsums(c, g, B, s2 ? (void*)s2 : stream));
-  }
-  if (g.ldh == 256 && g.ldt == 64) {
-    // dclick = dq1 Wq1^T as ONE fp32 launch of whole-row dots (query.hip: the layer-1 half of the click-query backward, as in the
-    // fused step): 7 us where the 16-workgroup small GEMM walks four serial 64-deep stages (16-20 us) on this chain
-    RET(tcar_query_mlp_bwd_o(&c->d, B, nullptr, nullptr, W(c, TCAR_V_Q1_W), nullptr, c->dq1, c->dclick, stream, nullptr));
-  } else {
-    tcar_gemm_desc_t p = prob1(B, g.ct, c->dq1, g.ldh, W(c, TCAR_V_Q1_W), g.ldh, g.ldh, c->dclick, g.ct);
-    RET(small_gemm(c, 1, 1, &p, stream));
-  }
+  // (the input-gradient launch carries the flag of the weight-gradient fork below)
+  RET(session_backward(c, g, B, T, stream, SessionBwd{false, s2 != nullptr}));
+  // beside the row gradients on the aux stream (behind tcar_shard_finish there); tcar_shard_join covers it.  Forked IN FRONT of
+  // the click-query input gradient: the weight gradients need dq1 of the launch above, not dclick (round 4 timeline: the aux
+  // chain — weight gradients, column sums — ends the piece; 20 us earlier here is 20 us off the join).  Through the launch's flag
+  // where the context has flag forks (round 5: no event record on the main chain, the aux stream starts ~10 us earlier)
+  if (s2) RET(fork_go(c, FK_INGRAD, st, s2, c->ev[0]));
+  RET(weight_grads(c, g, B, BT, s2 ? (void*)s2 : stream));
+  if (detc) RET(det_colsums(c, g, B, s2 ? (void*)s2 : stream));
+  RET(click_input_grad(c, g, B, stream));
   tcar_tables_t tab;
   tcar_grads_t gr;
   tables_of(c, tab);
   grads_of(c, gr);
   // (the small tables keep their LDS + atomic form here: the aux stream of this path already carries the dE tail, the weight
   // gradients and the column sums, and the order-fixed kernel behind them delays the join: 0.69 -> 0.72+ ms on one rank)
-  if (aux_stream(c) && hipEventRecord((hipEvent_t)c->ev[3], aux_stream(c)) != hipSuccess) return TCAR_E_LAUNCH;
+  if (s2) RET(record(s2, c->ev[3]));
   gr.rows_out = rows_out;
   gr.rows_ld = rows_ld;
   RET(tcar_gather_clip_bwd(&c->d, &tab, bt, c->dx_icp, c->dx_pt, c->dx_act, c->dclick, &gr, stream));

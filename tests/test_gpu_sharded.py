@@ -30,8 +30,15 @@ def _free_port():
     return p
 
 
-@pytest.mark.parametrize("K,scoring", [(7, "bf16x3"), (0, "bf16x3"), (7, "bf16x3-mixed"), (0, "bf16x3-mixed")])
-def test_single_rank_sharded_path_matches_oracle(K, scoring):
+# (N, H, Ht, B, T).  ldh = 256: the click-query input gradient of the session backward is the whole-row launch; ldh = 64 (a row of
+# test_gpu_parity.CASES): its small-GEMM form.  Both have ldt = 64: the mixed shard takes its one-hot form at either (_score_form)
+_GEO_LDH256, _GEO_LDH64 = (1000, 250, 64, 33, 5), (1000, 40, 16, 3, 40)
+
+
+@pytest.mark.parametrize("K,scoring,geometry",
+                         [pytest.param(K, sc, _GEO_LDH256, id="%d-%s" % (K, sc)) for sc in ("bf16x3", "bf16x3-mixed") for K in (7, 0)] +
+                         [pytest.param(K, sc, _GEO_LDH64, id="%d-%s-ldh64" % (K, sc)) for sc in ("bf16x3", "bf16x3-mixed") for K in (7, 0)])
+def test_single_rank_sharded_path_matches_oracle(K, scoring, geometry):
     """bf16x3: materialised logits of the shard; bf16x3-mixed (the benchmarked precision): the shard runs the single-GPU schedule —
     softmax epilogue with a label window, one-hot time segment, (q, z) form of dE, dP form of dX — between the same exchanges"""
     if not torch.cuda.is_available():
@@ -40,7 +47,7 @@ def test_single_rank_sharded_path_matches_oracle(K, scoring):
     from oracle.tcar_oracle import TcarOracle
     from tcar_amd.sharded import ShardedEngine
     from test_gpu_parity import _case, check_grads, close
-    N, H, Ht, B, T = 1000, 250, 64, 33, 5
+    N, H, Ht, B, T = geometry
     params, content, mw, batch = _case(N, H, Ht, B, T, max(K, 1), seed=321)
     if K == 0:
         batch = {k: v for k, v in batch.items() if k != "neg"}
