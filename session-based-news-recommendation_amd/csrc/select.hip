@@ -7,7 +7,7 @@
 // panel is the k best of the catalog whatever the partition and whatever order candidates arrive in LDS.
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
-#include "../../include/tcar_serve.h"
+#include "../../include/tcar_window.h"
 
 namespace {
 
@@ -35,10 +35,17 @@ __device__ __forceinline__ bool key_gt(float av, int ai, float bv, int bi) { ret
 
 // One workgroup per session.  The row slice is read ONCE into registers (as in rank_topk_rows_kernel<512, R>); columns outside the
 // slice and excluded items become NaN after the statistics: a NaN compares false with everything, so it is never a candidate.
-template <int R>
+//
+// W (include/tcar_window.h): item n0 + j is in the POOL of session b iff wlo[b] <= key[n0 + j] < whi[b], or it is the label of a
+// labelled call.  Columns out of the pool do not exist: -inf in the statistics (no count, no max, exp = 0; a NaN would poison the
+// sum), NaN among the candidates (a -inf would still beat the (-inf, -1) "nothing" key and enter a short list).  Which of its 4 R
+// columns are in the pool a thread keeps as 4 R bits (`pool`), from ONE read of the key slice; the slice has no second copy.
+template <int R, bool W = false>
 __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int k,
                                                               const int32_t* __restrict__ label, const float* __restrict__ lab_score,
-                                                              const int32_t* __restrict__ excl, int X, float* __restrict__ state) {
+                                                              const int32_t* __restrict__ excl, int X, float* __restrict__ state,
+                                                              const int32_t* __restrict__ key, const int32_t* __restrict__ wlo,
+                                                              const int32_t* __restrict__ whi) {
   constexpr int NT = SEL_NT, NWV = NT / 64, CAP = 2 * NT;
   __shared__ float shv[NWV];
   __shared__ int shi[NWV];
@@ -54,6 +61,43 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
   float* st = state + (long)b * sel_row_words(k);
   int* sti = reinterpret_cast<int*>(st);
   const float ninf = -INFINITY, dead = __builtin_nanf("");
+  unsigned pool[W ? (4 * R + 31) / 32 : 1] = {};      // W: bit 4 r + j = column (tid + r NT) 4 + j is in the pool
+  if constexpr (W) {
+    // The key slice key[n0 .. n0 + n), read once: 16-byte loads where key + n0 is aligned, with scalar loads for a last group of
+    // fewer than four columns; scalar loads (index clamped into the slice, no branch) where it is not.  No load leaves the slice.
+    const int32_t* kp = key + n0;
+    const int lo = wlo[b], hi = whi[b];
+    const int labc = lab_score ? label[b] - n0 : -1;          // a labelled call: the label's column is always in the pool
+    auto bits4 = [&](int c, int kx, int ky, int kz, int kw) __attribute__((always_inline)) -> unsigned {
+      return (unsigned)((((lo <= kx) & (kx < hi)) | (c + 0 == labc)) & (c + 0 < n)) |
+             (unsigned)((((lo <= ky) & (ky < hi)) | (c + 1 == labc)) & (c + 1 < n)) << 1 |
+             (unsigned)((((lo <= kz) & (kz < hi)) | (c + 2 == labc)) & (c + 2 < n)) << 2 |
+             (unsigned)((((lo <= kw) & (kw < hi)) | (c + 3 == labc)) & (c + 3 < n)) << 3;
+    };
+    auto scalar4 = [&](int c) __attribute__((always_inline)) -> unsigned {
+      const int last = n - 1;
+      return bits4(c, kp[min(c + 0, last)], kp[min(c + 1, last)], kp[min(c + 2, last)], kp[min(c + 3, last)]);
+    };
+    if ((reinterpret_cast<uintptr_t>(kp) & 15) == 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int c = (tid + r * NT) * 4;
+        const int4 q = (c + 3 < n) ? *reinterpret_cast<const int4*>(kp + c) : make_int4(0, 0, 0, 0);
+        pool[(4 * r) >> 5] |= (c + 3 < n ? bits4(c, q.x, q.y, q.z, q.w) : 0u) << ((4 * r) & 31);
+      }
+      if (n & 3) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int c = (tid + r * NT) * 4;
+          if (c < n && c + 3 >= n) pool[(4 * r) >> 5] |= scalar4(c) << ((4 * r) & 31);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < R; ++r) pool[(4 * r) >> 5] |= scalar4((tid + r * NT) * 4) << ((4 * r) & 31);
+    }
+    __builtin_amdgcn_sched_barrier(0);               // the keys are bits before the slice takes its 4 R registers
+  }
   // ---- load: the slice, this thread's entry of the running list, the running statistics
   float4 v[R];
 #pragma unroll
@@ -97,6 +141,13 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
     if (c + 1 >= n) v[r].y = ninf;
     if (c + 2 >= n) v[r].z = ninf;
     if (c + 3 >= n) v[r].w = ninf;
+    if constexpr (W) {                    // out of the pool: -inf IN PLACE (the value is never needed again; the bits say which)
+      const unsigned p = pool[(4 * r) >> 5] >> ((4 * r) & 31);
+      if (!(p & 1u)) v[r].x = ninf;
+      if (!(p & 2u)) v[r].y = ninf;
+      if (!(p & 4u)) v[r].z = ninf;
+      if (!(p & 8u)) v[r].w = ninf;
+    }
     if (counting)
       cnt += (v[r].x > xl && c + 0 != labc) + (v[r].y > xl && c + 1 != labc) + (v[r].z > xl && c + 2 != labc) +
              (v[r].w > xl && c + 3 != labc);
@@ -106,12 +157,27 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
   m = wave_max(m);
   if (lane == 0) { shc[w] = cnt; shv[w] = m; }
+  if constexpr (W) {
+    unsigned any = 0u;
+#pragma unroll
+    for (int i = 0; i < (4 * R + 31) / 32; ++i) any |= pool[i];
+    const bool wave_any = __any(any != 0u);
+    if (lane == 0) shi[w] = wave_any;
+  }
   __syncthreads();
   int tot = 0;
   float gm = old_m;
 #pragma unroll
   for (int i = 0; i < NWV; ++i) { tot += shc[i]; gm = fmaxf(gm, shv[i]); }
   const int has_excl = any_excl;
+  if constexpr (W) {
+    // A slice wholly out of the pool folds nothing: count, max, sum and list stay the bits they are.  (With an empty state, old_m =
+    // -inf, its maximum is -inf as well and exp(x - gm) would be exp(-inf + inf).)  Uniform over the workgroup.
+    int pooled_waves = 0;
+#pragma unroll
+    for (int i = 0; i < NWV; ++i) pooled_waves += shi[i];
+    if (!pooled_waves) return;
+  }
   __syncthreads();
   {
     // online softmax: m' = max(m, slice max), s = s exp(m - m') + sum exp(x - m'); fixed order within a launch
@@ -133,12 +199,13 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
     }
     __syncthreads();
   }
-  // ---- from here on the registers hold CANDIDATES: padding columns and excluded items die
+  // ---- from here on the registers hold CANDIDATES: padding columns, excluded items and (W) columns out of the pool die
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int c = (tid + r * NT) * 4;
     unsigned bits = 0u;
     if (has_excl && c < n) bits = exb[c >> 5] >> (c & 31);
+    if constexpr (W) bits |= ~(pool[(4 * r) >> 5] >> ((4 * r) & 31));
     if (c + 0 >= n || (bits & 1u)) v[r].x = dead;
     if (c + 1 >= n || (bits & 2u)) v[r].y = dead;
     if (c + 2 >= n || (bits & 4u)) v[r].z = dead;
@@ -321,22 +388,36 @@ extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) {
   return TCAR_OK;
 }
 
-extern "C" int tcar_select_panel(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
-                                 const float* lab_score, const int32_t* excl, int X, void* state, void* stream) {
+extern "C" int tcar_window_abi_version(void) { return TCAR_WINDOW_ABI_VERSION; }
+
+// one fold; key == NULL: the unwindowed kernels
+extern "C" int tcar_select_panel_window(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
+                                        const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
+                                        const int32_t* key, const int32_t* lo, const int32_t* hi) {
+  if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
   if (B < 0 || k < 1 || k > SEL_MAX_K || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
   if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
   if (B == 0 || n == 0) return TCAR_OK;
   if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* st = (float*)state;
-  if (n <= SEL_NT * 4 * 2)
-    TCAR_LAUNCH((select_panel_kernel<2>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
-  else if (n <= SEL_NT * 4 * 8)
-    TCAR_LAUNCH((select_panel_kernel<8>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
-  else
-    TCAR_LAUNCH((select_panel_kernel<24>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st);
+#define SEL_FOLD(R, W) \
+  TCAR_LAUNCH((select_panel_kernel<R, W>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st, key, lo, hi)
+  if (n <= SEL_NT * 4 * 2) {
+    if (key) SEL_FOLD(2, true); else SEL_FOLD(2, false);
+  } else if (n <= SEL_NT * 4 * 8) {
+    if (key) SEL_FOLD(8, true); else SEL_FOLD(8, false);
+  } else {
+    if (key) SEL_FOLD(24, true); else SEL_FOLD(24, false);
+  }
+#undef SEL_FOLD
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
+}
+
+extern "C" int tcar_select_panel(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
+                                 const float* lab_score, const int32_t* excl, int X, void* state, void* stream) {
+  return tcar_select_panel_window(B, n0, n, panel, ld, k, label, lab_score, excl, X, state, stream, nullptr, nullptr, nullptr);
 }
 
 extern "C" int tcar_select_finish(int B, int k, const void* state, const float* lab_score, int32_t* topk, float* score, int32_t* rank,

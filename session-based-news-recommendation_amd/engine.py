@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Dims, Grads, Segments, Serve, Tables, check
+from ._lib import Batch, Dims, Grads, Segments, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -869,8 +869,40 @@ class TcarEngine(OpLevelStep):
         work_B x 49,152 floats (96 MiB at B = 512); other batch sizes were not measured."""
         return int(max(128, min(self.SERVE_MAX_PANEL, self.geo.Npad)))
 
-    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool):
-        """one tcar_serve_step; returns (rank, topk, ce, scores) views of the workspace (rank / ce only when `labelled`)"""
+    def set_item_keys(self, keys) -> None:
+        """The int32 key of every catalog item ([N], e.g. its publish time in minutes), copied to the device once: what the
+        `window=(lo, hi)` of eval_step_streamed / recommend compares (include/tcar_window.h).  None removes it."""
+        if keys is None:
+            self._item_keys = None
+            return
+        k = np.asarray(keys)
+        if k.shape != (self.geo.N,) or not np.issubdtype(k.dtype, np.integer):
+            raise ValueError("item keys: an integer array of length N = %d" % self.geo.N)
+        if k.size and (int(k.min()) < -2 ** 31 or int(k.max()) >= 2 ** 31):
+            raise ValueError("item keys must fit int32")
+        self._item_keys = torch.from_numpy(np.array(k, dtype=np.int32, order="C")).to(self.dev)      # (np.array: a copy the caller cannot write)
+
+    def _window(self, window, B: int) -> Window:
+        """(lo, hi), each a scalar or an int array [B] -> the descriptor of a windowed call; bounds beyond int32 are clipped to it"""
+        if getattr(self, "_item_keys", None) is None:
+            raise ValueError("a window compares item keys: call set_item_keys(keys) first")
+        try:
+            lo, hi = window
+            lo, hi = (np.ascontiguousarray(np.broadcast_to(np.clip(np.asarray(x, dtype=np.int64), -2 ** 31, 2 ** 31 - 1), (B,)),
+                                           dtype=np.int32) for x in (lo, hi))
+        except (TypeError, ValueError):
+            raise ValueError("window = (lo, hi), each a scalar or an int array of length B = %d" % B) from None
+        # lo and hi are the two rows of ONE workspace entry, so that they go up in one copy (measured: the host-to-device copies are
+        # most of what a window costs a small catalog's step, docs/EXPERIMENTS.md)
+        self.ws.ensure([Spec("win_lohi", (2, self.work_B), I32)])
+        self.win_lohi[:, :B].copy_(torch.from_numpy(np.stack([lo, hi])))
+        w = Window()
+        w.key, w.lo, w.hi = self._item_keys.data_ptr(), self.win_lohi[0].data_ptr(), self.win_lohi[1].data_ptr()
+        return w
+
+    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None):
+        """one tcar_serve_step (tcar_serve_step_window with a `window`); returns (rank, topk, ce, scores) views of the workspace
+        (rank / ce only when `labelled`)"""
         g = self.geo
         if self.shard != (0, g.N):
             raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
@@ -900,8 +932,13 @@ class TcarEngine(OpLevelStep):
         s.topk, s.score, s.rank, s.ce = (t.data_ptr() for t in (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
         if not labelled:
             bt = self._without_label(bt)
-        check(self.lib.tcar_serve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), self._stream()),
-              "tcar_serve_step")
+        if window is not None:
+            w = self._window(window, B)
+            check(self.lib.tcar_serve_step_window(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), C.byref(w),
+                                                  self._stream()), "tcar_serve_step_window")
+        else:
+            check(self.lib.tcar_serve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), self._stream()),
+                  "tcar_serve_step")
         self._time_dirty = False
         self.poll_fork_errors()
         return self.sel_rank[:B], self.sel_topk[:B], self.sel_ce[:B], self.sel_score[:B]
@@ -914,19 +951,23 @@ class TcarEngine(OpLevelStep):
         nb._keep = getattr(bt, "_keep", None)
         return nb
 
-    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None):
+    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None, window=None):
         """eval_step without the [B, N] score matrix: the catalog is scored `panel` columns at a time and folded into a running
         top-k / rank / softmax state per session.  Returns (rank[B] int32, topk[B,k] int32, ce[B] f32) — views of the workspace,
-        valid until the next streamed call.  `last_scores` holds the fp32 scores of the lists."""
+        valid until the next streamed call.  `last_scores` holds the fp32 scores of the lists.
+        window = (lo, hi), scalars or int arrays [B]: session b is evaluated inside its POOL — the items with lo[b] <= key < hi[b]
+        (set_item_keys) and its label; the list (-1 where the pool holds fewer than k), the rank and the cross entropy are those of
+        the pool alone."""
         self.flush()
         bt = bt or self.upload(batch)
-        rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True)
+        rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True, window)
         return rank, topk, ce
 
-    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None):
+    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None):
         """The k best next items of every session: (topk [B,k] int32, scores [B,k] f32), best first (score, then item id,
         descending); -1 where fewer than k items remain.  `batch` needs no "label" and no "neg".  exclude_seen drops the items of
-        the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot)."""
+        the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot).  window = (lo, hi), scalars or
+        int arrays [B]: only items with lo[b] <= key < hi[b] (set_item_keys) are candidates of session b; exclusions apply on top."""
         self.flush()
         if "label" not in batch:
             batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
@@ -941,5 +982,5 @@ class TcarEngine(OpLevelStep):
             if ex.shape[1]:
                 parts.append(torch.from_numpy(ex).to(self.dev))
         excl = torch.cat(parts, dim=1).contiguous() if parts else None
-        _, topk, _, scores = self._serve(bt, k, panel, excl, False)
+        _, topk, _, scores = self._serve(bt, k, panel, excl, False, window)
         return topk, scores

@@ -71,6 +71,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval_panel", default=0, type=int,
                     help="P > 0: evaluation scores the catalog P columns at a time and selects while it streams (no [B, N] score matrix, "
                          "any catalog size; P % 128 == 0, P <= 49152).  0: the materialised evaluation.  Not with --dp_mode sharded")
+    ap.add_argument("--fresh_hours", default=0, type=float,
+                    help="H > 0: evaluation ranks every session inside its POOL — the items published in the H hours up to the label's "
+                         "click (and the label) — not against the whole catalog.  Needs --eval_panel; not with --dp_mode sharded.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -85,6 +88,18 @@ def check_eval_panel(eval_panel, dp_mode):
                          "(the catalog-sharded engine evaluates with its own exchange)")
     if eval_panel and (eval_panel < 0 or eval_panel % 128 or eval_panel > 49152):
         raise ValueError("--eval_panel must be a multiple of 128 in [128, 49152] (0: off)")
+
+
+def check_fresh_hours(fresh_hours, eval_panel, dp_mode):
+    """--fresh_hours windows the streamed evaluation (include/tcar_window.h): it needs --eval_panel and the whole catalog on one engine"""
+    if not fresh_hours:
+        return
+    if fresh_hours < 0:
+        raise ValueError("--fresh_hours must be positive (0: off)")
+    if dp_mode == "sharded":
+        raise ValueError("--fresh_hours windows the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
+    if not eval_panel:
+        raise ValueError("--fresh_hours needs --eval_panel P: only the streamed evaluation takes a publish-time window")
 
 
 def load_datas(args):
@@ -143,6 +158,7 @@ def main(argv=None):
     np.random.seed(args.seed)
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
     check_eval_panel(args.eval_panel, args.dp_mode)
+    check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -140,6 +140,11 @@ class Seq2SeqAttNN():
         self.eval_panel = int(args.get('eval_panel', 0) or 0)       # > 0: test() selects while the catalog streams by in panels
         if self.eval_panel and args.get('dp_mode', 'replica') == 'sharded':
             raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded")
+        self.fresh_hours = float(args.get('fresh_hours', 0) or 0)   # > 0: test() ranks every session inside its publish-time pool
+        from .cli import check_fresh_hours
+        check_fresh_hours(self.fresh_hours, self.eval_panel, args.get('dp_mode', 'replica'))
+        self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
+        self._keys = self._key_t0 = None
         self._ds_cache = {}
         self.curEpoch = 0
         self.error_during_train = False
@@ -194,6 +199,34 @@ class Seq2SeqAttNN():
         if len(recList) == 0:
             return 0
         return float(M.unexp_batch(np.asarray([inSeq]), np.asarray([recList]), self._category_table())[0])
+
+    def _item_keys(self):
+        """int32 key of every item = its publish time in minutes since the earliest one; installed on the engine once"""
+        if self._keys is None:
+            pt = self.publish_time
+            if pt is None or len(pt) != self.candidate_n - 1 or any(t is None for t in pt):
+                raise ValueError("a publish-time window needs args['publish_time']: one datetime per item, none of them None")
+            ts = np.asarray(pt, dtype="datetime64[s]")
+            self._key_t0 = ts.min()
+            minutes = (ts - self._key_t0).astype(np.int64) // 60
+            if int(minutes.max()) >= 2 ** 31 - 1:
+                raise ValueError("publish times span more minutes than an int32 key holds")
+            self._keys = minutes.astype(np.int32)
+            self.engine.set_item_keys(self._keys)
+        return self._keys
+
+    def minute_of(self, when) -> np.ndarray:
+        """datetimes -> the minutes of the item keys (since the earliest publish time): the unit of a window's bounds"""
+        self._item_keys()
+        return (np.asarray(when, dtype="datetime64[s]") - self._key_t0).astype(np.int64) // 60
+
+    def _fresh_window(self, feed, time_dict, hours):
+        """the pools of a test batch: hi = the minute of the label's click + 1, lo = hi - 60 hours -> (lo, hi, label outside its window)"""
+        T = feed["seq"].shape[1]
+        hi = self.minute_of([time_dict[key][T]['click_t'] for key in feed["keys"]]) + 1
+        lo = hi - int(round(60 * hours))
+        kl = self._item_keys()[np.asarray(feed["label"], dtype=np.int64)].astype(np.int64)
+        return lo, hi, ~((lo <= kl) & (kl < hi))
 
     def _sampler(self, data, neighbor_dict=None, item_dict=None, neg_num=None):
         # (len_dict, session_dict, session_time_dict) as util.py:56 returns it, or with a 4th element: a prebuilt
@@ -320,6 +353,15 @@ class Seq2SeqAttNN():
     def test(self, sess, test_data, args):
         print('Measuring...')
         eng = self.engine
+        fresh = float(args.get('fresh_hours', self.fresh_hours) or 0)       # > 0: every session inside its publish-time pool
+        time_dict = test_data[2] if len(test_data) > 2 else None
+        if fresh:
+            from .cli import check_fresh_hours
+            check_fresh_hours(fresh, int(args.get('eval_panel', self.eval_panel) or 0), args.get('dp_mode', 'replica'))
+            if not time_dict:
+                raise ValueError("fresh_hours takes the label's click time from the fold's session_time_dict, which this fold lacks")
+            self._item_keys()
+        outside = []
         cat = self._category_table()
         hits, mrrs, ndcgs, ilds, unexps, losses = [], [], [], [], [], []
         sampler = self._sampler(test_data)
@@ -339,7 +381,11 @@ class Seq2SeqAttNN():
             if feed is None:
                 continue
             bt = eng.upload(feed)
-            if panel:            # streamed: no [B, N] score matrix (engine.eval_step_streamed)
+            if fresh:            # streamed, every session inside its pool (include/tcar_window.h)
+                w_lo, w_hi, out = self._fresh_window(feed, time_dict, fresh)
+                outside += out.tolist()
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=(w_lo, w_hi))
+            elif panel:          # streamed: no [B, N] score matrix (engine.eval_step_streamed)
                 rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel)
             else:
                 rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
@@ -381,11 +427,18 @@ class Seq2SeqAttNN():
         print('MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(m_mrr, m_hit, m_ndcg))
         self.last_metrics = {"mrr": m_mrr, "recall": m_hit, "ndcg": m_ndcg, "loss": m_loss, "ild": m_ild,
                              "unexp": m_unexp, "coverage": n_covered}
+        if fresh:           # (these labels are still scored: a label is always in its session's pool)
+            share = self._allsum([float(np.sum(outside))])[0] / n
+            print('labels outside their window: {}'.format(share))
+            self.last_metrics["labels_outside"] = share
         return m_hit
 
     # ---------------------------------------------------------------------------------------- recommend
-    def recommend(self, sessions, k=20, **kw):
+    def recommend(self, sessions, k=20, window=None, **kw):
         """The k best next items of every session of `sessions` — a feed dict as the samplers build it (seq, pm, pd, pw, ph, pmi,
         gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
-        has already read are left out (engine.TcarEngine.recommend has the options)."""
-        return self.engine.recommend(sessions, k=k, **kw)
+        has already read are left out (engine.TcarEngine.recommend has the options).  window = (lo, hi), scalars or arrays [B], in
+        minutes since the earliest publish time (`minute_of(datetime)`): only items published in [lo, hi) are candidates."""
+        if window is not None:
+            self._item_keys()
+        return self.engine.recommend(sessions, k=k, window=window, **kw)

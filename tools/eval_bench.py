@@ -1,9 +1,11 @@
 """Evaluation-step throughput (forward + rank / top-20 + CE), B = 512, k = 20.
-Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]]] [--rounds R]
+Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]] [--window FRAC[,FRAC...]]] [--rounds R]
 
 Without --streamed: eval_step (materialised [B, N] scores) at the Globo shape, as before.  With --streamed: eval_step and
 eval_step_streamed at every panel size named (default: the engine's default panel), alternating in the same process for `rounds`
-rounds so that the spread between rounds is visible; the streamed results are compared with eval_step's at the timed size."""
+rounds so that the spread between rounds is visible; the streamed results are compared with eval_step's at the timed size.
+--window FRAC: also the windowed streamed step (include/tcar_window.h) with key = item index and [lo, hi) = the last FRAC of the
+catalog for every session, timed beside the unwindowed one at every panel size."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -18,6 +20,7 @@ ap.add_argument("iters", nargs="?", type=int, default=100)
 ap.add_argument("--n_items", type=int, default=46033)
 ap.add_argument("--streamed", action="store_true")
 ap.add_argument("--panel", type=str, default="", help="comma-separated panel sizes (multiples of 128, <= 49152); empty: the default panel")
+ap.add_argument("--window", type=str, default="", help="comma-separated fractions of the catalog (its last items) that form every session's pool")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -47,6 +50,10 @@ if not a.streamed:
     print("eval step: %.3f ms  = %.0f sessions/s" % (dt * 1e3, B / dt))
     sys.exit(0)
 panels = [int(p) for p in a.panel.split(",") if p] or [0]
+fracs = [float(f) for f in a.window.split(",") if f]
+if fracs:
+    eng.set_item_keys(np.arange(N, dtype=np.int32))
+windows = [(f, (N - int(round(f * N)), N)) for f in fracs]
 # same results?  (the panel GEMM may take another tile than the whole-catalog launch: the scores may differ in the last bits)
 r0, t0, c0 = [x.clone() for x in eng.eval_step(None, bt=res[0])]
 for P in panels:
@@ -59,4 +66,8 @@ for rnd in range(a.rounds):
     for P in panels:
         dt = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None))
         print("N=%d round %d eval_step_streamed panel=%d: %.3f ms = %.0f sessions/s" % (N, rnd, P or eng.default_panel(), dt * 1e3, B / dt))
+        for f, w in windows:
+            dw = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None, window=w))
+            print("N=%d round %d eval_step_streamed panel=%d window=%g: %.3f ms = %.0f sessions/s, %.3f of the unwindowed step" % (
+                N, rnd, P or eng.default_panel(), f, dw * 1e3, B / dw, dw / dt))
     sys.stdout.flush()
