@@ -7,7 +7,7 @@
 // panel is the k best of the catalog whatever the partition and whatever order candidates arrive in LDS.
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
-#include "../../include/tcar_window.h"
+#include "../../include/tcar_quota.h"
 
 namespace {
 
@@ -40,12 +40,16 @@ __device__ __forceinline__ bool key_gt(float av, int ai, float bv, int bi) { ret
 // labelled call.  Columns out of the pool do not exist: -inf in the statistics (no count, no max, exp = 0; a NaN would poison the
 // sum), NaN among the candidates (a -inf would still beat the (-inf, -1) "nothing" key and enter a short list).  Which of its 4 R
 // columns are in the pool a thread keeps as 4 R bits (`pool`), from ONE read of the key slice; the slice has no second copy.
-template <int R, bool W = false>
+//
+// Q (include/tcar_quota.h): at most `cap` entries of one category in the list.  The statistics are the shared code above the
+// extraction; only the extraction differs (the capped walk at the end of the kernel).  Q = false compiles none of it.
+template <int R, bool W = false, bool Q = false>
 __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int k,
                                                               const int32_t* __restrict__ label, const float* __restrict__ lab_score,
                                                               const int32_t* __restrict__ excl, int X, float* __restrict__ state,
                                                               const int32_t* __restrict__ key, const int32_t* __restrict__ wlo,
-                                                              const int32_t* __restrict__ whi) {
+                                                              const int32_t* __restrict__ whi, const int32_t* __restrict__ cat,
+                                                              int cap) {
   constexpr int NT = SEL_NT, NWV = NT / 64, CAP = 2 * NT;
   __shared__ float shv[NWV];
   __shared__ int shi[NWV];
@@ -110,6 +114,10 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
   if (tid < k) {
     si = sti[k + tid];
     if (si >= 0) sv = st[tid];
+  }
+  int sc = 0;                       // Q: the category of the state entry, re-read by index
+  if constexpr (Q) {
+    if (si >= 0) sc = cat[si];
   }
   const int old_cnt = sti[2 * k];
   const float old_m = st[2 * k + 1], old_s = st[2 * k + 2];
@@ -242,6 +250,22 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
       if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; }
     __syncthreads();
   };
+  // block_best with a payload (Q: the category of the key)
+  auto block_best_c = [&](float bv, int bi, int bc, float& fv, int& fi, int& fc) __attribute__((always_inline)) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o), oc = __shfl_xor(bc, o);
+      if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; bc = oc; }
+    }
+    if (lane == 0) { shv[w] = bv; shi[w] = bi; shc[w] = bc; }
+    __syncthreads();
+    fv = shv[0]; fi = shi[0]; fc = shc[0];
+#pragma unroll
+    for (int j = 1; j < NWV; ++j)
+      if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; fc = shc[j]; }
+    __syncthreads();
+  };
   // Threshold L = (lv, li): at least k candidates are at or above it, so the k best are.  A full list gives one for free (its last
   // entry: the k entries themselves are at or above it); else — or when too many columns pass it — the k-th largest of the
   // per-thread bests (phase A of rank_topk_rows_kernel).
@@ -294,6 +318,98 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
   if (nc > CAP && full) {
     phase_a();
     nc = compact();
+  }
+  if constexpr (Q) {
+    // ---- the capped walk (include/tcar_quota.h): candidates in list order, one taken iff fewer than `cap` of its category are.
+    // Lane j of EVERY wave keeps the category of list entry j (`mycat`), so "how many of category c are taken" is one ballot and the
+    // decision is uniform over the workgroup.  When a category reaches the cap its remaining candidates can be KILLED, after which
+    // every extracted best is acceptable: the number of block-wide rounds of a fold is bounded by k alone, never by n.
+    //   stage 1: the candidates at or above L, from LDS (<= 2 per thread, their categories in registers)
+    //   stage 2: when those run dry before k are taken (L only bounds the UNCAPPED k best) or do not fit the LDS: everything strictly
+    //            below the last key walked, from the registers, one entry per round as in the fallback of the uncapped kernel
+    //            (kills there cost a pass over the category slice, so they are put off: see below)
+    const int32_t* cp = cat + n0;
+    const bool cal = (reinterpret_cast<uintptr_t>(cp) & 15) == 0;
+    int taken = 0, mycat = 0;
+    auto accept = [&](float fv, int fi, int fc) __attribute__((always_inline)) -> bool {      // true: fc has reached the cap
+      if (tid == 0) { st[taken] = fv; sti[k + taken] = fi; }
+      if (lane == taken) mycat = fc;
+      ++taken;
+      return __popcll(__ballot(lane < taken && mycat == fc)) >= cap;
+    };
+    float pv = INFINITY;              // everything not walked yet is strictly below the key (pv, pi)
+    int pi = 0x7fffffff;
+    if (nc <= CAP) {
+      float c0v = tid < nc ? candv[tid] : ninf, c1v = tid + NT < nc ? candv[tid + NT] : ninf;
+      int c0i = tid < nc ? candi[tid] : -1, c1i = tid + NT < nc ? candi[tid + NT] : -1;
+      const int c0c = c0i >= 0 ? cat[c0i] : 0, c1c = c1i >= 0 ? cat[c1i] : 0;
+      while (taken < k) {
+        const bool first = key_gt(c0v, c0i, c1v, c1i);
+        float fv; int fi, fc;
+        block_best_c(first ? c0v : c1v, first ? c0i : c1i, first ? c0c : c1c, fv, fi, fc);
+        if (fi < 0) break;
+        const bool sat = accept(fv, fi, fc);
+        if (c0i == fi || (sat && c0c == fc)) { c0v = ninf; c0i = -1; }
+        if (c1i == fi || (sat && c1c == fc)) { c1v = ninf; c1i = -1; }
+      }
+      pv = lv; pi = li;               // what is left lies strictly below L; L = (-inf, -1): nothing is
+    }
+    if (taken < k && pi >= 0) {
+      // columns (and the state entry) of category kc die; `hit`: the thread's current best was one of them
+      bool hit = false;
+      auto kill_pass = [&](int kc) __attribute__((always_inline)) {
+        int t4 = tid * 4;
+        asm volatile("" : "+v"(t4));       // the 4 R load addresses are computed HERE, pass by pass: hoisted out of the rounds' loop
+                                           // they would be 2 R more live registers than the slice leaves
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          const int c = t4 + r * NT * 4;
+          if (c < n) {
+            int4 q;
+            if (cal && c + 3 < n) q = *reinterpret_cast<const int4*>(cp + c);
+            else { const int last = n - 1; q = make_int4(cp[min(c, last)], cp[min(c + 1, last)], cp[min(c + 2, last)], cp[min(c + 3, last)]); }
+            if (q.x == kc) { v[r].x = dead; hit |= n0 + c + 0 == cbi; }
+            if (q.y == kc) { v[r].y = dead; hit |= n0 + c + 1 == cbi; }
+            if (q.z == kc) { v[r].z = dead; hit |= n0 + c + 2 == cbi; }
+            if (q.w == kc) { v[r].w = dead; hit |= n0 + c + 3 == cbi; }
+          }
+          if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // four category loads in flight, not 4 R registers of them
+        }
+        if (si >= 0 && sc == kc) { hit |= si == cbi; sv = dead; si = -1; }
+      };
+      // A kill pass reads the whole category slice, so stage 2 starts LAZY: the categories that are full keep their columns, and an
+      // extracted best of such a category is rejected (one wasted round; its owner rescans).  Typically a handful of entries are
+      // missing and the next bests are acceptable.  After k rejected rounds the fold stops being lazy: every full category is killed,
+      // one pass each (at most k / cap of them, now and later), and from then on every extracted best is acceptable again.  So
+      // stage 2 spends at most k accepting and k + 1 rejecting rounds whatever the slice holds.
+      scan(pv, pi, cbv, cbi);
+      bool lazy = true;
+      int rejected = 0;
+      while (taken < k) {
+        float fv; int fi;
+        block_best(cbv, cbi, fv, fi);
+        if (fi < 0) break;
+        const int fc = cat[__builtin_amdgcn_readfirstlane(fi)];
+        hit = cbi == fi;
+        int j0 = 0, j1 = 0;                     // list entries whose category is to be killed now, if it is full
+        bool one = false;
+        if (lazy && __popcll(__ballot(lane < taken && mycat == fc)) >= cap) {
+          if (++rejected > k) { lazy = false; j1 = taken; }         // every full category, each once (at its first list entry)
+        } else {
+          const bool sat = accept(fv, fi, fc);
+          if (taken == k) break;
+          if (sat && !lazy) { j0 = taken - 1; j1 = taken; one = true; }        // the one that has just become full
+        }
+        for (int j = j0; j < j1; ++j) {
+          const int cj = __shfl(mycat, j);
+          const bool same = mycat == cj;
+          if ((one || __ballot(lane < j && same) == 0) && __popcll(__ballot(lane < taken && same)) >= cap) kill_pass(cj);
+        }
+        if (hit) scan(fv, fi, cbv, cbi);
+      }
+    }
+    if (tid >= taken && tid < k) { st[tid] = ninf; sti[k + tid] = -1; }
+    return;
   }
   if (nc <= CAP) {
     // k rounds over <= 2 candidates per thread
@@ -389,11 +505,13 @@ extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) {
 }
 
 extern "C" int tcar_window_abi_version(void) { return TCAR_WINDOW_ABI_VERSION; }
+extern "C" int tcar_quota_abi_version(void) { return TCAR_QUOTA_ABI_VERSION; }
 
-// one fold; key == NULL: the unwindowed kernels
-extern "C" int tcar_select_panel_window(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
-                                        const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
-                                        const int32_t* key, const int32_t* lo, const int32_t* hi) {
+// one fold; key == NULL: the unwindowed kernels; cat == NULL or cap >= k (no list of k entries can break such a cap): the uncapped ones
+extern "C" int tcar_select_panel_quota(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
+                                       const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
+                                       const int32_t* key, const int32_t* lo, const int32_t* hi, const int32_t* cat, int cap) {
+  if (cat ? cap < 1 : cap != 0) return TCAR_E_ARG;
   if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
   if (B < 0 || k < 1 || k > SEL_MAX_K || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
   if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
@@ -401,18 +519,28 @@ extern "C" int tcar_select_panel_window(int B, int n0, int n, const float* panel
   if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
   hipStream_t s = (hipStream_t)stream;
   float* st = (float*)state;
-#define SEL_FOLD(R, W) \
-  TCAR_LAUNCH((select_panel_kernel<R, W>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st, key, lo, hi)
-  if (n <= SEL_NT * 4 * 2) {
-    if (key) SEL_FOLD(2, true); else SEL_FOLD(2, false);
-  } else if (n <= SEL_NT * 4 * 8) {
-    if (key) SEL_FOLD(8, true); else SEL_FOLD(8, false);
-  } else {
-    if (key) SEL_FOLD(24, true); else SEL_FOLD(24, false);
-  }
+  const bool capped = cat && cap < k;
+#define SEL_FOLD(R, W, Q)                                                                                                         \
+  TCAR_LAUNCH((select_panel_kernel<R, W, Q>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st, key, \
+              lo, hi, cat, cap)
+#define SEL_FOLD_R(R)                                            \
+  do {                                                           \
+    if (capped) { if (key) SEL_FOLD(R, true, true); else SEL_FOLD(R, false, true); } \
+    else { if (key) SEL_FOLD(R, true, false); else SEL_FOLD(R, false, false); }      \
+  } while (0)
+  if (n <= SEL_NT * 4 * 2) SEL_FOLD_R(2);
+  else if (n <= SEL_NT * 4 * 8) SEL_FOLD_R(8);
+  else SEL_FOLD_R(24);
+#undef SEL_FOLD_R
 #undef SEL_FOLD
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
+}
+
+extern "C" int tcar_select_panel_window(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
+                                        const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
+                                        const int32_t* key, const int32_t* lo, const int32_t* hi) {
+  return tcar_select_panel_quota(B, n0, n, panel, ld, k, label, lab_score, excl, X, state, stream, key, lo, hi, nullptr, 0);
 }
 
 extern "C" int tcar_select_panel(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,

@@ -3,7 +3,7 @@
 // aux stream joined by events — no host synchronisation, no allocation.  tcar_train_step == sess.run([loss, global_step, train_op]) (model_combine.py:231);
 // tcar_eval_step == sess.run([softmax_input, cross_loss]) + util.cau_metrics + top-k (model_combine.py:283,296,301).
 #include "tcar_common.h"
-#include "../../include/tcar_window.h"
+#include "../../include/tcar_quota.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1253,10 +1253,12 @@ extern "C" int tcar_eval_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
 // panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel while the panel is cache-warm.
 // A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row blocks).
 // w (include/tcar_window.h): every fold keeps to the sessions' pools; NULL: the unwindowed step.
-extern "C" int tcar_serve_step_window(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
-                                      const tcar_window_t* w, void* stream) {
+// q (include/tcar_quota.h): every fold caps the list's entries per category; NULL: the uncapped step.
+extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
+                                     const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
   if (!c || !bt || !s || bt->B < 0) return TCAR_E_ARG;
   if (w && (!w->key || !w->lo || !w->hi)) return TCAR_E_ARG;
+  if (q && (!q->cat || q->cap < 1)) return TCAR_E_ARG;
   if (s->k < 1 || s->k > 64 || s->panel <= 0 || (s->panel & 127) || s->panel > 512 * 4 * 24) return TCAR_E_ARG;
   if (!s->panel_buf || !s->state || !s->topk || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0)) return TCAR_E_ARG;
   if (s->state_bytes < tcar_select_state_bytes(bt->B, s->k)) return TCAR_E_ARG;
@@ -1285,14 +1287,19 @@ extern "C" int tcar_serve_step_window(const tcar_ctx_t* c, const tcar_batch_t* b
     } else {
       RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, s->panel_buf, s->panel, nullptr, 0, 0, 1, stream));
     }
-    RET(tcar_select_panel_window(B, n0, n, s->panel_buf, s->panel, k, bt->label, lab, s->excl, s->X, s->state, stream,
-                                 w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr));
+    RET(tcar_select_panel_quota(B, n0, n, s->panel_buf, s->panel, k, bt->label, lab, s->excl, s->X, s->state, stream,
+                                w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, q ? q->cat : nullptr, q ? q->cap : 0));
   }
   return tcar_select_finish(B, k, s->state, lab, s->topk, s->score, lab ? s->rank : nullptr, lab ? s->ce : nullptr, stream);
 }
 
+extern "C" int tcar_serve_step_window(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
+                                      const tcar_window_t* w, void* stream) {
+  return tcar_serve_step_quota(c, bt, refresh_time, s, w, nullptr, stream);
+}
+
 extern "C" int tcar_serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s, void* stream) {
-  return tcar_serve_step_window(c, bt, refresh_time, s, nullptr, stream);
+  return tcar_serve_step_quota(c, bt, refresh_time, s, nullptr, nullptr, stream);
 }
 
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Dims, Grads, Segments, Serve, Tables, Window, check
+from ._lib import Batch, Dims, Grads, Segments, Quota, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -900,14 +900,26 @@ class TcarEngine(OpLevelStep):
         w.key, w.lo, w.hi = self._item_keys.data_ptr(), self.win_lohi[0].data_ptr(), self.win_lohi[1].data_ptr()
         return w
 
-    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None):
-        """one tcar_serve_step (tcar_serve_step_window with a `window`); returns (rank, topk, ce, scores) views of the workspace
-        (rank / ce only when `labelled`)"""
+    def _quota(self, max_per_category) -> Quota:
+        """max_per_category -> the descriptor of a capped call (include/tcar_quota.h) over the table of set_categories()"""
+        if isinstance(max_per_category, bool) or not isinstance(max_per_category, (int, np.integer)) or max_per_category < 1:
+            raise ValueError("max_per_category must be an int >= 1 (None: no cap)")
+        if getattr(self, "_cat", None) is None:
+            raise ValueError("max_per_category caps the items of one category: call set_categories(cat_of_item) first")
+        q = Quota()
+        q.cat, q.cap = self._cat.data_ptr(), int(min(max_per_category, 2 ** 31 - 1))
+        return q
+
+    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None,
+               max_per_category=None):
+        """one tcar_serve_step (tcar_serve_step_window with a `window`, tcar_serve_step_quota with a `max_per_category`); returns
+        (rank, topk, ce, scores) views of the workspace (rank / ce only when `labelled`)"""
         g = self.geo
         if self.shard != (0, g.N):
             raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
         if not 1 <= k <= 64:
             raise ValueError("k must be in [1, 64]")
+        quota = self._quota(max_per_category) if max_per_category is not None else None
         B = bt.B
         self._ensure_work(B, bt.T)
         panel = self.default_panel() if not panel else int(panel)
@@ -932,7 +944,12 @@ class TcarEngine(OpLevelStep):
         s.topk, s.score, s.rank, s.ce = (t.data_ptr() for t in (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
         if not labelled:
             bt = self._without_label(bt)
-        if window is not None:
+        if quota is not None:
+            w = self._window(window, B) if window is not None else None
+            check(self.lib.tcar_serve_step_quota(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s),
+                                                 C.byref(w) if w is not None else None, C.byref(quota), self._stream()),
+                  "tcar_serve_step_quota")
+        elif window is not None:
             w = self._window(window, B)
             check(self.lib.tcar_serve_step_window(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), C.byref(w),
                                                   self._stream()), "tcar_serve_step_window")
@@ -951,23 +968,30 @@ class TcarEngine(OpLevelStep):
         nb._keep = getattr(bt, "_keep", None)
         return nb
 
-    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None, window=None):
+    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None, window=None,
+                           max_per_category: Optional[int] = None):
         """eval_step without the [B, N] score matrix: the catalog is scored `panel` columns at a time and folded into a running
         top-k / rank / softmax state per session.  Returns (rank[B] int32, topk[B,k] int32, ce[B] f32) — views of the workspace,
         valid until the next streamed call.  `last_scores` holds the fp32 scores of the lists.
         window = (lo, hi), scalars or int arrays [B]: session b is evaluated inside its POOL — the items with lo[b] <= key < hi[b]
         (set_item_keys) and its label; the list (-1 where the pool holds fewer than k), the rank and the cross entropy are those of
-        the pool alone."""
+        the pool alone.
+        max_per_category = m >= 1: the list holds at most m items of one category of set_categories() (include/tcar_quota.h: the
+        walk in list order that takes an item iff fewer than m of its category are taken); rank and ce stay those of the uncapped
+        call, bit for bit."""
         self.flush()
         bt = bt or self.upload(batch)
-        rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True, window)
+        rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True, window, max_per_category)
         return rank, topk, ce
 
-    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None):
+    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,
+                  max_per_category: Optional[int] = None):
         """The k best next items of every session: (topk [B,k] int32, scores [B,k] f32), best first (score, then item id,
         descending); -1 where fewer than k items remain.  `batch` needs no "label" and no "neg".  exclude_seen drops the items of
         the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot).  window = (lo, hi), scalars or
-        int arrays [B]: only items with lo[b] <= key < hi[b] (set_item_keys) are candidates of session b; exclusions apply on top."""
+        int arrays [B]: only items with lo[b] <= key < hi[b] (set_item_keys) are candidates of session b; exclusions apply on top.
+        max_per_category = m >= 1: at most m items of one category of set_categories() in a list (include/tcar_quota.h); excluded
+        and out-of-window items consume no quota."""
         self.flush()
         if "label" not in batch:
             batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
@@ -982,5 +1006,5 @@ class TcarEngine(OpLevelStep):
             if ex.shape[1]:
                 parts.append(torch.from_numpy(ex).to(self.dev))
         excl = torch.cat(parts, dim=1).contiguous() if parts else None
-        _, topk, _, scores = self._serve(bt, k, panel, excl, False, window)
+        _, topk, _, scores = self._serve(bt, k, panel, excl, False, window, max_per_category)
         return topk, scores

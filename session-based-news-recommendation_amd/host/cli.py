@@ -74,6 +74,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fresh_hours", default=0, type=float,
                     help="H > 0: evaluation ranks every session inside its POOL — the items published in the H hours up to the label's "
                          "click (and the label) — not against the whole catalog.  Needs --eval_panel; not with --dp_mode sharded.  0: off")
+    ap.add_argument("--cat_cap", default=0, type=int,
+                    help="M > 0: evaluation lists hold at most M items of one category (the walk of include/tcar_quota.h); ILD, unexp and "
+                         "coverage describe the capped lists, and one more line gives their accuracy.  Needs --eval_panel; not with "
+                         "--dp_mode sharded; combines with --fresh_hours.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -100,6 +104,18 @@ def check_fresh_hours(fresh_hours, eval_panel, dp_mode):
         raise ValueError("--fresh_hours windows the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
     if not eval_panel:
         raise ValueError("--fresh_hours needs --eval_panel P: only the streamed evaluation takes a publish-time window")
+
+
+def check_cat_cap(cat_cap, eval_panel, dp_mode):
+    """--cat_cap caps the lists of the streamed evaluation (include/tcar_quota.h): it needs --eval_panel and the whole catalog on one engine"""
+    if not cat_cap:
+        return
+    if cat_cap < 0:
+        raise ValueError("--cat_cap must be positive (0: off)")
+    if dp_mode == "sharded":
+        raise ValueError("--cat_cap caps the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
+    if not eval_panel:
+        raise ValueError("--cat_cap needs --eval_panel P: only the streamed evaluation takes a per-category cap")
 
 
 def load_datas(args):
@@ -159,6 +175,7 @@ def main(argv=None):
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
     check_eval_panel(args.eval_panel, args.dp_mode)
     check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
+    check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -18,6 +18,14 @@ def metrics_from_ranks(ranks: np.ndarray, cutoff: int = 20):
     return hit, mrr, ndcg
 
 
+def list_ranks(topk, labels, cutoff: int = 20) -> np.ndarray:
+    """The 1-based place of every label in its OWN list (topk [B, k], 0-based ids, -1 = no entry), cutoff + 1 where the list's first
+    `cutoff` entries do not hold it: what metrics_from_ranks turns into the accuracy of the lists themselves."""
+    topk = np.asarray(topk)[:, :cutoff]
+    eq = topk == np.asarray(labels, dtype=np.int64)[:, None]
+    return np.where(eq.any(1), eq.argmax(1) + 1, cutoff + 1).astype(np.int64)
+
+
 def cau_metrics(preds, labels, cutoff=20):
     """Same contract as util.py:8-18: rank = 1 + #{j: preds[j] > preds[label]} (strict)."""
     preds = np.asarray(preds)

@@ -143,6 +143,9 @@ class Seq2SeqAttNN():
         self.fresh_hours = float(args.get('fresh_hours', 0) or 0)   # > 0: test() ranks every session inside its publish-time pool
         from .cli import check_fresh_hours
         check_fresh_hours(self.fresh_hours, self.eval_panel, args.get('dp_mode', 'replica'))
+        self.cat_cap = int(args.get('cat_cap', 0) or 0)             # > 0: test() caps the items of one category in every list
+        from .cli import check_cat_cap
+        check_cat_cap(self.cat_cap, self.eval_panel, args.get('dp_mode', 'replica'))
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -199,6 +202,13 @@ class Seq2SeqAttNN():
         if len(recList) == 0:
             return 0
         return float(M.unexp_batch(np.asarray([inSeq]), np.asarray([recList]), self._category_table())[0])
+
+    def _install_categories(self):
+        """the category table on the engine (set_categories), once per table: what eval_diversity and max_per_category read"""
+        cat = self._category_table()
+        if getattr(self, "_cat_on_engine", None) is not cat:
+            self.engine.set_categories(cat)
+            self._cat_on_engine = cat
 
     def _item_keys(self):
         """int32 key of every item = its publish time in minutes since the earliest one; installed on the engine once"""
@@ -362,15 +372,17 @@ class Seq2SeqAttNN():
                 raise ValueError("fresh_hours takes the label's click time from the fold's session_time_dict, which this fold lacks")
             self._item_keys()
         outside = []
-        cat = self._category_table()
+        cap = int(args.get('cat_cap', getattr(self, 'cat_cap', 0)) or 0)                   # > 0: at most `cap` items of one category in a list
+        if cap:
+            from .cli import check_cat_cap
+            check_cat_cap(cap, int(args.get('eval_panel', self.eval_panel) or 0), args.get('dp_mode', 'replica'))
         hits, mrrs, ndcgs, ilds, unexps, losses = [], [], [], [], [], []
+        c_hits, c_mrrs, c_ndcgs = [], [], []
         sampler = self._sampler(test_data)
         batch = 0
         pending = []
         # ILD / unexp pair counts and the set of recommended items stay on the device (tcar_eval_diversity)
-        if getattr(self, "_cat_on_engine", None) is not cat:
-            eng.set_categories(cat)
-            self._cat_on_engine = cat
+        self._install_categories()
         eng.reset_coverage()
         panel = int(args.get('eval_panel', self.eval_panel) or 0)
         if panel and args.get('dp_mode', 'replica') == 'sharded':
@@ -384,13 +396,16 @@ class Seq2SeqAttNN():
             if fresh:            # streamed, every session inside its pool (include/tcar_window.h)
                 w_lo, w_hi, out = self._fresh_window(feed, time_dict, fresh)
                 outside += out.tolist()
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=(w_lo, w_hi))
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=(w_lo, w_hi),
+                                                        max_per_category=cap or None)
+            elif cap:            # streamed, at most `cap` items of one category in a list (include/tcar_quota.h)
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, max_per_category=cap)
             elif panel:          # streamed: no [B, N] score matrix (engine.eval_step_streamed)
                 rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel)
             else:
                 rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
             ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)
-            pending.append((feed, rank.clone(), topk.clone() if args.get('is_print') else None, ce.clone(), ild_c, unexp_c, n_rec))     # device results; drained below
+            pending.append((feed, rank.clone(), topk.clone() if args.get('is_print') or cap else None, ce.clone(), ild_c, unexp_c, n_rec))     # device results; drained below
             if batch < 3:
                 tk = topk[0].cpu().numpy().tolist()
                 print('batch_in:', feed["seq"][0].tolist())
@@ -409,6 +424,11 @@ class Seq2SeqAttNN():
             il, un = M.diversity_from_counts(ild_c.cpu().numpy(), unexp_c.cpu().numpy(), n_rec.cpu().numpy(), feed["seq"].shape[1])
             ilds += il.tolist()
             unexps += un.tolist()
+            if cap:             # accuracy of the capped LISTS: the label's place in the list (the rank above is that of the whole pool)
+                h, m, n = M.metrics_from_ranks(M.list_ranks(topk.cpu().numpy(), feed["label"], 20), 20)
+                c_hits += h.tolist()
+                c_mrrs += m.tolist()
+                c_ndcgs += n.tolist()
             if args.get('is_print'):
                 self.printData(str(args['foldnum']) + '_' + str(self.curEpoch), feed["seq"].tolist(),
                                feed["label"].tolist(), topk.cpu().numpy().astype(np.int64).tolist())
@@ -431,14 +451,21 @@ class Seq2SeqAttNN():
             share = self._allsum([float(np.sum(outside))])[0] / n
             print('labels outside their window: {}'.format(share))
             self.last_metrics["labels_outside"] = share
+        if cap:
+            c_mrr, c_hit, c_ndcg = [v / n for v in self._allsum([float(np.sum(x)) for x in (c_mrrs, c_hits, c_ndcgs)])]
+            print('capped lists (<= {} per category): MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(cap, c_mrr, c_hit, c_ndcg))
+            self.last_metrics["capped"] = {"mrr": c_mrr, "recall": c_hit, "ndcg": c_ndcg}
         return m_hit
 
     # ---------------------------------------------------------------------------------------- recommend
-    def recommend(self, sessions, k=20, window=None, **kw):
+    def recommend(self, sessions, k=20, window=None, max_per_category=None, **kw):
         """The k best next items of every session of `sessions` — a feed dict as the samplers build it (seq, pm, pd, pw, ph, pmi,
         gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
         has already read are left out (engine.TcarEngine.recommend has the options).  window = (lo, hi), scalars or arrays [B], in
-        minutes since the earliest publish time (`minute_of(datetime)`): only items published in [lo, hi) are candidates."""
+        minutes since the earliest publish time (`minute_of(datetime)`): only items published in [lo, hi) are candidates.
+        max_per_category = m >= 1: at most m items of one category (the fold's category table) in a list."""
         if window is not None:
             self._item_keys()
-        return self.engine.recommend(sessions, k=k, window=window, **kw)
+        if max_per_category is not None:
+            self._install_categories()
+        return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)

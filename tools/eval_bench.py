@@ -1,11 +1,15 @@
 """Evaluation-step throughput (forward + rank / top-20 + CE), B = 512, k = 20.
-Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]] [--window FRAC[,FRAC...]]] [--rounds R]
+Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]] [--window FRAC[,FRAC...]]
+                                                               [--cap M[,M...]] [--cats C] [--cap_skew]] [--rounds R]
 
 Without --streamed: eval_step (materialised [B, N] scores) at the Globo shape, as before.  With --streamed: eval_step and
 eval_step_streamed at every panel size named (default: the engine's default panel), alternating in the same process for `rounds`
 rounds so that the spread between rounds is visible; the streamed results are compared with eval_step's at the timed size.
 --window FRAC: also the windowed streamed step (include/tcar_window.h) with key = item index and [lo, hi) = the last FRAC of the
-catalog for every session, timed beside the unwindowed one at every panel size."""
+catalog for every session, timed beside the unwindowed one at every panel size.
+--cap M: also the capped streamed step (include/tcar_quota.h) with at most M items of one category in a list, timed beside the uncapped
+one.  The categories are the synthetic fold's own table if it has one, else C = --cats random codes.  --cap_skew adds the catalog
+whose items all share ONE category at cap 1: one accepted item and one kill pass per fold, however wide the panel."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -21,6 +25,9 @@ ap.add_argument("--n_items", type=int, default=46033)
 ap.add_argument("--streamed", action="store_true")
 ap.add_argument("--panel", type=str, default="", help="comma-separated panel sizes (multiples of 128, <= 49152); empty: the default panel")
 ap.add_argument("--window", type=str, default="", help="comma-separated fractions of the catalog (its last items) that form every session's pool")
+ap.add_argument("--cap", type=str, default="", help="comma-separated caps: at most M items of one category in a list")
+ap.add_argument("--cats", type=int, default=300, help="number of category codes when the synthetic fold carries no category table")
+ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog whose items all share one category")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -54,6 +61,14 @@ fracs = [float(f) for f in a.window.split(",") if f]
 if fracs:
     eng.set_item_keys(np.arange(N, dtype=np.int32))
 windows = [(f, (N - int(round(f * N)), N)) for f in fracs]
+caps = [int(m) for m in a.cap.split(",") if m]
+cat = getattr(fold, "category", None)
+if cat is None or len(cat) != N:
+    cat = np.random.RandomState(7).randint(0, a.cats, N)
+cat = np.asarray(cat, dtype=np.int32)
+quotas = [("cap=%d, %d categories" % (m, len(np.unique(cat))), cat, m) for m in caps]
+if a.cap_skew:
+    quotas.append(("cap=1, one category", np.zeros(N, np.int32), 1))
 # same results?  (the panel GEMM may take another tile than the whole-catalog launch: the scores may differ in the last bits)
 r0, t0, c0 = [x.clone() for x in eng.eval_step(None, bt=res[0])]
 for P in panels:
@@ -70,4 +85,12 @@ for rnd in range(a.rounds):
             dw = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None, window=w))
             print("N=%d round %d eval_step_streamed panel=%d window=%g: %.3f ms = %.0f sessions/s, %.3f of the unwindowed step" % (
                 N, rnd, P or eng.default_panel(), f, dw * 1e3, B / dw, dw / dt))
+        table = None
+        for name, c, m in quotas:
+            if c is not table:
+                eng.set_categories(c)
+                table = c
+            dq = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None, max_per_category=m))
+            print("N=%d round %d eval_step_streamed panel=%d %s: %.3f ms = %.0f sessions/s, %.3f of the uncapped step" % (
+                N, rnd, P or eng.default_panel(), name, dq * 1e3, B / dq, dq / dt))
     sys.stdout.flush()
