@@ -35,7 +35,9 @@ HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_hip.h")       # the C ABI:
 SERVE_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_serve.h")  # streamed score-and-select, layered on HEADER (read by _bind() too)
 WINDOW_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_window.h")  # publish-time windows of the streamed selection, layered on SERVE_HEADER
 QUOTA_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_quota.h")  # per-category caps of the streamed selection, layered on WINDOW_HEADER
-HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER]
+SERVE_SHARD_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_serve_shard.h")  # state merge + the shard's fold of the catalog-sharded serving path, on QUOTA_HEADER
+HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER,
+           SERVE_SHARD_HEADER]
 _ID_MARK = b"TCAR_BUILD_ID="
 
 
@@ -193,7 +195,8 @@ def _bind() -> None:
     resolve) and (restype, argtypes) of every declared function.  Defines them as attributes of this module, once.  tcar_hip.h
     gives SYMBOLS / ABI_VERSION / the struct mirrors; tcar_serve.h, which builds on it, its own names: SERVE_SYMBOLS,
     SERVE_ABI_VERSION and the mirror Serve; tcar_window.h, which builds on that, WINDOW_SYMBOLS, WINDOW_ABI_VERSION and Window;
-    tcar_quota.h, on top of it, QUOTA_SYMBOLS, QUOTA_ABI_VERSION and Quota."""
+    tcar_quota.h, on top of it, QUOTA_SYMBOLS, QUOTA_ABI_VERSION and Quota; tcar_serve_shard.h, on top of that, SERVE_SHARD_SYMBOLS and
+    SERVE_SHARD_ABI_VERSION (it declares no struct)."""
     g = globals()
     if "SYMBOLS" in g:
         return
@@ -205,7 +208,10 @@ def _bind() -> None:
     window_classes, window_protos = _read_header(WINDOW_HEADER, window_const, window_structs)
     quota_const, quota_structs = dict(window_const), dict(window_structs)
     quota_classes, quota_protos = _read_header(QUOTA_HEADER, quota_const, quota_structs)
+    shard_const, shard_structs = dict(quota_const), dict(quota_structs)
+    shard_classes, shard_protos = _read_header(SERVE_SHARD_HEADER, shard_const, shard_structs)
     g.update(classes)
+    g.update(shard_classes)
     g.update(serve_classes)
     g.update(window_classes)
     g.update(quota_classes)
@@ -214,7 +220,9 @@ def _bind() -> None:
              SERVE_ABI_VERSION=serve_const["TCAR_SERVE_ABI_VERSION"], SERVE_SYMBOLS=list(serve_protos), _SERVE_PROTOTYPES=serve_protos,
              WINDOW_ABI_VERSION=window_const["TCAR_WINDOW_ABI_VERSION"], WINDOW_SYMBOLS=list(window_protos),
              _WINDOW_PROTOTYPES=window_protos,
-             QUOTA_ABI_VERSION=quota_const["TCAR_QUOTA_ABI_VERSION"], QUOTA_SYMBOLS=list(quota_protos), _QUOTA_PROTOTYPES=quota_protos)
+             QUOTA_ABI_VERSION=quota_const["TCAR_QUOTA_ABI_VERSION"], QUOTA_SYMBOLS=list(quota_protos), _QUOTA_PROTOTYPES=quota_protos,
+             SERVE_SHARD_ABI_VERSION=shard_const["TCAR_SERVE_SHARD_ABI_VERSION"], SERVE_SHARD_SYMBOLS=list(shard_protos),
+             _SERVE_SHARD_PROTOTYPES=shard_protos)
 
 
 def __getattr__(name: str):
@@ -262,11 +270,11 @@ def load() -> C.CDLL:
         raise TcarError("libtcar_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS + SERVE_SYMBOLS + WINDOW_SYMBOLS + QUOTA_SYMBOLS if not hasattr(lib, s)]
+    missing = [s for s in SYMBOLS + SERVE_SYMBOLS + WINDOW_SYMBOLS + QUOTA_SYMBOLS + SERVE_SHARD_SYMBOLS if not hasattr(lib, s)]
     if missing:
         raise TcarError("libtcar_hip.so lacks symbols: %s" % missing)
     for s, (restype, argtypes) in list(_PROTOTYPES.items()) + list(_SERVE_PROTOTYPES.items()) + list(_WINDOW_PROTOTYPES.items()) + \
-            list(_QUOTA_PROTOTYPES.items()):
+            list(_QUOTA_PROTOTYPES.items()) + list(_SERVE_SHARD_PROTOTYPES.items()):
         f = getattr(lib, s)
         f.restype, f.argtypes = restype, argtypes
     if lib.tcar_abi_version() != ABI_VERSION:
@@ -278,6 +286,9 @@ def load() -> C.CDLL:
         raise TcarError("libtcar_hip.so has window ABI %d, these bindings expect %d: rebuild" % (lib.tcar_window_abi_version(), WINDOW_ABI_VERSION))
     if lib.tcar_quota_abi_version() != QUOTA_ABI_VERSION:
         raise TcarError("libtcar_hip.so has quota ABI %d, these bindings expect %d: rebuild" % (lib.tcar_quota_abi_version(), QUOTA_ABI_VERSION))
+    if lib.tcar_serve_shard_abi_version() != SERVE_SHARD_ABI_VERSION:
+        raise TcarError("libtcar_hip.so has serve-shard ABI %d, these bindings expect %d: rebuild"
+                        % (lib.tcar_serve_shard_abi_version(), SERVE_SHARD_ABI_VERSION))
     # a binary built from other sources than the ones next to it is stale (the build is digest-gated, not mtime-gated)
     if have_sources():
         got, want = lib.tcar_build_id().decode(), source_build_id()

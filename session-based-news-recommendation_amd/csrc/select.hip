@@ -7,7 +7,7 @@
 // panel is the k best of the catalog whatever the partition and whatever order candidates arrive in LDS.
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
-#include "../../include/tcar_quota.h"
+#include "../../include/tcar_serve_shard.h"
 
 namespace {
 
@@ -453,6 +453,77 @@ __global__ __launch_bounds__(64) void select_finish_kernel(int k, const float* _
   }
 }
 
+// Merge of S select states into one (include/tcar_serve_shard.h).  ONE wave per session: lane s walks the list of shard s — every
+// input list is already in list order, so the merged list is an S-way merge.  A round takes the wave-wide best of the S heads (shuffles
+// only: no LDS, no barrier) and its owner moves on; Q (include/tcar_quota.h): a head whose category already holds `cap` entries of the
+// merged list is rejected and only moves its owner on, which is the capped walk over the S k entries.  Every round advances one cursor,
+// so a merge ends after at most S k rounds (k where nothing is rejected).  A lane keeps its head AND the entry behind it in registers:
+// the load that refills them is in flight during the next round's arg-max.  Lane j keeps entry j of the merged list (and, Q, its
+// category: "how many of this category are taken" is one ballot), written once at the end.  Scores are copied.
+// Statistics: counts add; (max, sum exp) pairs combine in ascending shard order — a fixed rounding order — and a pair with max = -inf
+// (a state that never folded a pooled column) is left out, so no exp(-inf + inf) is ever formed.
+template <bool Q>
+__global__ __launch_bounds__(64) void select_merge_kernel(int k, int S, const float* __restrict__ states, long stride,
+                                                          float* __restrict__ out, const int32_t* __restrict__ cat, int cap) {
+  const int b = blockIdx.x, lane = threadIdx.x, rw = sel_row_words(k);
+  const float ninf = -INFINITY;
+  const bool live = lane < S;
+  const float* st = states + (live ? (long)lane * stride : 0L) + (long)b * rw;       // (lanes >= S point at shard 0 and read nothing)
+  const int* sti = reinterpret_cast<const int*>(st);
+  int cnt = live ? sti[2 * k] : 0;
+  const float ms = live ? st[2 * k + 1] : ninf;
+  const float ss = live ? st[2 * k + 2] : 0.f;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+  const float M = wave_max(ms);
+  const float part = ms > ninf ? ss * expf(ms - M) : 0.f;
+  float sum = 0.f;
+  for (int s = 0; s < S; ++s) sum += __shfl(part, s);
+  // entry j of this lane's list; (-inf, -1): the list has ended
+  auto entry = [&](int j, float& v, int& i) __attribute__((always_inline)) {
+    v = ninf; i = -1;
+    if (live && j < k) {
+      i = sti[k + j];
+      if (i >= 0) v = st[j];
+    }
+  };
+  float hv, nv, ov = ninf;
+  int hi, ni, oi = -1, cur = 0, taken = 0, mycat = 0;
+  entry(0, hv, hi);
+  entry(1, nv, ni);
+  while (taken < k) {
+    // wave-wide arg-max of the heads in list order; equal keys (the same item in two lists) go to the lower lane
+    float bv = hv;
+    int bi = hi, bl = lane;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float xv = __shfl_xor(bv, o);
+      const int xi = __shfl_xor(bi, o), xl = __shfl_xor(bl, o);
+      if (key_gt(xv, xi, bv, bi) || (xv == bv && xi == bi && xl < bl)) { bv = xv; bi = xi; bl = xl; }
+    }
+    if (bi < 0) break;                      // every list has ended
+    bool ok = true;
+    int fc = 0;
+    if constexpr (Q) {
+      fc = cat[__builtin_amdgcn_readfirstlane(bi)];
+      ok = __popcll(__ballot(lane < taken && mycat == fc)) < cap;
+    }
+    if (ok) {
+      if (lane == taken) { ov = bv; oi = bi; mycat = fc; }
+      ++taken;
+    }
+    if (lane == bl) {
+      hv = nv; hi = ni;
+      ++cur;
+      entry(cur + 1, nv, ni);
+    }
+  }
+  float* o = out + (long)b * rw;
+  int* oint = reinterpret_cast<int*>(o);
+  if (lane < k) { o[lane] = ov; oint[k + lane] = oi; }
+  if (lane == 0) { oint[2 * k] = cnt; o[2 * k + 1] = M; o[2 * k + 2] = sum; o[2 * k + 3] = 0.f; }
+}
+
 // lab_score[b] = attout[b] . E[label[b]] over K columns, from the operands the panel GEMM contracts: one wave per session
 __global__ __launch_bounds__(64) void label_score_f32_kernel(int N, int K, const float* __restrict__ att, long ld_att,
                                                              const float* __restrict__ E, long ldE, const int32_t* __restrict__ label,
@@ -469,9 +540,17 @@ __global__ __launch_bounds__(64) void label_score_f32_kernel(int N, int K, const
 __global__ __launch_bounds__(64) void label_score_bf16_kernel(int N, int K, const __bf16* __restrict__ a_hi, const __bf16* __restrict__ a_lo,
                                                               int a_in32, const __bf16* __restrict__ e_hi,
                                                               const __bf16* __restrict__ e_lo, int e_in32, int nsplit,
-                                                              const int32_t* __restrict__ label, float* __restrict__ out) {
+                                                              const int32_t* __restrict__ label, float* __restrict__ out, int lab0,
+                                                              int owned_only) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  const int lab = clampi(label[b], 0, N - 1);
+  // owned_only (a catalog shard whose planes hold the rows [lab0, lab0 + N)): a label outside them — another shard's, or the -1 of a
+  // padding session — reads no row and scores 0
+  int lab = label[b] - lab0;
+  if (owned_only && (lab < 0 || lab >= N)) {
+    if (lane == 0) out[b] = 0.f;
+    return;
+  }
+  lab = clampi(lab, 0, N - 1);
   float s = 0.f;
   for (int c = lane; c < K; c += 64) {
     const long oa = kb32_off(b, c, a_in32), oe = kb32_off(lab, c, e_in32);
@@ -558,18 +637,49 @@ extern "C" int tcar_select_finish(int B, int k, const void* state, const float* 
   return TCAR_OK;
 }
 
+extern "C" int tcar_serve_shard_abi_version(void) { return TCAR_SERVE_SHARD_ABI_VERSION; }
+
+extern "C" int tcar_select_merge(int B, int k, int S, const void* states, int64_t stride_words, void* out, const int32_t* cat, int cap,
+                                 void* stream) {
+  if (cat ? cap < 1 : cap != 0) return TCAR_E_ARG;
+  if (B < 0 || k < 1 || k > SEL_MAX_K || S < 1 || S > 64) return TCAR_E_ARG;
+  const int64_t rows = (int64_t)B * sel_row_words(k);
+  if (S > 1 && stride_words < rows) return TCAR_E_ARG;
+  if (B == 0) return TCAR_OK;
+  if (!states || !out || ((uintptr_t)states & 3) || ((uintptr_t)out & 3)) return TCAR_E_ARG;
+  const uintptr_t in0 = (uintptr_t)states, in1 = in0 + (uintptr_t)(((int64_t)(S - 1) * stride_words + rows) * 4);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * 4);
+  if (o0 < in1 && in0 < o1) return TCAR_E_ARG;            // out overlaps the inputs
+  hipStream_t s = (hipStream_t)stream;
+  if (cat && cap < k)
+    TCAR_LAUNCH((select_merge_kernel<true>), dim3(B), dim3(64), 0, s, k, S, (const float*)states, (long)stride_words, (float*)out, cat, cap);
+  else
+    TCAR_LAUNCH((select_merge_kernel<false>), dim3(B), dim3(64), 0, s, k, S, (const float*)states, (long)stride_words, (float*)out, cat,
+                cap);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+
 // planes: hi / lo KB32 of attout [ceil128(B), a_inner] and of E [ceil128(N), e_inner] (nsplit 1: hi only); NULL a_hi: fp32 operands
 int tcar_label_scores(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
                       const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
                       const int32_t* label, float* out, void* stream) {
+  return tcar_label_scores_owned(B, N, K, att, ld_att, E, ldE, a_hi, a_lo, a_inner, e_hi, e_lo, e_inner, nsplit, label, out, 0, 0, stream);
+}
+
+// owned_only != 0 (bf16 planes only): the e planes hold the catalog rows [lab0, lab0 + N) of a shard; out[b] = 0 for a label outside
+int tcar_label_scores_owned(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
+                            const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
+                            const int32_t* label, float* out, int lab0, int owned_only, void* stream) {
   if (B <= 0) return TCAR_OK;
+  if (owned_only && !a_hi) return TCAR_E_ARG;
   if (N <= 0 || K <= 0 || !label || !out) return TCAR_E_ARG;
   if (a_hi) {
     if (!e_hi || (nsplit == 3 && (!a_lo || !e_lo)) || (nsplit != 1 && nsplit != 3) || (a_inner & 31) || (e_inner & 31) ||
         a_inner < K || e_inner < K)
       return TCAR_E_ARG;
     TCAR_LAUNCH(label_score_bf16_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, N, K, (const __bf16*)a_hi, (const __bf16*)a_lo,
-                (int)(a_inner >> 5), (const __bf16*)e_hi, (const __bf16*)e_lo, (int)(e_inner >> 5), nsplit, label, out);
+                (int)(a_inner >> 5), (const __bf16*)e_hi, (const __bf16*)e_lo, (int)(e_inner >> 5), nsplit, label, out, lab0, owned_only);
   } else {
     if (!att || !E || (K & 3) || (ld_att & 3) || (ldE & 3) || !tcar_aligned16(att) || !tcar_aligned16(E)) return TCAR_E_ARG;
     TCAR_LAUNCH(label_score_f32_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, N, K, att, (long)ld_att, E, (long)ldE, label, out);

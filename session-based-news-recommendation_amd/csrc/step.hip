@@ -3,7 +3,7 @@
 // aux stream joined by events — no host synchronisation, no allocation.  tcar_train_step == sess.run([loss, global_step, train_op]) (model_combine.py:231);
 // tcar_eval_step == sess.run([softmax_input, cross_loss]) + util.cau_metrics + top-k (model_combine.py:283,296,301).
 #include "tcar_common.h"
-#include "../../include/tcar_quota.h"
+#include "../../include/tcar_serve_shard.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1249,6 +1249,35 @@ extern "C" int tcar_eval_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
   return tcar_softmax_ce(bt->B, g.N, c->logits, g.Npad, bt->label, c->ce, stream);
 }
 
+namespace {
+// The fold of one evaluation / recommendation step: reset the state, then the catalog rows the context's candidate side covers in
+// column panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel_quota while the panel is
+// cache-warm.  A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row
+// blocks).  a16h / a16l: the planes of the B session rows (split-bf16 modes).  id0: the catalog id of the context's first candidate
+// row — 0, or the first row of a shard (tcar_shard_serve_fold), whose folds then carry GLOBAL item ids.
+int serve_fold(const tcar_ctx_t* c, int B, const void* a16h, const void* a16l, int id0, const int32_t* label, const float* lab,
+               const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  const Geo g(c->d);
+  const int k = s->k;
+  RET(tcar_select_reset(B, k, s->state, stream));
+  for (int n0 = 0; n0 < g.N; n0 += s->panel) {
+    const int n = g.N - n0 < s->panel ? g.N - n0 : s->panel;
+    if (c->scoring) {
+      TcarOpt ol = opt_of(c);
+      const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
+      RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, a16h, a16l, g.ek, B, (const char*)c->e16h + off,
+                                c->e16l ? (const char*)c->e16l + off : nullptr, g.ek, g.Npad - n0, s->panel_buf, s->panel, nullptr, 0, 0,
+                                nullptr, 0, c->scoring, 1, stream, &ol));
+    } else {
+      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, s->panel_buf, s->panel, nullptr, 0, 0, 1, stream));
+    }
+    RET(tcar_select_panel_quota(B, id0 + n0, n, s->panel_buf, s->panel, k, label, lab, s->excl, s->X, s->state, stream,
+                                w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, q ? q->cat : nullptr, q ? q->cap : 0));
+  }
+  return TCAR_OK;
+}
+}  // namespace
+
 // Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, then the catalog in column
 // panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel while the panel is cache-warm.
 // A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row blocks).
@@ -1275,21 +1304,7 @@ extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt
   if (lab)
     RET(tcar_label_scores(B, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l,
                           g.ek, c->scoring, bt->label, s->lab_score, stream));
-  RET(tcar_select_reset(B, k, s->state, stream));
-  for (int n0 = 0; n0 < g.N; n0 += s->panel) {
-    const int n = g.N - n0 < s->panel ? g.N - n0 : s->panel;
-    if (c->scoring) {
-      TcarOpt ol = opt_of(c);
-      const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
-      RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, c->a16h, c->a16l, g.ek, B, (const char*)c->e16h + off,
-                                c->e16l ? (const char*)c->e16l + off : nullptr, g.ek, g.Npad - n0, s->panel_buf, s->panel, nullptr, 0, 0,
-                                nullptr, 0, c->scoring, 1, stream, &ol));
-    } else {
-      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, s->panel_buf, s->panel, nullptr, 0, 0, 1, stream));
-    }
-    RET(tcar_select_panel_quota(B, n0, n, s->panel_buf, s->panel, k, bt->label, lab, s->excl, s->X, s->state, stream,
-                                w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, q ? q->cat : nullptr, q ? q->cap : 0));
-  }
+  RET(serve_fold(c, B, c->a16h, c->a16l, 0, bt->label, lab, s, w, q, stream));
   return tcar_select_finish(B, k, s->state, lab, s->topk, s->score, lab ? s->rank : nullptr, lab ? s->ce : nullptr, stream);
 }
 
@@ -1445,6 +1460,51 @@ extern "C" int tcar_shard_score(const tcar_ctx_t* c, const tcar_shard_t* s, int 
   RET(tcar_gemm_bf16(1, Bq, nl, g.ek, s->a16h, s->a16l, g.ek, Bq, c->e16h, c->e16l, g.ek, nlpad, s->logits, nlpad, nullptr, 0, 0,
                      c->scoring, 1, stream));
   return tcar_softmax_stats(Bq, nl, s->logits, nlpad, s->lab_all, s->n0, s->stats, stream);
+}
+
+// ---- streamed score-and-select on a catalog shard (include/tcar_serve_shard.h; sharded.py: ShardExchange.serve)
+namespace {
+int check_shard_serve(const tcar_ctx_t* sc, const tcar_shard_t* sh) {
+  if (!sc || !sh || !sc->scoring || sh->world <= 0 || sh->cap <= 0 || sh->n_loc <= 0 || sh->n0 < 0) return TCAR_E_ARG;
+  if (sc->d.n_items != sh->n_loc || (int64_t)sh->n0 + sh->n_loc > 0x7fffffffL) return TCAR_E_ARG;       // sc is the SHARD's context
+  if (!sh->att_all || !sh->a16h || !sc->e16h || (sc->scoring == 3 && (!sh->a16l || !sc->e16l))) return TCAR_E_ARG;
+  const Geo g(sc->d);
+  if (sh->ld_att && (sh->ld_att < g.ek || (sh->ld_att & 3))) return TCAR_E_ARG;
+  return TCAR_OK;
+}
+}  // namespace
+
+extern "C" int tcar_shard_serve_begin(const tcar_ctx_t* sc, const tcar_shard_t* sh, int refresh_time, const int32_t* label,
+                                      float* lab_part, void* stream) {
+  RET(check_shard_serve(sc, sh));
+  if (label && !lab_part) return TCAR_E_ARG;
+  if (refresh_time && !sc->mwdhm) return TCAR_E_ARG;
+  const Geo g(sc->d);
+  const int Bq = sh->world * sh->cap;
+  if (refresh_time) {        // the candidate-time columns of the shard's planes, on this stream: the panel GEMM contracts all ek columns
+    const float* tt[5];
+    time_tables(sc, tt);
+    RET(tcar_cand_time_fwd_bf16(&sc->d, tt, sc->mwdhm, nullptr, sc->e16h, sc->e16l, stream));
+  }
+  RET(tcar_split_bf16(sh->att_all, sh->ld_att ? sh->ld_att : g.ek, Bq, g.ek, sh->a16h, sh->a16l, g.ek, nullptr, nullptr, 0, 0, 0, stream));
+  if (label)
+    RET(tcar_label_scores_owned(Bq, sh->n_loc, g.ek, nullptr, 0, nullptr, 0, sh->a16h, sh->a16l, g.ek, sc->e16h, sc->e16l, g.ek,
+                                sc->scoring, label, lab_part, sh->n0, 1, stream));
+  return TCAR_OK;
+}
+
+extern "C" int tcar_shard_serve_fold(const tcar_ctx_t* sc, const tcar_shard_t* sh, const int32_t* label, const float* lab_score,
+                                     const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  if (!s) return TCAR_E_ARG;
+  if (w && (!w->key || !w->lo || !w->hi)) return TCAR_E_ARG;
+  if (q && (!q->cat || q->cap < 1)) return TCAR_E_ARG;
+  if (s->k < 1 || s->k > 64 || s->panel <= 0 || (s->panel & 127) || s->panel > 512 * 4 * 24) return TCAR_E_ARG;
+  if (!s->panel_buf || !s->state || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0)) return TCAR_E_ARG;
+  if ((label != nullptr) != (lab_score != nullptr)) return TCAR_E_ARG;
+  RET(check_shard_serve(sc, sh));
+  const int Bq = sh->world * sh->cap;
+  if (s->state_bytes < tcar_select_state_bytes(Bq, s->k)) return TCAR_E_ARG;
+  return serve_fold(sc, Bq, sh->a16h, sh->a16l, sh->n0, label, lab_score, s, w, q, stream);
 }
 
 extern "C" int tcar_shard_backward(const tcar_ctx_t* c, const tcar_shard_t* s, const float* stats_all, void* stream) {

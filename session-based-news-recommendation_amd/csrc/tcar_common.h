@@ -246,6 +246,9 @@ int tcar_softmax_ce_bf16_o(int B, int N, float* logits, int64_t ld, const int32_
 int tcar_label_scores(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
                       const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
                       const int32_t* label, float* out, void* stream);
+int tcar_label_scores_owned(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
+                            const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
+                            const int32_t* label, float* out, int lab0, int owned_only, void* stream);
 
 // 16-byte write-through store (sc1): the bytes bypass the write-back state of this XCD's L2, so a consumer behind a completion
 // flag needs no release fence / L2 write-back from the producer (cdna_hip_programming.md Guideline 16, R1).  The compiler does not

@@ -882,8 +882,8 @@ class TcarEngine(OpLevelStep):
             raise ValueError("item keys must fit int32")
         self._item_keys = torch.from_numpy(np.array(k, dtype=np.int32, order="C")).to(self.dev)      # (np.array: a copy the caller cannot write)
 
-    def _window(self, window, B: int) -> Window:
-        """(lo, hi), each a scalar or an int array [B] -> the descriptor of a windowed call; bounds beyond int32 are clipped to it"""
+    def _window_bounds(self, window, B: int):
+        """(lo, hi), each a scalar or an int array [B] -> two int32 host arrays [B]; bounds beyond int32 are clipped to it"""
         if getattr(self, "_item_keys", None) is None:
             raise ValueError("a window compares item keys: call set_item_keys(keys) first")
         try:
@@ -892,6 +892,11 @@ class TcarEngine(OpLevelStep):
                                            dtype=np.int32) for x in (lo, hi))
         except (TypeError, ValueError):
             raise ValueError("window = (lo, hi), each a scalar or an int array of length B = %d" % B) from None
+        return lo, hi
+
+    def _window(self, window, B: int) -> Window:
+        """(lo, hi) -> the descriptor of a windowed call"""
+        lo, hi = self._window_bounds(window, B)
         # lo and hi are the two rows of ONE workspace entry, so that they go up in one copy (measured: the host-to-device copies are
         # most of what a window costs a small catalog's step, docs/EXPERIMENTS.md)
         self.ws.ensure([Spec("win_lohi", (2, self.work_B), I32)])
@@ -984,15 +989,8 @@ class TcarEngine(OpLevelStep):
         rank, topk, ce, self.last_scores = self._serve(bt, k, panel, None, True, window, max_per_category)
         return rank, topk, ce
 
-    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,
-                  max_per_category: Optional[int] = None):
-        """The k best next items of every session: (topk [B,k] int32, scores [B,k] f32), best first (score, then item id,
-        descending); -1 where fewer than k items remain.  `batch` needs no "label" and no "neg".  exclude_seen drops the items of
-        the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot).  window = (lo, hi), scalars or
-        int arrays [B]: only items with lo[b] <= key < hi[b] (set_item_keys) are candidates of session b; exclusions apply on top.
-        max_per_category = m >= 1: at most m items of one category of set_categories() in a list (include/tcar_quota.h); excluded
-        and out-of-window items consume no quota."""
-        self.flush()
+    def _recommend_inputs(self, batch, exclude_seen: bool, exclude):
+        """the uploaded sessions of a recommend() call and their exclusion lists [B, X] on the device (None: none)"""
         if "label" not in batch:
             batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
         if "neg" in batch:
@@ -1005,6 +1003,17 @@ class TcarEngine(OpLevelStep):
             ex = np.ascontiguousarray(np.asarray(exclude, dtype=np.int32).reshape(bt.B, -1))
             if ex.shape[1]:
                 parts.append(torch.from_numpy(ex).to(self.dev))
-        excl = torch.cat(parts, dim=1).contiguous() if parts else None
+        return bt, (torch.cat(parts, dim=1).contiguous() if parts else None)
+
+    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,
+                  max_per_category: Optional[int] = None):
+        """The k best next items of every session: (topk [B,k] int32, scores [B,k] f32), best first (score, then item id,
+        descending); -1 where fewer than k items remain.  `batch` needs no "label" and no "neg".  exclude_seen drops the items of
+        the session itself (seq - 1); `exclude` [B, X] names further 0-based ids (-1 = empty slot).  window = (lo, hi), scalars or
+        int arrays [B]: only items with lo[b] <= key < hi[b] (set_item_keys) are candidates of session b; exclusions apply on top.
+        max_per_category = m >= 1: at most m items of one category of set_categories() in a list (include/tcar_quota.h); excluded
+        and out-of-window items consume no quota."""
+        self.flush()
+        bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
         _, topk, _, scores = self._serve(bt, k, panel, excl, False, window, max_per_category)
         return topk, scores

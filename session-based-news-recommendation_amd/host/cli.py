@@ -78,6 +78,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="M > 0: evaluation lists hold at most M items of one category (the walk of include/tcar_quota.h); ILD, unexp and "
                          "coverage describe the capped lists, and one more line gives their accuracy.  Needs --eval_panel; not with "
                          "--dp_mode sharded; combines with --fresh_hours.  0: off")
+    ap.add_argument("--shard_eval_panel", default=0, type=int,
+                    help="P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
+                         "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= 49152).  "
+                         "0: the materialised evaluation of the catalog-sharded engine")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -116,6 +120,17 @@ def check_cat_cap(cat_cap, eval_panel, dp_mode):
         raise ValueError("--cat_cap caps the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
     if not eval_panel:
         raise ValueError("--cat_cap needs --eval_panel P: only the streamed evaluation takes a per-category cap")
+
+
+def check_shard_eval_panel(shard_eval_panel, dp_mode):
+    """--shard_eval_panel is the streamed evaluation of the catalog-sharded engine (include/tcar_serve_shard.h)"""
+    if not shard_eval_panel:
+        return
+    if shard_eval_panel < 0 or shard_eval_panel % 128 or shard_eval_panel > 49152:
+        raise ValueError("--shard_eval_panel must be a multiple of 128 in [128, 49152] (0: off)")
+    if dp_mode != "sharded":
+        raise ValueError("--shard_eval_panel streams the shards of the catalog-sharded engine: it needs --dp_mode sharded "
+                         "(one engine with the whole catalog: --eval_panel)")
 
 
 def load_datas(args):
@@ -176,6 +191,7 @@ def main(argv=None):
     check_eval_panel(args.eval_panel, args.dp_mode)
     check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
     check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
+    check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -146,6 +146,9 @@ class Seq2SeqAttNN():
         self.cat_cap = int(args.get('cat_cap', 0) or 0)             # > 0: test() caps the items of one category in every list
         from .cli import check_cat_cap
         check_cat_cap(self.cat_cap, self.eval_panel, args.get('dp_mode', 'replica'))
+        self.shard_eval_panel = int(args.get('shard_eval_panel', 0) or 0)     # > 0 (dp_mode sharded): test() streams every rank's shard
+        from .cli import check_shard_eval_panel
+        check_shard_eval_panel(self.shard_eval_panel, args.get('dp_mode', 'replica'))
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -170,6 +173,9 @@ class Seq2SeqAttNN():
             if args.get('dp_mode', 'replica') == 'sharded':
                 from ..sharded import ShardedEngine
                 engine_cls = ShardedEngine
+        elif self.shard_eval_panel:             # one process, no group: the catalog-sharded engine with ONE shard (no collective runs)
+            from ..sharded import ShardedEngine
+            engine_cls = ShardedEngine
         self.engine = engine_cls(params, content, self.publish_time_MWDHM, lr=args['lr'], max_grad=args.get('max_grad'),
                                  device=args.get('device', 'cuda:0'), scoring=args.get('scoring', 'bf16x3-mixed'), **kw)
         self._cat = None
@@ -387,10 +393,19 @@ class Seq2SeqAttNN():
         panel = int(args.get('eval_panel', self.eval_panel) or 0)
         if panel and args.get('dp_mode', 'replica') == 'sharded':
             raise ValueError("eval_panel cannot be combined with dp_mode sharded")
+        spanel = int(args.get('shard_eval_panel', self.shard_eval_panel) or 0)      # > 0: the shards stream, the ranks' states merge
+        if spanel:
+            from .cli import check_shard_eval_panel
+            check_shard_eval_panel(spanel, args.get('dp_mode', 'replica'))
+            if not hasattr(eng, "xch"):
+                raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         for feed in prefetch_batches(sampler):
             batch += 1
+            T = feed["seq"].shape[1]
             feed, _cap = self._shard(feed)           # data parallel: every rank scores its shard of the batch
             if feed is None:
+                if spanel:       # a COLLECTIVE: a rank without sessions still joins every exchange (sharded.ShardExchange.serve)
+                    eng.eval_step_streamed(None, k=20, panel=spanel, cap=_cap, T=T)
                 continue
             bt = eng.upload(feed)
             if fresh:            # streamed, every session inside its pool (include/tcar_window.h)
@@ -402,6 +417,8 @@ class Seq2SeqAttNN():
                 rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, max_per_category=cap)
             elif panel:          # streamed: no [B, N] score matrix (engine.eval_step_streamed)
                 rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel)
+            elif spanel:         # streamed over the shards (sharded.ShardedEngine.eval_step_streamed)
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=spanel, cap=_cap)
             else:
                 rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
             ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)
@@ -463,7 +480,9 @@ class Seq2SeqAttNN():
         gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
         has already read are left out (engine.TcarEngine.recommend has the options).  window = (lo, hi), scalars or arrays [B], in
         minutes since the earliest publish time (`minute_of(datetime)`): only items published in [lo, hi) are candidates.
-        max_per_category = m >= 1: at most m items of one category (the fold's category table) in a list."""
+        max_per_category = m >= 1: at most m items of one category (the fold's category table) in a list.
+        With the catalog-sharded engine (dp_mode sharded) this is a COLLECTIVE: every rank calls it with its own sessions — None
+        where it has none, with cap= and T= (sharded.ShardedEngine.recommend)."""
         if window is not None:
             self._item_keys()
         if max_per_category is not None:

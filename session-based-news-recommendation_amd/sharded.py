@@ -27,7 +27,20 @@ Six collectives per step (eleven before the exchange buffers were packed): at ~2
 not the bytes, are what a step waits for at this catalog size.
 
 Sequenced from C++ between the exchanges (csrc/step.hip: tcar_step_session_forward / tcar_shard_score / tcar_shard_backward /
-tcar_shard_finish / tcar_step_session_backward), the collectives in between from here; split-bf16 scoring modes only.  Evaluation scores the local sessions against the whole catalog on the fp32 GEMM.
+tcar_shard_finish / tcar_step_session_backward), the collectives in between from here; split-bf16 scoring modes only.
+
+Evaluation: `eval_step` scores the local sessions against the whole catalog on the fp32 GEMM ([B, Npad] logits on every rank).
+`eval_step_streamed` / `recommend` (ShardExchange.serve, include/tcar_serve_shard.h) use the shard instead:
+
+  session forward (local B sessions)                                                            -> attout [B, ek]
+  all-gather   ONE packed row per session: [attout | label | - | window lo | window hi | exclusion ids]   -> [W*cap, ld]
+  label scores attout_all . E_shard[label] where this shard owns the label, 0 elsewhere (evaluation only)
+  all-gather   the shards' label scores; every session takes its label owner's entry             (1 float per session and shard)
+  fold         the shard's split-bf16 planes in column panels, global item ids -> one select state per gathered session
+  all-gather   the select states [W*cap, 2k + 4]; rank r merges the W states of its own sessions (tcar_select_merge), finishes
+
+The merge is exact: top-k, scores and rank are the bits of the unsharded streamed call, the cross entropy differs by the rounding of a
+sum whose order is fixed.  No [., Npad] buffer exists on any rank.
 """
 from __future__ import annotations
 
@@ -40,7 +53,7 @@ import torch
 from . import _lib, dp
 from ._lib import Batch, Dims, check
 from .engine import Switches, TcarEngine, _ru
-from .workspace import F32, I32, ScoreForm, Spec, scoring_specs
+from .workspace import BF16, F32, I32, ScoreForm, Spec, scoring_specs
 
 
 def shard_rows(n_items: int, world: int):
@@ -90,6 +103,29 @@ class ShardExchange(dp.Collectives):
             out = pieces.update()
             if out is not None:
                 self.share_rows(*out)
+
+    def serve(self, pieces, cap: int, labelled: bool):
+        """one evaluation (labelled) or recommendation step of the streamed score-and-select (include/tcar_serve_shard.h): every
+        rank folds ITS shard of the catalog for the sessions of EVERY rank, and the per-shard select states merge exactly.  Every
+        rank, also one without sessions, issues the same collectives in the same order with buffers of the same shape:
+
+          1 all-gather  packed session rows [cap, ld]: [attout | label | - | window lo | window hi | X exclusion ids | pad], ints as bits
+          2 all-gather  the shards' label scores [W * cap] (labelled only; each session takes its label OWNER's entry)
+          3 all-gather  the shards' select states [W * cap, 2k + 4]; rank r merges rows [r cap, (r + 1) cap) of the W states
+
+        `pieces` supplies the local compute:
+             begin() -> rows [cap, ld]                     prepare(rows_all [W*cap, ld]) -> label-score parts [W*cap] (or None)
+             label_scores(parts_all [W, W*cap])            fold() -> state [W*cap, 2k+4]
+             finish(states [W, W*cap, 2k+4]) -> the result of the local sessions (returned)"""
+        self.order = []
+        self.wait_rows()
+        head = pieces.begin()
+        head_all = self.all_gather(head, "serve_rows").view(self.world * cap, -1)
+        parts = pieces.prepare(head_all)
+        if labelled:
+            pieces.label_scores(self.all_gather(parts, "serve_label_scores"))
+        state = pieces.fold()
+        return pieces.finish(self.all_gather(state, "serve_states"))
 
 
 class _Pieces:
@@ -180,6 +216,104 @@ class _Pieces:
         return self.eng._update_local()
 
 
+class _ServePieces:
+    """The local compute between the exchanges of ShardExchange.serve, bound to the C entry points of include/tcar_serve_shard.h.  ONE
+    object per engine, re-armed per call.  Each piece can be called on its own (tests play the collectives by hand)."""
+
+    def __init__(self, eng):
+        self.eng = eng
+
+    def arm(self, bt, cap, k, panel, labelled, meta, X, windowed, quota):
+        e = self.eng
+        self.bt, self.cap, self.k, self.panel, self.labelled = bt, cap, k, panel, labelled
+        self.meta, self.X, self.K, self.windowed, self.quota = meta, X, 2 + X, windowed, quota
+        self.B = bt.B if bt is not None else 0
+        self.Bq = e.world * cap
+        self.rw = 2 * k + 4                       # words of a state row (tcar_select_state_bytes)
+        self.ld = _ru(e.geo.ek + 2 + self.K, 4)
+        self.st = e._stream()
+        self.refresh = int(e._time_dirty)
+        sh = _lib.Shard()
+        sh.world, sh.cap, sh.n0, sh.n_loc = e.world, cap, e.n0, e.nl
+        sh.a16h, sh.a16l = e.sv_a16h.data_ptr(), e.sv_a16l.data_ptr()
+        self.sh, self.sctx = sh, e._serve_ctx()
+
+    # session forward of the local sessions, ONE packed row per session: [attout (ek) | label | unused | lo | hi | X exclusion ids |
+    # pad] in the slots of the training step's rows (tcar_shard_pack_head: label, coefficient, "negatives"); rows past the local
+    # batch are padding sessions: label -1, an empty window, no exclusions
+    def begin(self):
+        e, bt, B = self.eng, self.bt, self.B
+        head = e.sv_head[:self.cap]
+        if bt is not None:
+            check(e.lib.tcar_step_session_forward(C.byref(e._ctx()), C.byref(bt), self.st), "tcar_step_session_forward")
+        check(e.lib.tcar_shard_pack_head(B, self.cap, e.geo.ek, self.K, self.K, e._p(e.attout) if B else None,
+                                         C.c_void_p(bt.label) if B else None, None, e._p(self.meta) if B else None, e._p(head),
+                                         self.ld, self.st), "tcar_shard_pack_head")
+        return head
+
+    # the gathered rows: their ints back into arrays, the attout planes, the label scores this shard owns (0 elsewhere)
+    def prepare(self, head_all):
+        e, Bq = self.eng, self.Bq
+        self._head_all = head_all
+        self.sh.att_all, self.sh.ld_att = head_all.data_ptr(), self.ld
+        check(e.lib.tcar_shard_unpack_head(Bq, e.geo.ek, self.K, e._p(head_all), self.ld, e._p(e.sv_lab), e._p(e.sv_coef),
+                                           e._p(e.sv_meta), self.st), "tcar_shard_unpack_head")
+        if self.windowed:
+            e.sv_lohi[:, :Bq].copy_(e.sv_meta[:Bq, :2].t())
+        if self.X:
+            e.sv_excl[:Bq].copy_(e.sv_meta[:Bq, 2:])
+        lab = self.labelled
+        check(e.lib.tcar_shard_serve_begin(C.byref(self.sctx), C.byref(self.sh), self.refresh, e._p(e.sv_lab) if lab else None,
+                                           e._p(e.sv_lab_part) if lab else None, self.st), "tcar_shard_serve_begin")
+        if self.refresh:
+            e._time_dirty = False
+        return e.sv_lab_part[:Bq] if lab else None
+
+    # every session takes the label score of its label's owner (label // shard rows), on the device
+    def label_scores(self, parts_all):
+        e, Bq = self.eng, self.Bq
+        if parts_all.shape[0] == 1:
+            e.sv_lab_score[:Bq].copy_(parts_all[0])
+            return
+        owner = torch.div(e.sv_lab[:Bq].clamp(min=0), e.S, rounding_mode="floor").clamp(max=parts_all.shape[0] - 1).long()
+        e.sv_lab_score[:Bq].copy_(parts_all.gather(0, owner[None, :])[0])
+
+    # the shard's rows, panel by panel, into one state per session of every rank
+    def fold(self):
+        e, Bq, lab = self.eng, self.Bq, self.labelled
+        s = _lib.Serve()
+        s.k, s.panel = self.k, self.panel
+        s.panel_buf, s.state, s.state_bytes = e.sv_panel.data_ptr(), e.sv_state.data_ptr(), e.sv_state.numel() * 4
+        if self.X:
+            s.excl, s.X = e.sv_excl.data_ptr(), self.X
+        w = None
+        if self.windowed:
+            w = _lib.Window()
+            w.key, w.lo, w.hi = e._item_keys.data_ptr(), e.sv_lohi[0].data_ptr(), e.sv_lohi[1].data_ptr()
+        q = self.quota
+        check(e.lib.tcar_shard_serve_fold(C.byref(self.sctx), C.byref(self.sh), e._p(e.sv_lab) if lab else None,
+                                          e._p(e.sv_lab_score) if lab else None, C.byref(s), C.byref(w) if w is not None else None,
+                                          C.byref(q) if q is not None else None, self.st), "tcar_shard_serve_fold")
+        return e.sv_state[:Bq]
+
+    # the W states of the local sessions' rows -> one (tcar_select_merge), finished
+    def finish(self, states):
+        e, cap, k, B, lab = self.eng, self.cap, self.k, self.B, self.labelled
+        W = states.shape[0]
+        if not states.is_contiguous():
+            states = states.contiguous()
+        self._states = states
+        r0 = e.dp_rank * cap
+        q = self.quota
+        check(e.lib.tcar_select_merge(cap, k, W, e._p(states, r0 * self.rw), self.Bq * self.rw, e._p(e.sv_merged),
+                                      C.c_void_p(q.cat) if q is not None else None, q.cap if q is not None else 0, self.st),
+              "tcar_select_merge")
+        ls = e._p(e.sv_lab_score, r0) if lab else None
+        check(e.lib.tcar_select_finish(cap, k, e._p(e.sv_merged), ls, e._p(e.sel_topk), e._p(e.sel_score), e._p(e.sel_rank) if lab else None,
+                                       e._p(e.sel_ce) if lab else None, self.st), "tcar_select_finish")
+        return e.sel_rank[:B], e.sel_topk[:B], e.sel_ce[:B], e.sel_score[:B]
+
+
 class ShardedEngine(TcarEngine):
     def __init__(self, params, content_emb, mwdhm, lr=1e-3, max_grad=150.0, neg_weight=0.01, device="cuda:0", group=None,
                  scoring="bf16x3", world: Optional[int] = None, rank: Optional[int] = None,
@@ -237,6 +371,8 @@ class ShardedEngine(TcarEngine):
                 "item_rows_allgather_bytes": 4 * self.world * self.S * g.ldh,
                 "replica_mode_allreduce_bytes": 4 * (g.N * (g.ldh + g.pt) + self.arena_n + _lib.NSLOT),
                 "collectives_per_step": 6,
+                "serve_collectives": ("serve_rows", "serve_label_scores", "serve_states"),        # ShardExchange.serve (labelled: all three)
+                "serve_bytes": {n: self.bytes_moved.get(n, 0) for n in ("serve_rows", "serve_label_scores", "serve_states")},
                 "note": "all-gather [attout | label | negatives | coefficient] rows, all-gather softmax stats, reduce-scatter dX, "
                         "all-gather [row | id] item-row gradients, all-reduce arena, all-gather updated item rows; the dense item "
                         "gradient and the candidate-time block stay local"}
@@ -386,6 +522,18 @@ class ShardedEngine(TcarEngine):
 
     _update_ctx = _shard_ctx
 
+    def _serve_ctx(self):
+        """the shard's context of the serving pieces (tcar_shard_serve_begin / _fold): candidate side = this rank's shard, none of the
+        training step's scoring workspaces (an engine that only serves never allocates them)"""
+        c = self._ctx()
+        if getattr(self, "_svctx_src", None) is not c:
+            s = _lib.Ctx()
+            C.memmove(C.byref(s), C.byref(c), C.sizeof(_lib.Ctx))
+            s.d = self.dims_cand
+            s.E = self.E.data_ptr() + 4 * self.n0 * self.geo.ek
+            self._svctx, self._svctx_src = s, c
+        return self._svctx
+
     def _update_local(self):
         """clip + Adam: arena on every rank, the item rows of the shard by their owner; returns the staging buffer of collective 6
         (this rank's updated rows in its slot) and the installer that copies the gathered table into E"""
@@ -484,6 +632,111 @@ class ShardedEngine(TcarEngine):
                                  p(self.ce), st), "tcar_eval_rows")
         out = (self.rank[:B], self.topk[:B], self.ce[:B])
         return out + (self.ev_logits[:B, :g.N].clone(),) if keep_logits else out
+
+    # ---- streamed score-and-select over the shards (include/tcar_serve_shard.h; the collectives: ShardExchange.serve)
+    def default_panel(self) -> int:
+        """columns per panel when the caller names none: the widest a fold takes, at most the shard's rows"""
+        return int(max(128, min(self.SERVE_MAX_PANEL, _ru(self.nl, 128))))
+
+    def serve_pieces(self, batch, k: int = 20, labelled: bool = True, exclude_seen: bool = False, exclude=None,
+                     panel: Optional[int] = None, window=None, max_per_category: Optional[int] = None, cap: Optional[int] = None,
+                     T: Optional[int] = None, bt: Optional[Batch] = None) -> _ServePieces:
+        """The armed local pieces of ONE ShardExchange.serve for this rank's sessions (`batch` / `bt`; both None: none — then T and
+        cap are needed): eval_step_streamed (labelled) and recommend hand them to the exchange; a caller that moves the buffers
+        itself calls begin / prepare / label_scores / fold / finish in that order.  No buffer of the catalog's width is touched:
+        every rank scores its shard's rows only."""
+        g = self.geo
+        if not 1 <= k <= 64:
+            raise ValueError("k must be in [1, 64]")
+        quota = self._quota(max_per_category) if max_per_category is not None else None
+        if window is not None and getattr(self, "_item_keys", None) is None:
+            raise ValueError("a window compares item keys: call set_item_keys(keys) first")
+        self.flush()
+        excl = None
+        if labelled:
+            if bt is None and batch is not None:
+                bt = self.upload(batch)
+        elif batch is not None:
+            bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
+        if bt is not None:
+            T = bt.T
+            bt = self._without_neg(bt)
+            if not bt.label:                                # (the pack reads a label per live session; unlabelled: a placeholder)
+                bt.label = self._label0(bt.B)
+        elif T is None or cap is None:
+            raise ValueError("a rank without sessions needs the step's T and cap")
+        elif not labelled:                                  # the exclusion width every rank packs
+            ex = np.asarray(exclude) if exclude is not None else np.zeros((0, 0))
+            X = (T if exclude_seen else 0) + (int(ex.shape[1]) if ex.ndim == 2 else 0)
+            excl = torch.zeros(0, X, dtype=torch.int32, device=self.dev) if X else None
+        B = bt.B if bt is not None else 0
+        cap = max(cap or 0, B, 1)
+        panel = self.default_panel() if not panel else int(panel)
+        if panel <= 0 or panel % 128 or panel > self.SERVE_MAX_PANEL:
+            raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
+        panel = min(panel, _ru(self.nl, 128))
+        self._ensure_work(max(B, 1), T)
+        X = int(excl.shape[1]) if excl is not None else 0
+        Bq, K, rw = self.world * cap, 2 + X, 2 * k + 4
+        ld = _ru(g.ek + 2 + K, 4)
+        rp = _ru(Bq, 128)
+        self.ws.ensure([Spec("sv_head", (cap, ld), F32, 0), Spec("sv_lab", (Bq,), I32, -1), Spec("sv_coef", (Bq,), F32, 0),
+                        Spec("sv_meta", (Bq, K), I32, -1), Spec("sv_lohi", (2, Bq), I32, 0), Spec("sv_excl", (Bq, max(X, 1)), I32, -1),
+                        Spec("sv_a16h", (rp, g.ek), BF16, 0), Spec("sv_a16l", (rp, g.ek), BF16, 0),
+                        Spec("sv_lab_part", (Bq,), F32, 0), Spec("sv_lab_score", (Bq,), F32, 0),
+                        Spec("sv_panel", (Bq, panel), F32), Spec("sv_state", (Bq, rw), I32), Spec("sv_merged", (cap, rw), I32),
+                        Spec("sel_score", (cap, k), F32), Spec("sel_topk", (cap, k), I32), Spec("sel_rank", (cap,), I32),
+                        Spec("sel_ce", (cap,), F32)])
+        meta = None
+        if B:
+            # the ints that ride behind attout: [lo | hi | exclusion ids], one row per local session
+            if window is not None:
+                lo, hi = self._window_bounds(window, B)
+                lohi = torch.from_numpy(np.stack([lo, hi], axis=1)).to(self.dev)
+            else:
+                lohi = torch.zeros(B, 2, dtype=torch.int32, device=self.dev)
+            meta = torch.cat([lohi, excl], dim=1).contiguous() if X else lohi
+        pc = getattr(self, "_serve_pc", None)
+        if pc is None:
+            pc = self._serve_pc = _ServePieces(self)
+        pc.arm(bt, cap, k, panel, labelled, meta, X, window is not None, quota)
+        return pc
+
+    def _serve(self, pc: _ServePieces):
+        out = self.xch.serve(pc, pc.cap, pc.labelled)
+        self.poll_fork_errors()
+        return out
+
+    @staticmethod
+    def _without_neg(bt: Batch) -> Batch:
+        nb = Batch()
+        C.memmove(C.byref(nb), C.byref(bt), C.sizeof(Batch))
+        nb.neg, nb.K = None, 0
+        nb._keep = getattr(bt, "_keep", None)
+        return nb
+
+    def _label0(self, B: int) -> int:
+        self.ws.ensure([Spec("sv_label0", (B,), I32, 0)])
+        return self.sv_label0.data_ptr()
+
+    def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None, window=None,
+                           max_per_category: Optional[int] = None, cap: Optional[int] = None, T: Optional[int] = None):
+        """TcarEngine.eval_step_streamed over the shards: (rank[B] int32, topk[B,k] int32, ce[B] f32) of THIS rank's sessions against
+        the whole catalog, `last_scores` the scores of the lists.  A COLLECTIVE: every rank calls it — `batch` = None (and `bt` =
+        None) on a rank without sessions, which must then be told the step's input length T and `cap`, the rows every rank
+        contributes to the all-gathers (>= the largest local batch; default: the local batch size).  topk, scores and rank are the
+        bits the unsharded streamed call gives for the same scores; ce differs by the rounding of the repartitioned sum."""
+        pc = self.serve_pieces(batch, k, True, panel=panel, window=window, max_per_category=max_per_category, cap=cap, T=T, bt=bt)
+        rank, topk, ce, self.last_scores = self._serve(pc)
+        return rank, topk, ce
+
+    def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,
+                  max_per_category: Optional[int] = None, cap: Optional[int] = None, T: Optional[int] = None):
+        """TcarEngine.recommend over the shards: (topk [B,k] int32, scores [B,k] f32) of this rank's sessions.  A COLLECTIVE, as
+        eval_step_streamed; every rank passes exclusion lists of the same width (exclude_seen adds T ids, `exclude` its columns)."""
+        pc = self.serve_pieces(batch, k, False, exclude_seen, exclude, panel, window, max_per_category, cap, T)
+        _, topk, _, self.last_scores = self._serve(pc)
+        return topk, self.last_scores
 
     # ------------------------------------------------------------------------------ inspection (tests, export)
     def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:

@@ -2,6 +2,14 @@
 Usage: python tools/eval_bench.py [iters] [--n_items N] [--streamed [--panel P[,P...]] [--window FRAC[,FRAC...]]
                                                                [--cap M[,M...]] [--cats C] [--cap_skew]] [--rounds R]
 
+       python tools/eval_bench.py [iters] [--n_items N] --streamed --sharded W [--panel P[,P...]] [--rounds R]
+
+--sharded W: the per-rank time of one evaluation step of the catalog-sharded engine at the shapes of RANK 0 of a W-rank job, on one GPU
+(W > 1: TCAR_SIM_WORLD=W — every all-gather repeats the local rows, so the buffers have the job's shapes and the results mean nothing
+beyond them; the collectives' own time is not in the numbers): ShardedEngine.eval_step, which scores the B local sessions against the
+WHOLE catalog on the fp32 GEMM, beside ShardedEngine.eval_step_streamed, which scores the W B gathered sessions against the shard's
+N / W rows on its split-bf16 planes and merges W states.
+
 Without --streamed: eval_step (materialised [B, N] scores) at the Globo shape, as before.  With --streamed: eval_step and
 eval_step_streamed at every panel size named (default: the engine's default panel), alternating in the same process for `rounds`
 rounds so that the spread between rounds is visible; the streamed results are compared with eval_step's at the timed size.
@@ -28,6 +36,7 @@ ap.add_argument("--window", type=str, default="", help="comma-separated fraction
 ap.add_argument("--cap", type=str, default="", help="comma-separated caps: at most M items of one category in a list")
 ap.add_argument("--cats", type=int, default=300, help="number of category codes when the synthetic fold carries no category table")
 ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog whose items all share one category")
+ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (needs --streamed)")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -35,7 +44,16 @@ if not torch.cuda.is_available():
 N, B, iters = a.n_items, 512, a.iters
 fold = SynthFold(n_items=N, dim=250, n_train=60000, n_test=1000, seed=2020, **(dict(lean=True) if N > 200000 else {}))
 np.random.seed(2020)
-eng = TcarEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
+if a.sharded:
+    if not a.streamed:
+        sys.exit("--sharded W compares the two evaluation steps of the catalog-sharded engine: it needs --streamed")
+    if a.sharded > 1:
+        os.environ["TCAR_SIM_WORLD"] = str(a.sharded)
+    from tcar_amd.sharded import ShardedEngine
+    eng = ShardedEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
+    assert eng.world == a.sharded
+else:
+    eng = TcarEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
 batches = build_batches(fold, 16, B, 0, np.random.RandomState(1), CONFIGS["globo"])
 res = [eng.make_resident(b) for b in batches]
 
@@ -57,6 +75,31 @@ if not a.streamed:
     print("eval step: %.3f ms  = %.0f sessions/s" % (dt * 1e3, B / dt))
     sys.exit(0)
 panels = [int(p) for p in a.panel.split(",") if p] or [0]
+if a.sharded:
+    W = eng.world
+    print("N=%d sharded W=%d: shard of %d rows, %d gathered sessions per step" % (N, W, eng.nl, W * B))
+    if W == 1 and eng.geo.Npad <= 49152:       # one shard: the two steps see the same catalog, so their results compare
+        r0, t0, c0 = [x.clone() for x in eng.eval_step(None, bt=res[0])]
+        r1, t1, c1 = eng.eval_step_streamed(None, bt=res[0], panel=panels[0] or None)
+        print("N=%d W=1: rank equal %.4f, top-20 rows equal %.4f, max |ce diff| %.2e" % (
+            N, (r0 == r1).float().mean().item(), (t0 == t1).all(1).float().mean().item(), (c0 - c1).abs().max().item()))
+    # ShardedEngine.eval_step ends in tcar_eval_rows with a CE output, which takes rows of at most 49,152 columns: beyond that the
+    # materialised step returns an argument error, so only the streamed step is timed
+    wide = eng.geo.Npad > 49152
+    if wide:
+        print("N=%d W=%d: ShardedEngine.eval_step does not run at this size (tcar_eval_rows takes no CE for rows wider than 49,152 "
+              "columns): nothing to set the streamed step beside" % (N, W))
+    for rnd in range(a.rounds):
+        dt = None
+        if not wide:
+            dt = timed(plain)
+            print("N=%d W=%d round %d sharded eval_step (materialised, whole catalog, fp32): %.3f ms = %.0f sessions/s" % (N, W, rnd, dt * 1e3, B / dt))
+        for P in panels:
+            ds = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None, cap=B))
+            print("N=%d W=%d round %d sharded eval_step_streamed panel=%d: %.3f ms = %.0f sessions/s%s" % (
+                N, W, rnd, P or eng.default_panel(), ds * 1e3, B / ds, ", %.3f of the materialised step" % (ds / dt) if dt else ""))
+        sys.stdout.flush()
+    sys.exit(0)
 fracs = [float(f) for f in a.window.split(",") if f]
 if fracs:
     eng.set_item_keys(np.arange(N, dtype=np.int32))
