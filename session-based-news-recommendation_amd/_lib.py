@@ -31,13 +31,22 @@ def _hipcc() -> str:
     return "hipcc"
 
 
-HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_hip.h")       # the C ABI: compiled into the library AND read by _bind() below
-SERVE_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_serve.h")  # streamed score-and-select, layered on HEADER (read by _bind() too)
-WINDOW_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_window.h")  # publish-time windows of the streamed selection, layered on SERVE_HEADER
-QUOTA_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_quota.h")  # per-category caps of the streamed selection, layered on WINDOW_HEADER
-SERVE_SHARD_HEADER = os.path.join(PKG_DIR, "..", "include", "tcar_serve_shard.h")  # state merge + the shard's fold of the catalog-sharded serving path, on QUOTA_HEADER
-HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER,
-           SERVE_SHARD_HEADER]
+# The C ABI, one row per layer: (prefix of the layer's names in this module, its header under include/).  Every header is compiled
+# into the library AND read by _bind(), and each builds on the rows above it: the core; streamed score-and-select; its publish-time
+# windows; its per-category caps; the state merge and the shard's fold of the catalog-sharded serving path.
+ABI_LAYERS = [("", "tcar_hip.h"), ("SERVE", "tcar_serve.h"), ("WINDOW", "tcar_window.h"), ("QUOTA", "tcar_quota.h"),
+              ("SERVE_SHARD", "tcar_serve_shard.h")]
+
+
+def _name(prefix: str, name: str) -> str:
+    """the module name `name` of the layer `prefix`: HEADER / SERVE_HEADER, SYMBOLS / SERVE_SYMBOLS, ..."""
+    return prefix + "_" + name if prefix else name
+
+
+for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER
+    globals()[_name(_prefix, "HEADER")] = os.path.join(PKG_DIR, "..", "include", _file)
+HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h")] + \
+    [globals()[_name(_prefix, "HEADER")] for _prefix, _ in ABI_LAYERS]
 _ID_MARK = b"TCAR_BUILD_ID="
 
 
@@ -191,38 +200,22 @@ def _read_header(path: str, const: dict, structs: dict):
 
 
 def _bind() -> None:
-    """Read the C ABI from the headers: the constants, one ctypes.Structure per `typedef struct` (header order, so nested structs
-    resolve) and (restype, argtypes) of every declared function.  Defines them as attributes of this module, once.  tcar_hip.h
-    gives SYMBOLS / ABI_VERSION / the struct mirrors; tcar_serve.h, which builds on it, its own names: SERVE_SYMBOLS,
-    SERVE_ABI_VERSION and the mirror Serve; tcar_window.h, which builds on that, WINDOW_SYMBOLS, WINDOW_ABI_VERSION and Window;
-    tcar_quota.h, on top of it, QUOTA_SYMBOLS, QUOTA_ABI_VERSION and Quota; tcar_serve_shard.h, on top of that, SERVE_SHARD_SYMBOLS and
-    SERVE_SHARD_ABI_VERSION (it declares no struct)."""
+    """Read the C ABI from the headers of ABI_LAYERS, in order: the constants, one ctypes.Structure per `typedef struct` (header order,
+    so nested structs resolve) and (restype, argtypes) of every declared function.  Each layer is read on top of the constants and
+    structs of the layers above it and publishes, as attributes of this module, <PREFIX>_SYMBOLS, <PREFIX>_ABI_VERSION and its
+    struct mirrors (the core layer, without a prefix: SYMBOLS, ABI_VERSION, Dims, Ctx, ...); the prototypes of all layers go into
+    _PROTOTYPES.  Once."""
     g = globals()
     if "SYMBOLS" in g:
         return
-    const, structs = {}, {}
-    classes, protos = _read_header(HEADER, const, structs)
-    serve_const, serve_structs = dict(const), dict(structs)
-    serve_classes, serve_protos = _read_header(SERVE_HEADER, serve_const, serve_structs)
-    window_const, window_structs = dict(serve_const), dict(serve_structs)
-    window_classes, window_protos = _read_header(WINDOW_HEADER, window_const, window_structs)
-    quota_const, quota_structs = dict(window_const), dict(window_structs)
-    quota_classes, quota_protos = _read_header(QUOTA_HEADER, quota_const, quota_structs)
-    shard_const, shard_structs = dict(quota_const), dict(quota_structs)
-    shard_classes, shard_protos = _read_header(SERVE_SHARD_HEADER, shard_const, shard_structs)
-    g.update(classes)
-    g.update(shard_classes)
-    g.update(serve_classes)
-    g.update(window_classes)
-    g.update(quota_classes)
-    g.update(ABI_VERSION=const["TCAR_ABI_VERSION"], NSLOT=const["TCAR_NSLOT"], NVAR=const["TCAR_NVAR"], SYMBOLS=list(protos),
-             _PROTOTYPES=protos, TUNING_FIELDS=[f[0] for f in classes["Tuning"]._fields_],
-             SERVE_ABI_VERSION=serve_const["TCAR_SERVE_ABI_VERSION"], SERVE_SYMBOLS=list(serve_protos), _SERVE_PROTOTYPES=serve_protos,
-             WINDOW_ABI_VERSION=window_const["TCAR_WINDOW_ABI_VERSION"], WINDOW_SYMBOLS=list(window_protos),
-             _WINDOW_PROTOTYPES=window_protos,
-             QUOTA_ABI_VERSION=quota_const["TCAR_QUOTA_ABI_VERSION"], QUOTA_SYMBOLS=list(quota_protos), _QUOTA_PROTOTYPES=quota_protos,
-             SERVE_SHARD_ABI_VERSION=shard_const["TCAR_SERVE_SHARD_ABI_VERSION"], SERVE_SHARD_SYMBOLS=list(shard_protos),
-             _SERVE_SHARD_PROTOTYPES=shard_protos)
+    const, structs, out = {}, {}, {"_PROTOTYPES": {}}
+    for prefix, _ in ABI_LAYERS:
+        classes, protos = _read_header(g[_name(prefix, "HEADER")], const, structs)
+        out.update(classes)
+        out[_name(prefix, "SYMBOLS")] = list(protos)
+        out[_name(prefix, "ABI_VERSION")] = const["TCAR_" + _name(prefix, "ABI_VERSION")]
+        out["_PROTOTYPES"].update(protos)
+    g.update(out, NSLOT=const["TCAR_NSLOT"], NVAR=const["TCAR_NVAR"], TUNING_FIELDS=[f[0] for f in out["Tuning"]._fields_])
 
 
 def __getattr__(name: str):
@@ -270,25 +263,19 @@ def load() -> C.CDLL:
         raise TcarError("libtcar_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'`; "
                         "there is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    missing = [s for s in SYMBOLS + SERVE_SYMBOLS + WINDOW_SYMBOLS + QUOTA_SYMBOLS + SERVE_SHARD_SYMBOLS if not hasattr(lib, s)]
+    g = globals()
+    missing = [s for prefix, _ in ABI_LAYERS for s in g[_name(prefix, "SYMBOLS")] if not hasattr(lib, s)]
     if missing:
         raise TcarError("libtcar_hip.so lacks symbols: %s" % missing)
-    for s, (restype, argtypes) in list(_PROTOTYPES.items()) + list(_SERVE_PROTOTYPES.items()) + list(_WINDOW_PROTOTYPES.items()) + \
-            list(_QUOTA_PROTOTYPES.items()) + list(_SERVE_SHARD_PROTOTYPES.items()):
+    for s, (restype, argtypes) in _PROTOTYPES.items():
         f = getattr(lib, s)
         f.restype, f.argtypes = restype, argtypes
-    if lib.tcar_abi_version() != ABI_VERSION:
-        raise TcarError("libtcar_hip.so has ABI %d, these bindings expect %d: rebuild (python -c 'import __graft_entry__ "
-                        "as g; g.build()')" % (lib.tcar_abi_version(), ABI_VERSION))
-    if lib.tcar_serve_abi_version() != SERVE_ABI_VERSION:
-        raise TcarError("libtcar_hip.so has serve ABI %d, these bindings expect %d: rebuild" % (lib.tcar_serve_abi_version(), SERVE_ABI_VERSION))
-    if lib.tcar_window_abi_version() != WINDOW_ABI_VERSION:
-        raise TcarError("libtcar_hip.so has window ABI %d, these bindings expect %d: rebuild" % (lib.tcar_window_abi_version(), WINDOW_ABI_VERSION))
-    if lib.tcar_quota_abi_version() != QUOTA_ABI_VERSION:
-        raise TcarError("libtcar_hip.so has quota ABI %d, these bindings expect %d: rebuild" % (lib.tcar_quota_abi_version(), QUOTA_ABI_VERSION))
-    if lib.tcar_serve_shard_abi_version() != SERVE_SHARD_ABI_VERSION:
-        raise TcarError("libtcar_hip.so has serve-shard ABI %d, these bindings expect %d: rebuild"
-                        % (lib.tcar_serve_shard_abi_version(), SERVE_SHARD_ABI_VERSION))
+    for prefix, _ in ABI_LAYERS:           # tcar_abi_version, tcar_serve_abi_version, ...: "serve ABI", ..., "serve-shard ABI"
+        got, want = getattr(lib, "tcar_" + _name(prefix.lower(), "abi_version"))(), g[_name(prefix, "ABI_VERSION")]
+        if got != want:
+            raise TcarError("libtcar_hip.so has %sABI %d, these bindings expect %d: rebuild%s"
+                            % (prefix and prefix.lower().replace("_", "-") + " ", got, want,
+                               "" if prefix else " (python -c 'import __graft_entry__ as g; g.build()')"))
     # a binary built from other sources than the ones next to it is stale (the build is digest-gated, not mtime-gated)
     if have_sources():
         got, want = lib.tcar_build_id().decode(), source_build_id()

@@ -12,8 +12,6 @@
 namespace {
 
 constexpr int SEL_NT = 512;             // threads of a fold workgroup
-constexpr int SEL_MAX_N = 512 * 4 * 24; // columns of a fold (row slice in registers: 24 float4 per thread)
-constexpr int SEL_MAX_K = 64;
 
 // state row of one session, 2k + 4 words: score[k] | index[k] (-1: empty) | count, max, sum, pad
 __host__ __device__ inline int sel_row_words(int k) { return 2 * k + 4; }
@@ -563,6 +561,9 @@ __global__ __launch_bounds__(64) void label_score_bf16_kernel(int N, int K, cons
   if (lane == 0) out[b] = s;
 }
 
+// a cap goes with a category table (then >= 1), and with nothing else
+inline bool bad_quota(const int32_t* cat, int cap) { return cat ? cap < 1 : cap != 0; }
+
 }  // namespace
 
 extern "C" int tcar_serve_abi_version(void) { return TCAR_SERVE_ABI_VERSION; }
@@ -590,7 +591,7 @@ extern "C" int tcar_quota_abi_version(void) { return TCAR_QUOTA_ABI_VERSION; }
 extern "C" int tcar_select_panel_quota(int B, int n0, int n, const float* panel, int64_t ld, int k, const int32_t* label,
                                        const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
                                        const int32_t* key, const int32_t* lo, const int32_t* hi, const int32_t* cat, int cap) {
-  if (cat ? cap < 1 : cap != 0) return TCAR_E_ARG;
+  if (bad_quota(cat, cap)) return TCAR_E_ARG;
   if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
   if (B < 0 || k < 1 || k > SEL_MAX_K || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
   if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
@@ -641,7 +642,7 @@ extern "C" int tcar_serve_shard_abi_version(void) { return TCAR_SERVE_SHARD_ABI_
 
 extern "C" int tcar_select_merge(int B, int k, int S, const void* states, int64_t stride_words, void* out, const int32_t* cat, int cap,
                                  void* stream) {
-  if (cat ? cap < 1 : cap != 0) return TCAR_E_ARG;
+  if (bad_quota(cat, cap)) return TCAR_E_ARG;
   if (B < 0 || k < 1 || k > SEL_MAX_K || S < 1 || S > 64) return TCAR_E_ARG;
   const int64_t rows = (int64_t)B * sel_row_words(k);
   if (S > 1 && stride_words < rows) return TCAR_E_ARG;

@@ -1276,20 +1276,25 @@ int serve_fold(const tcar_ctx_t* c, int B, const void* a16h, const void* a16l, i
   }
   return TCAR_OK;
 }
-}  // namespace
 
-// Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, then the catalog in column
-// panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel while the panel is cache-warm.
-// A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row blocks).
-// w (include/tcar_window.h): every fold keeps to the sessions' pools; NULL: the unwindowed step.
-// q (include/tcar_quota.h): every fold caps the list's entries per category; NULL: the uncapped step.
-extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
-                                     const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
-  if (!c || !bt || !s || bt->B < 0) return TCAR_E_ARG;
+// the descriptors of a streamed call; need_topk: the call finishes the state itself (a whole step, not a shard's fold)
+int check_serve_desc(const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, bool need_topk) {
+  if (!s) return TCAR_E_ARG;
   if (w && (!w->key || !w->lo || !w->hi)) return TCAR_E_ARG;
   if (q && (!q->cat || q->cap < 1)) return TCAR_E_ARG;
-  if (s->k < 1 || s->k > 64 || s->panel <= 0 || (s->panel & 127) || s->panel > 512 * 4 * 24) return TCAR_E_ARG;
-  if (!s->panel_buf || !s->state || !s->topk || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0)) return TCAR_E_ARG;
+  if (s->k < 1 || s->k > SEL_MAX_K || s->panel <= 0 || (s->panel & 127) || s->panel > SEL_MAX_N) return TCAR_E_ARG;
+  if (!s->panel_buf || !s->state || (need_topk && !s->topk) || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0))
+    return TCAR_E_ARG;
+  return TCAR_OK;
+}
+}  // namespace
+
+// Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, the label scores, then
+// serve_fold over the whole catalog and the finishing launch.  w / q NULL: the unwindowed / uncapped step.
+extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
+                                     const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  if (!c || !bt || bt->B < 0) return TCAR_E_ARG;
+  RET(check_serve_desc(s, w, q, true));
   if (s->state_bytes < tcar_select_state_bytes(bt->B, s->k)) return TCAR_E_ARG;
   if (bt->label && !s->lab_score) return TCAR_E_ARG;
   if (bt->B == 0) return TCAR_OK;
@@ -1495,11 +1500,7 @@ extern "C" int tcar_shard_serve_begin(const tcar_ctx_t* sc, const tcar_shard_t* 
 
 extern "C" int tcar_shard_serve_fold(const tcar_ctx_t* sc, const tcar_shard_t* sh, const int32_t* label, const float* lab_score,
                                      const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
-  if (!s) return TCAR_E_ARG;
-  if (w && (!w->key || !w->lo || !w->hi)) return TCAR_E_ARG;
-  if (q && (!q->cat || q->cap < 1)) return TCAR_E_ARG;
-  if (s->k < 1 || s->k > 64 || s->panel <= 0 || (s->panel & 127) || s->panel > 512 * 4 * 24) return TCAR_E_ARG;
-  if (!s->panel_buf || !s->state || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0)) return TCAR_E_ARG;
+  RET(check_serve_desc(s, w, q, false));
   if ((label != nullptr) != (lab_score != nullptr)) return TCAR_E_ARG;
   RET(check_shard_serve(sc, sh));
   const int Bq = sh->world * sh->cap;

@@ -25,6 +25,10 @@
 
 static inline bool tcar_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Limits of the streamed selection (select.hip), which the serve entry points of step.hip check too
+constexpr int SEL_MAX_N = 512 * 4 * 24;  // columns of a fold (row slice in registers: 24 float4 per thread)
+constexpr int SEL_MAX_K = 64;
+
 // One-time, per-DEVICE kernel attributes (hipFuncSetAttribute for > 64 KB of dynamic LDS).  One bit per device ordinal:
 // correct with several devices in one process and safe from several host threads (two threads may both set the
 // attribute once: the call is idempotent).  This is the only mutable state the library keeps.

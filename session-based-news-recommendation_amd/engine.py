@@ -860,7 +860,7 @@ class TcarEngine(OpLevelStep):
         return out + (logits,) if keep_logits else out
 
     # ---- streamed score-and-select (include/tcar_serve.h): evaluation and recommendation without the [B, N] logits
-    SERVE_MAX_PANEL = 49152        # columns one fold keeps in registers (tcar_select_panel)
+    SERVE_MAX_PANEL = 49152        # columns one fold keeps in registers (tcar_select_panel: SEL_MAX_N of csrc/tcar_common.h)
 
     def default_panel(self) -> int:
         """Columns per panel when the caller names none: 49,152, the widest a fold takes (at most Npad) — at B = 512, k = 20 the
@@ -884,8 +884,6 @@ class TcarEngine(OpLevelStep):
 
     def _window_bounds(self, window, B: int):
         """(lo, hi), each a scalar or an int array [B] -> two int32 host arrays [B]; bounds beyond int32 are clipped to it"""
-        if getattr(self, "_item_keys", None) is None:
-            raise ValueError("a window compares item keys: call set_item_keys(keys) first")
         try:
             lo, hi = window
             lo, hi = (np.ascontiguousarray(np.broadcast_to(np.clip(np.asarray(x, dtype=np.int64), -2 ** 31, 2 ** 31 - 1), (B,)),
@@ -901,9 +899,30 @@ class TcarEngine(OpLevelStep):
         # most of what a window costs a small catalog's step, docs/EXPERIMENTS.md)
         self.ws.ensure([Spec("win_lohi", (2, self.work_B), I32)])
         self.win_lohi[:, :B].copy_(torch.from_numpy(np.stack([lo, hi])))
+        return self._window_desc(self._item_keys, self.win_lohi)
+
+    @staticmethod
+    def _window_desc(keys: torch.Tensor, lohi: torch.Tensor) -> Window:
+        """the window descriptor over the item keys [N] and the bounds [2, >= B] (row 0: lo, row 1: hi) on the device"""
         w = Window()
-        w.key, w.lo, w.hi = self._item_keys.data_ptr(), self.win_lohi[0].data_ptr(), self.win_lohi[1].data_ptr()
+        w.key, w.lo, w.hi = keys.data_ptr(), lohi[0].data_ptr(), lohi[1].data_ptr()
         return w
+
+    @staticmethod
+    def _serve_desc(k: int, panel: int, panel_buf: torch.Tensor, state: torch.Tensor, excl: Optional[torch.Tensor] = None, X: int = 0,
+                    lab_score: Optional[torch.Tensor] = None, outputs=()) -> Serve:
+        """the descriptor of a streamed call over device tensors: the panel buffer, the select state, the exclusion lists
+        [>= B, X] (None: none), the label-score workspace and the (topk, score, rank, ce) a whole step writes (a fold alone: none)"""
+        s = Serve()
+        s.k, s.panel = k, panel
+        s.panel_buf, s.state, s.state_bytes = panel_buf.data_ptr(), state.data_ptr(), state.numel() * 4
+        if lab_score is not None:
+            s.lab_score = lab_score.data_ptr()
+        if excl is not None:
+            s.excl, s.X = excl.data_ptr(), X
+        for f, t in zip(("topk", "score", "rank", "ce"), outputs):
+            setattr(s, f, t.data_ptr())
+        return s
 
     def _quota(self, max_per_category) -> Quota:
         """max_per_category -> the descriptor of a capped call (include/tcar_quota.h) over the table of set_categories()"""
@@ -915,22 +934,30 @@ class TcarEngine(OpLevelStep):
         q.cat, q.cap = self._cat.data_ptr(), int(min(max_per_category, 2 ** 31 - 1))
         return q
 
-    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None,
-               max_per_category=None):
-        """one tcar_serve_step (tcar_serve_step_window with a `window`, tcar_serve_step_quota with a `max_per_category`); returns
-        (rank, topk, ce, scores) views of the workspace (rank / ce only when `labelled`)"""
-        g = self.geo
-        if self.shard != (0, g.N):
-            raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
+    def _serve_request(self, k: int, panel: Optional[int], window, max_per_category, width: int):
+        """The request of a streamed call, validated before anything is launched -> (k, panel, quota): k, the columns per panel
+        (`panel`, None or 0: default_panel()) clipped to `width`, the scored columns rounded up to 128, and the descriptor of
+        `max_per_category` (None: no cap).  A `window` needs the item keys."""
         if not 1 <= k <= 64:
             raise ValueError("k must be in [1, 64]")
         quota = self._quota(max_per_category) if max_per_category is not None else None
-        B = bt.B
-        self._ensure_work(B, bt.T)
+        if window is not None and getattr(self, "_item_keys", None) is None:
+            raise ValueError("a window compares item keys: call set_item_keys(keys) first")
         panel = self.default_panel() if not panel else int(panel)
         if panel <= 0 or panel % 128 or panel > self.SERVE_MAX_PANEL:
             raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
-        panel = min(panel, g.Npad)
+        return k, min(panel, width), quota
+
+    def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None,
+               max_per_category=None):
+        """one tcar_serve_step_quota (its window / quota NULL where the request has none); returns (rank, topk, ce, scores) views of
+        the workspace (rank / ce only when `labelled`)"""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
+        k, panel, quota = self._serve_request(k, panel, window, max_per_category, g.Npad)
+        B = bt.B
+        self._ensure_work(B, bt.T)
         wb = self.work_B
         state_words = 2 * k + 4                  # tcar_select_state_bytes(B, k) / (4 B)
         specs = [Spec("panel_buf", (wb, panel), F32), Spec("sel_state", (wb, state_words), I32), Spec("lab_score", (wb,), F32),
@@ -939,37 +966,29 @@ class TcarEngine(OpLevelStep):
             specs.append(Spec("excl", (wb, int(excl.shape[1])), I32))
         self.ws.ensure(specs)
         assert self.lib.tcar_select_state_bytes(B, k) <= self.sel_state.numel() * 4
-        s = Serve()
-        s.k, s.panel = k, panel
-        s.panel_buf, s.state, s.state_bytes = self.panel_buf.data_ptr(), self.sel_state.data_ptr(), self.sel_state.numel() * 4
-        s.lab_score = self.lab_score.data_ptr()
         if excl is not None:
             self.excl[:B].copy_(excl)
-            s.excl, s.X = self.excl.data_ptr(), int(excl.shape[1])
-        s.topk, s.score, s.rank, s.ce = (t.data_ptr() for t in (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
+        s = self._serve_desc(k, panel, self.panel_buf, self.sel_state, self.excl if excl is not None else None,
+                             int(excl.shape[1]) if excl is not None else 0, self.lab_score,
+                             (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
         if not labelled:
-            bt = self._without_label(bt)
-        if quota is not None:
-            w = self._window(window, B) if window is not None else None
-            check(self.lib.tcar_serve_step_quota(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s),
-                                                 C.byref(w) if w is not None else None, C.byref(quota), self._stream()),
-                  "tcar_serve_step_quota")
-        elif window is not None:
-            w = self._window(window, B)
-            check(self.lib.tcar_serve_step_window(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), C.byref(w),
-                                                  self._stream()), "tcar_serve_step_window")
-        else:
-            check(self.lib.tcar_serve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s), self._stream()),
-                  "tcar_serve_step")
+            bt = self._without_neg(bt, label=False)
+        w = self._window(window, B) if window is not None else None
+        check(self.lib.tcar_serve_step_quota(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s),
+                                             C.byref(w) if w is not None else None, C.byref(quota) if quota is not None else None,
+                                             self._stream()), "tcar_serve_step_quota")
         self._time_dirty = False
         self.poll_fork_errors()
         return self.sel_rank[:B], self.sel_topk[:B], self.sel_ce[:B], self.sel_score[:B]
 
     @staticmethod
-    def _without_label(bt: Batch) -> Batch:
+    def _without_neg(bt: Batch, label: bool = True) -> Batch:
+        """a copy of the descriptor without its negatives (label=False: without its labels too)"""
         nb = Batch()
         C.memmove(C.byref(nb), C.byref(bt), C.sizeof(Batch))
-        nb.label, nb.neg, nb.K = None, None, 0
+        nb.neg, nb.K = None, 0
+        if not label:
+            nb.label = None
         nb._keep = getattr(bt, "_keep", None)
         return nb
 

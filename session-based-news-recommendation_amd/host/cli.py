@@ -44,6 +44,9 @@ REFERENCE_FLAGS = [
 ]
 
 
+MAX_PANEL = 49152          # the widest panel a fold takes (SEL_MAX_N of csrc/tcar_common.h; engine.TcarEngine.SERVE_MAX_PANEL)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="TCAR trainer (MI355X-native hot path)")
     for name, default, typ, hlp in REFERENCE_FLAGS:
@@ -70,7 +73,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "scoring (sharded.py: the item gradient stays on the rank that owns the rows)")
     ap.add_argument("--eval_panel", default=0, type=int,
                     help="P > 0: evaluation scores the catalog P columns at a time and selects while it streams (no [B, N] score matrix, "
-                         "any catalog size; P % 128 == 0, P <= 49152).  0: the materialised evaluation.  Not with --dp_mode sharded")
+                         "any catalog size; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  0: the materialised evaluation.  Not with --dp_mode sharded")
     ap.add_argument("--fresh_hours", default=0, type=float,
                     help="H > 0: evaluation ranks every session inside its POOL — the items published in the H hours up to the label's "
                          "click (and the label) — not against the whole catalog.  Needs --eval_panel; not with --dp_mode sharded.  0: off")
@@ -80,7 +83,7 @@ def build_parser() -> argparse.ArgumentParser:
                          "--dp_mode sharded; combines with --fresh_hours.  0: off")
     ap.add_argument("--shard_eval_panel", default=0, type=int,
                     help="P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
-                         "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= 49152).  "
+                         "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  "
                          "0: the materialised evaluation of the catalog-sharded engine")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
@@ -89,46 +92,45 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def _check_panel(flag, panel):
+    if panel < 0 or panel % 128 or panel > MAX_PANEL:
+        raise ValueError("--%s must be a multiple of 128 in [128, %d] (0: off)" % (flag, MAX_PANEL))
+
+
+def _check_streamed_option(flag, value, what, takes, eval_panel, dp_mode):
+    """an option of the streamed evaluation of ONE engine: positive, refused under --dp_mode sharded, and it needs --eval_panel"""
+    if not value:
+        return
+    if value < 0:
+        raise ValueError("--%s must be positive (0: off)" % flag)
+    if dp_mode == "sharded":
+        raise ValueError("--%s %s the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded" % (flag, what))
+    if not eval_panel:
+        raise ValueError("--%s needs --eval_panel P: only the streamed evaluation takes a %s" % (flag, takes))
+
+
 def check_eval_panel(eval_panel, dp_mode):
     """--eval_panel is the single-engine streamed evaluation: the catalog-sharded engine keeps its own evaluation"""
     if eval_panel and dp_mode == "sharded":
         raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded "
                          "(the catalog-sharded engine evaluates with its own exchange)")
-    if eval_panel and (eval_panel < 0 or eval_panel % 128 or eval_panel > 49152):
-        raise ValueError("--eval_panel must be a multiple of 128 in [128, 49152] (0: off)")
+    _check_panel("eval_panel", eval_panel)
 
 
 def check_fresh_hours(fresh_hours, eval_panel, dp_mode):
     """--fresh_hours windows the streamed evaluation (include/tcar_window.h): it needs --eval_panel and the whole catalog on one engine"""
-    if not fresh_hours:
-        return
-    if fresh_hours < 0:
-        raise ValueError("--fresh_hours must be positive (0: off)")
-    if dp_mode == "sharded":
-        raise ValueError("--fresh_hours windows the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
-    if not eval_panel:
-        raise ValueError("--fresh_hours needs --eval_panel P: only the streamed evaluation takes a publish-time window")
+    _check_streamed_option("fresh_hours", fresh_hours, "windows", "publish-time window", eval_panel, dp_mode)
 
 
 def check_cat_cap(cat_cap, eval_panel, dp_mode):
     """--cat_cap caps the lists of the streamed evaluation (include/tcar_quota.h): it needs --eval_panel and the whole catalog on one engine"""
-    if not cat_cap:
-        return
-    if cat_cap < 0:
-        raise ValueError("--cat_cap must be positive (0: off)")
-    if dp_mode == "sharded":
-        raise ValueError("--cat_cap caps the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
-    if not eval_panel:
-        raise ValueError("--cat_cap needs --eval_panel P: only the streamed evaluation takes a per-category cap")
+    _check_streamed_option("cat_cap", cat_cap, "caps", "per-category cap", eval_panel, dp_mode)
 
 
 def check_shard_eval_panel(shard_eval_panel, dp_mode):
     """--shard_eval_panel is the streamed evaluation of the catalog-sharded engine (include/tcar_serve_shard.h)"""
-    if not shard_eval_panel:
-        return
-    if shard_eval_panel < 0 or shard_eval_panel % 128 or shard_eval_panel > 49152:
-        raise ValueError("--shard_eval_panel must be a multiple of 128 in [128, 49152] (0: off)")
-    if dp_mode != "sharded":
+    _check_panel("shard_eval_panel", shard_eval_panel)
+    if shard_eval_panel and dp_mode != "sharded":
         raise ValueError("--shard_eval_panel streams the shards of the catalog-sharded engine: it needs --dp_mode sharded "
                          "(one engine with the whole catalog: --eval_panel)")
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from ..engine import TIME_NAMES, TIME_VOCAB, TcarEngine, VAR_ORDER
-from . import metrics as M
+from . import cli, metrics as M
 from .sampler import Sampler
 
 
@@ -137,18 +137,9 @@ class Seq2SeqAttNN():
         self.neg_fast = bool(args.get('neg_fast', 0))
         self.device_sampler = bool(args.get('device_sampler', 0))   # form batches + draw negatives on the GPU
         self.seed = int(args.get('seed', 2020))
-        self.eval_panel = int(args.get('eval_panel', 0) or 0)       # > 0: test() selects while the catalog streams by in panels
-        if self.eval_panel and args.get('dp_mode', 'replica') == 'sharded':
-            raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded")
-        self.fresh_hours = float(args.get('fresh_hours', 0) or 0)   # > 0: test() ranks every session inside its publish-time pool
-        from .cli import check_fresh_hours
-        check_fresh_hours(self.fresh_hours, self.eval_panel, args.get('dp_mode', 'replica'))
-        self.cat_cap = int(args.get('cat_cap', 0) or 0)             # > 0: test() caps the items of one category in every list
-        from .cli import check_cat_cap
-        check_cat_cap(self.cat_cap, self.eval_panel, args.get('dp_mode', 'replica'))
-        self.shard_eval_panel = int(args.get('shard_eval_panel', 0) or 0)     # > 0 (dp_mode sharded): test() streams every rank's shard
-        from .cli import check_shard_eval_panel
-        check_shard_eval_panel(self.shard_eval_panel, args.get('dp_mode', 'replica'))
+        # test(): eval_panel > 0 selects while the catalog streams by in panels, shard_eval_panel > 0 (dp_mode sharded) streams every
+        # rank's shard, fresh_hours > 0 ranks every session inside its publish-time pool, cat_cap > 0 caps the items of one category
+        self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -187,6 +178,18 @@ class Seq2SeqAttNN():
             self.dp_rank, self.dp_world = dist.get_rank(self.dp_group), dist.get_world_size(self.dp_group)
         else:
             self.dp_rank, self.dp_world = 0, 1
+
+    def _eval_options(self, args):
+        """(eval_panel, shard_eval_panel, fresh_hours, cat_cap) of a test() call: `args` over the values the model was built with,
+        refused where they cannot work (the command line's checks, host/cli.py)"""
+        dp_mode = args.get('dp_mode', 'replica')
+        panel, spanel, cap = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'shard_eval_panel', 'cat_cap'))
+        fresh = float(args.get('fresh_hours', getattr(self, 'fresh_hours', 0)) or 0)
+        cli.check_eval_panel(panel, dp_mode)
+        cli.check_fresh_hours(fresh, panel, dp_mode)
+        cli.check_cat_cap(cap, panel, dp_mode)
+        cli.check_shard_eval_panel(spanel, dp_mode)
+        return panel, spanel, fresh, cap
 
     # ------------------------------------------------------------------------------------------ helpers
     def _category_table(self):
@@ -369,19 +372,15 @@ class Seq2SeqAttNN():
     def test(self, sess, test_data, args):
         print('Measuring...')
         eng = self.engine
-        fresh = float(args.get('fresh_hours', self.fresh_hours) or 0)       # > 0: every session inside its publish-time pool
+        panel, spanel, fresh, cap = self._eval_options(args)
+        if spanel and not hasattr(eng, "xch"):
+            raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         time_dict = test_data[2] if len(test_data) > 2 else None
         if fresh:
-            from .cli import check_fresh_hours
-            check_fresh_hours(fresh, int(args.get('eval_panel', self.eval_panel) or 0), args.get('dp_mode', 'replica'))
             if not time_dict:
                 raise ValueError("fresh_hours takes the label's click time from the fold's session_time_dict, which this fold lacks")
             self._item_keys()
         outside = []
-        cap = int(args.get('cat_cap', getattr(self, 'cat_cap', 0)) or 0)                   # > 0: at most `cap` items of one category in a list
-        if cap:
-            from .cli import check_cat_cap
-            check_cat_cap(cap, int(args.get('eval_panel', self.eval_panel) or 0), args.get('dp_mode', 'replica'))
         hits, mrrs, ndcgs, ilds, unexps, losses = [], [], [], [], [], []
         c_hits, c_mrrs, c_ndcgs = [], [], []
         sampler = self._sampler(test_data)
@@ -390,15 +389,6 @@ class Seq2SeqAttNN():
         # ILD / unexp pair counts and the set of recommended items stay on the device (tcar_eval_diversity)
         self._install_categories()
         eng.reset_coverage()
-        panel = int(args.get('eval_panel', self.eval_panel) or 0)
-        if panel and args.get('dp_mode', 'replica') == 'sharded':
-            raise ValueError("eval_panel cannot be combined with dp_mode sharded")
-        spanel = int(args.get('shard_eval_panel', self.shard_eval_panel) or 0)      # > 0: the shards stream, the ranks' states merge
-        if spanel:
-            from .cli import check_shard_eval_panel
-            check_shard_eval_panel(spanel, args.get('dp_mode', 'replica'))
-            if not hasattr(eng, "xch"):
-                raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         for feed in prefetch_batches(sampler):
             batch += 1
             T = feed["seq"].shape[1]
@@ -408,17 +398,14 @@ class Seq2SeqAttNN():
                     eng.eval_step_streamed(None, k=20, panel=spanel, cap=_cap, T=T)
                 continue
             bt = eng.upload(feed)
-            if fresh:            # streamed, every session inside its pool (include/tcar_window.h)
-                w_lo, w_hi, out = self._fresh_window(feed, time_dict, fresh)
-                outside += out.tolist()
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=(w_lo, w_hi),
-                                                        max_per_category=cap or None)
-            elif cap:            # streamed, at most `cap` items of one category in a list (include/tcar_quota.h)
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, max_per_category=cap)
-            elif panel:          # streamed: no [B, N] score matrix (engine.eval_step_streamed)
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel)
-            elif spanel:         # streamed over the shards (sharded.ShardedEngine.eval_step_streamed)
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=spanel, cap=_cap)
+            if panel or spanel:  # streamed: no [B, N] score matrix; inside the sessions' pools (fresh), capped per category (cap)
+                window = None
+                if fresh:
+                    w_lo, w_hi, out = self._fresh_window(feed, time_dict, fresh)
+                    outside += out.tolist()
+                    window = (w_lo, w_hi)
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel or spanel, window=window,
+                                                        max_per_category=cap or None, **({"cap": _cap} if spanel else {}))
             else:
                 rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
             ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)

@@ -281,15 +281,8 @@ class _ServePieces:
     # the shard's rows, panel by panel, into one state per session of every rank
     def fold(self):
         e, Bq, lab = self.eng, self.Bq, self.labelled
-        s = _lib.Serve()
-        s.k, s.panel = self.k, self.panel
-        s.panel_buf, s.state, s.state_bytes = e.sv_panel.data_ptr(), e.sv_state.data_ptr(), e.sv_state.numel() * 4
-        if self.X:
-            s.excl, s.X = e.sv_excl.data_ptr(), self.X
-        w = None
-        if self.windowed:
-            w = _lib.Window()
-            w.key, w.lo, w.hi = e._item_keys.data_ptr(), e.sv_lohi[0].data_ptr(), e.sv_lohi[1].data_ptr()
+        s = e._serve_desc(self.k, self.panel, e.sv_panel, e.sv_state, e.sv_excl if self.X else None, self.X)
+        w = e._window_desc(e._item_keys, e.sv_lohi) if self.windowed else None
         q = self.quota
         check(e.lib.tcar_shard_serve_fold(C.byref(self.sctx), C.byref(self.sh), e._p(e.sv_lab) if lab else None,
                                           e._p(e.sv_lab_score) if lab else None, C.byref(s), C.byref(w) if w is not None else None,
@@ -646,11 +639,7 @@ class ShardedEngine(TcarEngine):
         itself calls begin / prepare / label_scores / fold / finish in that order.  No buffer of the catalog's width is touched:
         every rank scores its shard's rows only."""
         g = self.geo
-        if not 1 <= k <= 64:
-            raise ValueError("k must be in [1, 64]")
-        quota = self._quota(max_per_category) if max_per_category is not None else None
-        if window is not None and getattr(self, "_item_keys", None) is None:
-            raise ValueError("a window compares item keys: call set_item_keys(keys) first")
+        k, panel, quota = self._serve_request(k, panel, window, max_per_category, _ru(self.nl, 128))
         self.flush()
         excl = None
         if labelled:
@@ -671,10 +660,6 @@ class ShardedEngine(TcarEngine):
             excl = torch.zeros(0, X, dtype=torch.int32, device=self.dev) if X else None
         B = bt.B if bt is not None else 0
         cap = max(cap or 0, B, 1)
-        panel = self.default_panel() if not panel else int(panel)
-        if panel <= 0 or panel % 128 or panel > self.SERVE_MAX_PANEL:
-            raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
-        panel = min(panel, _ru(self.nl, 128))
         self._ensure_work(max(B, 1), T)
         X = int(excl.shape[1]) if excl is not None else 0
         Bq, K, rw = self.world * cap, 2 + X, 2 * k + 4
@@ -702,18 +687,10 @@ class ShardedEngine(TcarEngine):
         pc.arm(bt, cap, k, panel, labelled, meta, X, window is not None, quota)
         return pc
 
-    def _serve(self, pc: _ServePieces):
+    def _exchange(self, pc: _ServePieces):
         out = self.xch.serve(pc, pc.cap, pc.labelled)
         self.poll_fork_errors()
         return out
-
-    @staticmethod
-    def _without_neg(bt: Batch) -> Batch:
-        nb = Batch()
-        C.memmove(C.byref(nb), C.byref(bt), C.sizeof(Batch))
-        nb.neg, nb.K = None, 0
-        nb._keep = getattr(bt, "_keep", None)
-        return nb
 
     def _label0(self, B: int) -> int:
         self.ws.ensure([Spec("sv_label0", (B,), I32, 0)])
@@ -727,7 +704,7 @@ class ShardedEngine(TcarEngine):
         contributes to the all-gathers (>= the largest local batch; default: the local batch size).  topk, scores and rank are the
         bits the unsharded streamed call gives for the same scores; ce differs by the rounding of the repartitioned sum."""
         pc = self.serve_pieces(batch, k, True, panel=panel, window=window, max_per_category=max_per_category, cap=cap, T=T, bt=bt)
-        rank, topk, ce, self.last_scores = self._serve(pc)
+        rank, topk, ce, self.last_scores = self._exchange(pc)
         return rank, topk, ce
 
     def recommend(self, batch, k: int = 20, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,
@@ -735,7 +712,7 @@ class ShardedEngine(TcarEngine):
         """TcarEngine.recommend over the shards: (topk [B,k] int32, scores [B,k] f32) of this rank's sessions.  A COLLECTIVE, as
         eval_step_streamed; every rank passes exclusion lists of the same width (exclude_seen adds T ids, `exclude` its columns)."""
         pc = self.serve_pieces(batch, k, False, exclude_seen, exclude, panel, window, max_per_category, cap, T)
-        _, topk, _, self.last_scores = self._serve(pc)
+        _, topk, _, self.last_scores = self._exchange(pc)
         return topk, self.last_scores
 
     # ------------------------------------------------------------------------------ inspection (tests, export)

@@ -1,7 +1,7 @@
 """Capped streamed selection at the op level (include/tcar_quota.h: tcar_select_panel_quota) against the numpy walk, exactly.
 
 Built like test_gpu_window_select.py, with its sizes: one fp32 matrix x [B, ldn] per catalog size, the panels pointer views into it.
-The list of a row is quota_ref.capped_walk over its eligible items (in its pool, not excluded); topk, the scores where topk >= 0 and
+The list of a row is select_ref.capped_walk over its eligible items (in its pool, not excluded); topk, the scores where topk >= 0 and
 the rank must be the model's bits for every partition and for the panels folded in reverse order; ce must be the bits of the uncapped
 call of the same partition.  Three category tables — one code for all, about N/3 random codes, id % 5 — and two configurations:
 A (no window, no exclusions) and B (windows and exclusion lists).
@@ -15,15 +15,14 @@ One row per case:
   5  displacement: m items of one category lead the first panel, the last panel holds a better one of it
   6  B: the best item of every category is excluded and consumes no quota
   7  B: a window and a label outside it; the label is in the pool and counts against its category"""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import tcar_amd  # noqa: F401
 
-from quota_ref import capped_walk
+from select_ref import capped_walk
+from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,22 +31,6 @@ KS = (1, 20, 64)
 B = 8
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 DOM = I32_MAX                                          # the code of the dominant category of rows 3 and 5
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    _need_gpu()
-    from tcar_amd import _lib
-    return _lib.load()
-
-
-def ptr(t, off=0):
-    return C.c_void_p(t.data_ptr() + 4 * off)
 
 
 _BASE = {}

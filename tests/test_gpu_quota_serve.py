@@ -5,11 +5,11 @@ The engine check needs no tolerance: recommend(k=64) returns the 64 best items o
 scores lower, so the capped walk over those 64 — as long as it yields k items — is the capped list of the whole catalog."""
 import numpy as np
 import pytest
-import torch
 
 import tcar_amd  # noqa: F401
 
-from quota_ref import capped_walk
+from select_ref import capped_walk
+from select_util import _need_gpu
 from test_gpu_window_serve import B, N, PANEL, reference, run_test, trained
 
 pytestmark = pytest.mark.gpu
@@ -17,11 +17,6 @@ pytestmark = pytest.mark.gpu
 K, M = 10, 2
 CAT = (np.arange(N) % 8).astype(np.int32)
 CAT.setflags(write=False)
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def walk_of_the_best_64(tk64, sc64):

@@ -10,7 +10,7 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from quota_ref import capped_walk
+from select_ref import capped_walk
 from test_gpu_select import KS, PANELS, case, check_lists, close, lib, ptr, run  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu

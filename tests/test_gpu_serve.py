@@ -12,25 +12,12 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+from select_util import _need_gpu, close
+
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-3
 N, H, Ht, B, T, K = 700, 250, 64, 41, 3, 5        # the shape of test_python_sequenced_op_level_path_matches_the_cpp_driver
 PANEL, TOPK = 256, 20                             # three panels, the last one partial
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def close(got, want, rtol=RTOL, atol_scale=2e-5, name=""):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    scale = max(float(np.abs(want).max()), 1e-30)
-    err = np.abs(got - want)
-    bad = err > rtol * np.abs(want) + atol_scale * scale + 1e-9
-    assert not bad.any(), "%s: %d/%d off, max err %.3e (scale %.3e)" % (name, bad.sum(), bad.size, err.max(), scale)
 
 
 _REF = {}

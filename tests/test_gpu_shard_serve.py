@@ -4,7 +4,7 @@ include/tcar_serve_shard.h) on the inputs and bands of test_gpu_serve.
 W engines ShardedEngine(world=W, rank=r) run in ONE process without a process group; the test plays the three collectives of
 ShardExchange.serve by concatenating the ranks' buffers between the pieces.  The variables are those after two training steps (trained on
 a one-rank sharded engine and loaded into the W engines, whose candidate-time planes are then stale: the first evaluation has to rebuild
-them).  The merged result is held against the numpy merge (merge_ref) of the W shard states bit for bit, and against the fp64 oracle of
+them).  The merged result is held against the numpy merge (select_ref) of the W shard states bit for bit, and against the fp64 oracle of
 the trained variables in the bands of test_gpu_serve."""
 import copy
 import ctypes as C
@@ -24,18 +24,14 @@ import tcar_amd  # noqa: F401
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from merge_ref import merge_states  # noqa: E402
+from select_ref import merge_states  # noqa: E402
+from select_util import _need_gpu  # noqa: E402
 from test_gpu_serve import B, N, T, TOPK, check_band, close, reference  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 PANEL = 128                                     # shards of 384 / 316 rows (W = 2) and 256 / 256 / 188 (W = 3): several panels each, the last partial
 SPLITS = {2: ([25, 16], 27), 3: ([20, 0, 21], 23)}       # sessions per rank (uneven, one rank with none at W = 3), cap > the largest
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 _TRAINED = {}
@@ -100,7 +96,7 @@ def play(pcs):
 
 
 def shard_states(eng, states, k):
-    """every shard's state of every gathered session, read through tcar_select_finish -> merge_ref states [W][Bq]"""
+    """every shard's state of every gathered session, read through tcar_select_finish -> select_ref states [W][Bq]"""
     W, Bq, rw = states.shape
     out = []
     for w in range(W):

@@ -10,48 +10,22 @@ One row per case:
   1  lo == hi: the label alone / nothing                          5  pool only in the first panel
   2  about half the catalog                                       6  exactly min(k, N) items in the pool
   3  all-tie row, fewer than k items in the pool                  7  the label outside its own window"""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import tcar_amd  # noqa: F401
 
+from select_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
+
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-3
 # N -> panel sizes: the largest allowed (ceil128(N), at most 49,152) and a smaller one.  Together they reach R = 2, 8 and 24.
 PANELS = {7: (128,), 1003: (1024, 128), 20001: (20096, 4096), 49200: (49152, 8192)}
 KS = (1, 20, 64)
 B = 8
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
 LATE, EARLY = 1_000_000, -1_000_000                  # reserved key values of a few items at the end / the start of the catalog
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def close(got, want, rtol=RTOL, atol_scale=2e-5, name=""):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    scale = max(float(np.abs(want).max()), 1e-30)
-    err = np.abs(got - want)
-    bad = err > rtol * np.abs(want) + atol_scale * scale + 1e-9
-    assert not bad.any(), "%s: %d/%d off, max err %.3e (scale %.3e)" % (name, bad.sum(), bad.size, err.max(), scale)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    _need_gpu()
-    from tcar_amd import _lib
-    return _lib.load()
-
-
-def ptr(t, off=0):
-    return C.c_void_p(t.data_ptr() + 4 * off)
 
 
 _CASES = {}

@@ -11,7 +11,7 @@ import pytest
 import tcar_amd  # noqa: F401
 from tcar_amd import _lib
 
-from quota_ref import capped_walk
+from select_ref import capped_walk
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROTOTYPE = r"^((?:const )?\w+\*?) (tcar_\w+)\(([^)]*)\)\s*;"

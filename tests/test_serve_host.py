@@ -4,6 +4,9 @@ import ctypes as C
 import os
 import re
 import subprocess
+import types
+
+import pytest
 
 import tcar_amd  # noqa: F401
 from tcar_amd import _lib
@@ -111,3 +114,31 @@ def test_argument_errors_come_back_before_any_launch():
     assert lib.tcar_serve_step(None, C.byref(bt), 0, C.byref(s), None) == -1
     bt.B = 0
     assert step() == 0
+
+
+@pytest.mark.parametrize("sharded", [False, True])
+def test_a_request_is_refused_by_one_rule_on_both_engines(sharded):
+    """TcarEngine._serve and ShardedEngine.serve_pieces normalise (k, panel, window, max_per_category) through ONE method: the same
+    ValueError, word for word, on both classes, before anything of the device is touched (the engines are never built)"""
+    from tcar_amd.engine import TcarEngine
+    from tcar_amd.sharded import ShardedEngine
+    cls = ShardedEngine if sharded else TcarEngine
+    assert cls._serve_request is TcarEngine._serve_request
+    eng = cls.__new__(cls)
+    eng.geo, eng.nl, eng._cat = types.SimpleNamespace(N=700, Npad=768), 700, None
+    width = 768
+    refused = [(dict(k=0), "k must be in [1, 64]"), (dict(k=65), "k must be in [1, 64]"),
+               (dict(panel=100), "panel must be a positive multiple of 128, at most 49152"),
+               (dict(panel=49152 + 128), "panel must be a positive multiple of 128, at most 49152"),
+               (dict(max_per_category=0), "max_per_category must be an int >= 1 (None: no cap)"),
+               (dict(max_per_category=True), "max_per_category must be an int >= 1 (None: no cap)"),
+               (dict(window=(0, 10)), "a window compares item keys: call set_item_keys(keys) first")]
+    for kw, text in refused:
+        req = dict(dict(k=20, panel=None, window=None, max_per_category=None), **kw)
+        with pytest.raises(ValueError) as e:
+            eng._serve_request(req["k"], req["panel"], req["window"], req["max_per_category"], width)
+        assert str(e.value) == text, kw
+    # and what it lets through: the default panel, a named one clipped to the scored width
+    assert eng._serve_request(20, None, None, None, width) == (20, 768, None)
+    assert eng._serve_request(64, 49152, None, None, width) == (64, 768, None)
+    assert eng._serve_request(1, 128, None, None, width) == (1, 128, None)

@@ -1,6 +1,6 @@
 """The exchange of the catalog-sharded streamed selection on CPU, worlds 2 and 3 over gloo: the PRODUCT's collective schedule
 (tcar_amd.sharded.ShardExchange.serve — the same object ShardedEngine drives with the HIP entry points) with numpy / torch pieces built
-on the model of tests/merge_ref.py, against the single-process model of the whole catalog (no GPU, no HIP library: this pins the
+on the model of tests/select_ref.py, against the single-process model of the whole catalog (no GPU, no HIP library: this pins the
 sequencing, the buffer shapes of uneven / empty shards of the batch and a short last shard of the catalog, the label score taken from
 the label's owner, and the algebra of the state merge with windows, exclusions and a cap in the packed rows).
 
@@ -36,7 +36,7 @@ def _worker(rank, world, port, ret, N=300, B=7):
     try:
         import tcar_amd  # noqa: F401
         from tcar_amd.sharded import ShardExchange, shard_rows
-        from merge_ref import finish, fold_state, merge_states
+        from select_ref import finish, fold_state, merge_states
         rng = np.random.RandomState(3)
         ek, k, X = 24, 20, 4
         rw = 2 * k + 4

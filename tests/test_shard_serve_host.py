@@ -11,8 +11,7 @@ import pytest
 import tcar_amd  # noqa: F401
 from tcar_amd import _lib
 
-from merge_ref import finish, fold_state, merge_states, pack_states
-from quota_ref import capped_walk
+from select_ref import capped_walk, finish, fold_state, merge_states, pack_states
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROTOTYPE = r"^((?:const )?\w+\*?) (tcar_\w+)\(([^)]*)\)\s*;"
