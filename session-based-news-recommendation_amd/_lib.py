@@ -45,7 +45,7 @@ def _name(prefix: str, name: str) -> str:
 
 for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER
     globals()[_name(_prefix, "HEADER")] = os.path.join(PKG_DIR, "..", "include", _file)
-HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h")] + \
+HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), os.path.join(CSRC, "topk_rows.h")] + \
     [globals()[_name(_prefix, "HEADER")] for _prefix, _ in ABI_LAYERS]
 _ID_MARK = b"TCAR_BUILD_ID="
 
@@ -61,7 +61,7 @@ def _digest(paths) -> str:
 
 
 def source_build_id() -> str:
-    """Digest of every source the library is compiled from (csrc/*.hip, the two csrc headers, include/*.h) and of the
+    """Digest of every source the library is compiled from (csrc/*.hip, the csrc headers, include/*.h) and of the
     code-generation flags every translation unit must be built with (SAFE_FLAGS): a binary built without them is stale."""
     import hashlib
     base = _digest([os.path.join(CSRC, s) for s in SOURCES] + HEADERS)

@@ -8,6 +8,7 @@
 #include <utility>
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
+#include "topk_rows.h"
 #include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_s;
@@ -1002,8 +1003,8 @@ __global__ __launch_bounds__(256) void dact_colsum_kernel(int M, int ncol, long 
 
 // ---- rank of the label and top-k (util.py:13-17, model_combine.py:301) -----------------------------------
 // One workgroup per session.  rank = 1 + #{n: x[n] > x[label]}.  top-k by k rounds of block-wide arg-max over
-// keys ordered by (score desc, index desc) — the order of np.argsort(x)[::-1]; the row stays in L2 between
-// rounds.
+// keys in the list order (key_gt of topk_rows.h: score desc, index desc — the order of np.argsort(x)[::-1]); the row stays in
+// L2 between rounds.
 __global__ __launch_bounds__(256) void rank_topk_kernel(int N, const float* __restrict__ logits, long ld,
                                                         const int32_t* __restrict__ label, int k,
                                                         int32_t* __restrict__ rank, int32_t* __restrict__ topk) {
@@ -1027,15 +1028,13 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(int N, const float* __re
     int bi = -1;
     for (int i = tid; i < N; i += 256) {
       const float v = row[i];
-      const bool eligible = (v < pv) || (v == pv && i < pi);
-      const bool better = (v > bv) || (v == bv && i > bi);
-      if (eligible && better) { bv = v; bi = i; }
+      if (key_gt(pv, pi, v, i) && key_gt(v, i, bv, bi)) { bv = v; bi = i; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(bv, o);
       const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi > bi)) { bv = ov; bi = oi; }
+      if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     if (lane == 0) { shv[w] = bv; shi[w] = bi; }
     __syncthreads();
@@ -1043,25 +1042,25 @@ __global__ __launch_bounds__(256) void rank_topk_kernel(int N, const float* __re
     int fi = shi[0];
 #pragma unroll
     for (int j = 1; j < 4; ++j)
-      if (shv[j] > fv || (shv[j] == fv && shi[j] > fi)) { fv = shv[j]; fi = shi[j]; }
+      if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; }
     __syncthreads();
     if (tid == 0) topk[(long)b * k + r] = fi;
     pv = fv; pi = fi;
   }
 }
 
-// Row-resident rank / top-k (catalogs up to NT*4*R items): the row is read from memory ONCE into registers.  Every thread
-// caches the best of its own elements under the total order (score desc, index desc); a round is one block-wide arg-max
-// over the cached bests, after which only the WINNER rescans its 4*R elements below the extracted key.  21 passes over a
-// 184-KB row (1.34 ms per launch at B = 512, N = 46,033) become one read + k cheap rounds.
+// Row-resident rank / top-k / CE (catalogs up to NT*4*R items): the row is read from memory ONCE into registers — 21 passes over a
+// 184-KB row (1.34 ms per launch at B = 512, N = 46,033) become one read + k cheap rounds.  The statistics are this kernel's own;
+// after them the padding columns die as NaN and the list is the shared core's (topk_rows.h) with no extra entry and n0 = 0, which
+// select_panel_kernel (select.hip) folds panels with.  Rounds past the last item deliver the "nothing" key: topk ends in -1.
 template <int NT, int R>
 __global__ __launch_bounds__(NT) void rank_topk_rows_kernel(int N, const float* __restrict__ logits, long ld,
                                                             const int32_t* __restrict__ label, int k,
                                                             int32_t* __restrict__ rank, int32_t* __restrict__ topk,
                                                             float* __restrict__ ce) {
   constexpr int NWV = NT / 64;
+  __shared__ TopkShared<NT> sh;
   __shared__ float shv[NWV];
-  __shared__ int shi[NWV];
   __shared__ float shs[NWV];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* row = logits + (long)b * ld;
@@ -1107,102 +1106,27 @@ __global__ __launch_bounds__(NT) void rank_topk_rows_kernel(int N, const float* 
     if (tid == 0) ce[b] = gm + logf(gs) - xl;
     __syncthreads();
   }
-  // best of this thread's elements strictly below the key (pv, pi) in the order (score desc, index desc)
-  auto scan = [&](float pv, int pi, float& bv, int& bi) {
-    bv = ninf; bi = -1;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int c = (tid + r * NT) * 4;
-      const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = c + j;
-        const bool eligible = (e[j] < pv) || (e[j] == pv && i < pi);
-        const bool better = (e[j] > bv) || (e[j] == bv && i > bi);
-        if (i < N && eligible && better) { bv = e[j]; bi = i; }
-      }
-    }
-  };
-  float cbv;
-  int cbi;
-  scan(INFINITY, N, cbv, cbi);
-  const int kk = k < N ? k : N;
-  // block-wide arg-max of one (value, index) key per thread under (score desc, index desc); result to every thread
-  auto block_best = [&](float bv, int bi, float& fv, int& fi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (ov > bv || (ov == bv && oi > bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { shv[w] = bv; shi[w] = bi; }
-    __syncthreads();
-    fv = shv[0]; fi = shi[0];
-#pragma unroll
-    for (int j = 1; j < NWV; ++j)
-      if (shv[j] > fv || (shv[j] == fv && shi[j] > fi)) { fv = shv[j]; fi = shi[j]; }
-    __syncthreads();
-  };
-  // Phase A: the kk-th largest of the per-thread bests, L.  At least kk elements are >= L, so the whole top-kk is.
-  float lv = INFINITY;
-  int li = N;
-  {
-    float av = cbv;
-    int ai = cbi;
-    for (int r = 0; r < kk; ++r) {
-      float fv; int fi;
-      block_best(av, ai, fv, fi);
-      if (fi < 0) { lv = ninf; li = -1; break; }        // fewer than kk threads hold anything: every element qualifies
-      lv = fv; li = fi;
-      if (ai == fi) { av = ninf; ai = -1; }
-    }
-  }
-  // Phase B: compact the elements >= L into LDS
-  constexpr int CAP = 2 * NT;
-  __shared__ float candv[CAP];
-  __shared__ int candi[CAP];
-  __shared__ int ncand;
-  if (tid == 0) ncand = 0;
-  __syncthreads();
+  // ---- from here on the registers hold CANDIDATES: the padding columns die
+  // (The 4 R comparisons are made AGAIN, against an opaque copy of N.  Against N itself they are the comparisons of the statistics:
+  //  the compiler keeps their 4 R masks alive across the sums, and the unmasked slice beside the masked one — NaN needs only the
+  //  former —, which spilled 28 bytes per lane at R = 24.)
+  const float dead = __builtin_nanf("");
+  int nl = N;
+  asm volatile("" : "+s"(nl));
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int c = (tid + r * NT) * 4;
-    const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = c + j;
-      if (i < N && (e[j] > lv || (e[j] == lv && i >= li))) {
-        const int pos = atomicAdd(&ncand, 1);
-        if (pos < CAP) { candv[pos] = e[j]; candi[pos] = i; }
-      }
-    }
+    if (c + 0 >= nl) v[r].x = dead;
+    if (c + 1 >= nl) v[r].y = dead;
+    if (c + 2 >= nl) v[r].z = dead;
+    if (c + 3 >= nl) v[r].w = dead;
   }
-  __syncthreads();
-  const int nc = ncand;
-  if (nc <= CAP) {
-    // Phase C: kk rounds over <= 2 candidates per thread
-    float c0v = tid < nc ? candv[tid] : ninf, c1v = tid + NT < nc ? candv[tid + NT] : ninf;
-    int c0i = tid < nc ? candi[tid] : -1, c1i = tid + NT < nc ? candi[tid + NT] : -1;
-    for (int r = 0; r < k; ++r) {
-      if (r >= kk) { if (tid == 0) topk[(long)b * k + r] = -1; continue; }
-      const bool first = (c0v > c1v) || (c0v == c1v && c0i > c1i);
-      float fv; int fi;
-      block_best(first ? c0v : c1v, first ? c0i : c1i, fv, fi);
-      if (tid == 0) topk[(long)b * k + r] = fi;
-      if (c0i == fi) { c0v = ninf; c0i = -1; }
-      if (c1i == fi) { c1v = ninf; c1i = -1; }
-    }
-    return;
-  }
-  // Fallback (more than CAP elements tie with or exceed L, e.g. a constant row): extract one element per round; only the
-  // owner of the extracted element rescans its registers
-  for (int r = 0; r < k; ++r) {
-    if (r >= kk) { if (tid == 0) topk[(long)b * k + r] = -1; continue; }
-    float fv; int fi;
-    block_best(cbv, cbi, fv, fi);
+  float sv = dead;                  // no extra entry
+  int si = KEY_NONE_I;
+  TopkRows<NT, R> core{sh, v, sv, si, 0, tid};
+  core.topk(k, false, [&](int r, float, int fi) __attribute__((always_inline)) {
     if (tid == 0) topk[(long)b * k + r] = fi;
-    if (fi >= 0 && ((fi >> 2) % NT) == tid) scan(fv, fi, cbv, cbi);
-  }
+  });
 }
 
 }  // namespace
@@ -1475,13 +1399,13 @@ extern "C" int tcar_eval_rows(int B, int N, const float* logits, int64_t ld, con
                               int32_t* topk, float* ce, void* stream) {
   if (B <= 0) return TCAR_OK;
   if (N <= 0 || k < 0 || ld < N || !logits || !label || !rank || (k > 0 && !topk)) return TCAR_E_ARG;
-  if ((ld & 3) == 0 && tcar_aligned16(logits) && ld <= 512L * 4 * 24) {
-    if (ld <= 512L * 4 * 8)
-      TCAR_LAUNCH((rank_topk_rows_kernel<512, 8>), dim3(B), dim3(512), 0, (hipStream_t)stream, N, logits, (long)ld, label, k,
-                  rank, topk, ce);
+  if ((ld & 3) == 0 && tcar_aligned16(logits) && ld <= topk_cols(TOPK_R_WIDE)) {
+    if (ld <= topk_cols(TOPK_R_MID))
+      TCAR_LAUNCH((rank_topk_rows_kernel<TOPK_NT, TOPK_R_MID>), dim3(B), dim3(TOPK_NT), 0, (hipStream_t)stream, N, logits, (long)ld,
+                  label, k, rank, topk, ce);
     else
-      TCAR_LAUNCH((rank_topk_rows_kernel<512, 24>), dim3(B), dim3(512), 0, (hipStream_t)stream, N, logits, (long)ld, label, k,
-                  rank, topk, ce);
+      TCAR_LAUNCH((rank_topk_rows_kernel<TOPK_NT, TOPK_R_WIDE>), dim3(B), dim3(TOPK_NT), 0, (hipStream_t)stream, N, logits, (long)ld,
+                  label, k, rank, topk, ce);
     TCAR_CHECK_LAUNCH();
     return TCAR_OK;
   }

@@ -2,16 +2,15 @@
 // state per session — the k best (score, index) entries so far in list order, the count of scores strictly above the label's, and the
 // online softmax pair (max, sum exp) — and one finishing launch turns the state into top-k / rank / cross entropy.  No [B, N] matrix.
 //
-// List order: score descending, then index descending (np.argsort(x)[::-1], rank_topk_rows_kernel of score.hip).  It is a TOTAL order
+// List order: score descending, then index descending (np.argsort(x)[::-1]; key_gt of topk_rows.h).  It is a TOTAL order
 // over (score, item id), and a fold computes the exact k best of (state entries + panel columns) under it, so the list after the last
 // panel is the k best of the catalog whatever the partition and whatever order candidates arrive in LDS.
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
+#include "topk_rows.h"
 #include "../../include/tcar_serve_shard.h"
 
 namespace {
-
-constexpr int SEL_NT = 512;             // threads of a fold workgroup
 
 // state row of one session, 2k + 4 words: score[k] | index[k] (-1: empty) | count, max, sum, pad
 __host__ __device__ inline int sel_row_words(int k) { return 2 * k + 4; }
@@ -28,11 +27,9 @@ __global__ __launch_bounds__(256) void select_reset_kernel(int B, int k, float* 
   }
 }
 
-// key order: a above b?
-__device__ __forceinline__ bool key_gt(float av, int ai, float bv, int bi) { return av > bv || (av == bv && ai > bi); }
-
-// One workgroup per session.  The row slice is read ONCE into registers (as in rank_topk_rows_kernel<512, R>); columns outside the
-// slice and excluded items become NaN after the statistics: a NaN compares false with everything, so it is never a candidate.
+// One workgroup per session.  The row slice is read ONCE into registers; columns outside the slice and excluded items become NaN after
+// the statistics: a NaN compares false with everything, so it is never a candidate.  The extraction is the core of topk_rows.h, which
+// rank_topk_rows_kernel (score.hip) shares.
 //
 // W (include/tcar_window.h): item n0 + j is in the POOL of session b iff wlo[b] <= key[n0 + j] < whi[b], or it is the label of a
 // labelled call.  Columns out of the pool do not exist: -inf in the statistics (no count, no max, exp = 0; a NaN would poison the
@@ -42,20 +39,18 @@ __device__ __forceinline__ bool key_gt(float av, int ai, float bv, int bi) { ret
 // Q (include/tcar_quota.h): at most `cap` entries of one category in the list.  The statistics are the shared code above the
 // extraction; only the extraction differs (the capped walk at the end of the kernel).  Q = false compiles none of it.
 template <int R, bool W = false, bool Q = false>
-__global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int k,
+__global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int k,
                                                               const int32_t* __restrict__ label, const float* __restrict__ lab_score,
                                                               const int32_t* __restrict__ excl, int X, float* __restrict__ state,
                                                               const int32_t* __restrict__ key, const int32_t* __restrict__ wlo,
                                                               const int32_t* __restrict__ whi, const int32_t* __restrict__ cat,
                                                               int cap) {
-  constexpr int NT = SEL_NT, NWV = NT / 64, CAP = 2 * NT;
-  __shared__ float shv[NWV];
+  constexpr int NT = TOPK_NT, NWV = NT / 64;
+  __shared__ TopkShared<NT> sh;
+  __shared__ float shv[NWV];        // the statistics' per-wave partials: max, count, "any column in the pool", sum exp
+  __shared__ int shc[NWV];
   __shared__ int shi[NWV];
   __shared__ float shs[NWV];
-  __shared__ int shc[NWV];
-  __shared__ float candv[CAP];
-  __shared__ int candi[CAP];
-  __shared__ int ncand;
   __shared__ int any_excl;
   __shared__ unsigned exb[SEL_MAX_N / 32];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -217,114 +212,22 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
     if (c + 2 >= n || (bits & 4u)) v[r].z = dead;
     if (c + 3 >= n || (bits & 8u)) v[r].w = dead;
   }
-  // best of this thread's candidates (its columns + its state entry) strictly below the key (pv, pi)
-  auto scan = [&](float pv, int pi, float& bv, int& bi) __attribute__((always_inline)) {
-    bv = ninf; bi = -1;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int c = n0 + (tid + r * NT) * 4;
-      const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = c + j;
-        if (key_gt(pv, pi, e[j], i) && key_gt(e[j], i, bv, bi)) { bv = e[j]; bi = i; }
-      }
-    }
-    if (key_gt(pv, pi, sv, si) && key_gt(sv, si, bv, bi)) { bv = sv; bi = si; }
-  };
-  // block-wide arg-max of one key per thread; (-inf, -1) = nothing.  Result to every thread.
-  auto block_best = [&](float bv, int bi, float& fv, int& fi) __attribute__((always_inline)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o);
-      if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { shv[w] = bv; shi[w] = bi; }
-    __syncthreads();
-    fv = shv[0]; fi = shi[0];
-#pragma unroll
-    for (int j = 1; j < NWV; ++j)
-      if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; }
-    __syncthreads();
-  };
-  // block_best with a payload (Q: the category of the key)
-  auto block_best_c = [&](float bv, int bi, int bc, float& fv, int& fi, int& fc) __attribute__((always_inline)) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o);
-      const int oi = __shfl_xor(bi, o), oc = __shfl_xor(bc, o);
-      if (key_gt(ov, oi, bv, bi)) { bv = ov; bi = oi; bc = oc; }
-    }
-    if (lane == 0) { shv[w] = bv; shi[w] = bi; shc[w] = bc; }
-    __syncthreads();
-    fv = shv[0]; fi = shi[0]; fc = shc[0];
-#pragma unroll
-    for (int j = 1; j < NWV; ++j)
-      if (key_gt(shv[j], shi[j], fv, fi)) { fv = shv[j]; fi = shi[j]; fc = shc[j]; }
-    __syncthreads();
-  };
-  // Threshold L = (lv, li): at least k candidates are at or above it, so the k best are.  A full list gives one for free (its last
-  // entry: the k entries themselves are at or above it); else — or when too many columns pass it — the k-th largest of the
-  // per-thread bests (phase A of rank_topk_rows_kernel).
-  float lv = lastv;
-  int li = lasti;
-  float cbv = ninf;
-  int cbi = -1;
-  bool scanned = false;
-  auto phase_a = [&]() __attribute__((always_inline)) {
-    scan(INFINITY, 0x7fffffff, cbv, cbi);
-    scanned = true;
-    float av = cbv;
-    int ai = cbi;
-    lv = ninf; li = -1;
-    for (int r = 0; r < k; ++r) {
-      float fv; int fi;
-      block_best(av, ai, fv, fi);
-      if (fi < 0) { lv = ninf; li = -1; break; }        // fewer than k threads hold anything: every candidate qualifies
-      lv = fv; li = fi;
-      if (ai == fi) { av = ninf; ai = -1; }
-    }
-  };
-  auto compact = [&]() __attribute__((always_inline)) -> int {
-    if (tid == 0) ncand = 0;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      const int c = n0 + (tid + r * NT) * 4;
-      const float e[4] = {v[r].x, v[r].y, v[r].z, v[r].w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int i = c + j;
-        if (e[j] > lv || (e[j] == lv && i >= li)) {
-          const int pos = atomicAdd(&ncand, 1);
-          if (pos < CAP) { candv[pos] = e[j]; candi[pos] = i; }
-        }
-      }
-    }
-    if (sv > lv || (sv == lv && si >= li)) {
-      const int pos = atomicAdd(&ncand, 1);
-      if (pos < CAP) { candv[pos] = sv; candi[pos] = si; }
-    }
-    __syncthreads();
-    const int nc = ncand;
-    __syncthreads();
-    return nc;
-  };
-  if (!full) phase_a();
-  int nc = compact();
-  if (nc > CAP && full) {
-    phase_a();
-    nc = compact();
-  }
-  if constexpr (Q) {
+  // ---- the k best of (columns + state entries) under the list order: the shared core (topk_rows.h).  A full list gives the threshold
+  // for free (its last entry: the k entries themselves are at or above it), so a panel that cannot improve the list costs one compaction.
+  TopkRows<NT, R> core{sh, v, sv, si, n0, tid, lastv, lasti};
+  if constexpr (!Q) {
+    core.topk(k, full, [&](int r, float fv, int fi) __attribute__((always_inline)) {
+      if (tid == 0) { st[r] = fv; sti[k + r] = fi; }
+    });
+  } else {
+    const int nc = core.candidates(k, full);
     // ---- the capped walk (include/tcar_quota.h): candidates in list order, one taken iff fewer than `cap` of its category are.
     // Lane j of EVERY wave keeps the category of list entry j (`mycat`), so "how many of category c are taken" is one ballot and the
     // decision is uniform over the workgroup.  When a category reaches the cap its remaining candidates can be KILLED, after which
     // every extracted best is acceptable: the number of block-wide rounds of a fold is bounded by k alone, never by n.
-    //   stage 1: the candidates at or above L, from LDS (<= 2 per thread, their categories in registers)
+    //   stage 1: the candidates at or above L, from LDS (the core's phase C; the category is the payload of the arg-max)
     //   stage 2: when those run dry before k are taken (L only bounds the UNCAPPED k best) or do not fit the LDS: everything strictly
-    //            below the last key walked, from the registers, one entry per round as in the fallback of the uncapped kernel
+    //            below the last key walked, from the registers, one entry per round as in the core's fallback
     //            (kills there cost a pass over the category slice, so they are put off: see below)
     const int32_t* cp = cat + n0;
     const bool cal = (reinterpret_cast<uintptr_t>(cp) & 15) == 0;
@@ -335,22 +238,16 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
       ++taken;
       return __popcll(__ballot(lane < taken && mycat == fc)) >= cap;
     };
-    float pv = INFINITY;              // everything not walked yet is strictly below the key (pv, pi)
-    int pi = 0x7fffffff;
-    if (nc <= CAP) {
-      float c0v = tid < nc ? candv[tid] : ninf, c1v = tid + NT < nc ? candv[tid + NT] : ninf;
-      int c0i = tid < nc ? candi[tid] : -1, c1i = tid + NT < nc ? candi[tid + NT] : -1;
-      const int c0c = c0i >= 0 ? cat[c0i] : 0, c1c = c1i >= 0 ? cat[c1i] : 0;
-      while (taken < k) {
-        const bool first = key_gt(c0v, c0i, c1v, c1i);
-        float fv; int fi, fc;
-        block_best_c(first ? c0v : c1v, first ? c0i : c1i, first ? c0c : c1c, fv, fi, fc);
-        if (fi < 0) break;
-        const bool sat = accept(fv, fi, fc);
-        if (c0i == fi || (sat && c0c == fc)) { c0v = ninf; c0i = -1; }
-        if (c1i == fi || (sat && c1c == fc)) { c1v = ninf; c1i = -1; }
-      }
-      pv = lv; pi = li;               // what is left lies strictly below L; L = (-inf, -1): nothing is
+    float pv = KEY_ALL_V;             // everything not walked yet is strictly below the key (pv, pi)
+    int pi = KEY_ALL_I;
+    if (nc <= core.CAP) {
+      core.template extract_lds<true>(
+          nc, k, [&](int i) __attribute__((always_inline)) { return cat[i]; },
+          [&](int, float fv, int fi, int fc) __attribute__((always_inline)) -> int {
+            if (fi < 0) return TOPK_STOP;
+            return accept(fv, fi, fc) ? TOPK_KILL : TOPK_NEXT;
+          });
+      pv = core.lv; pi = core.li;     // what is left lies strictly below L; L = (-inf, -1): nothing is
     }
     if (taken < k && pi >= 0) {
       // columns (and the state entry) of category kc die; `hit`: the thread's current best was one of them
@@ -366,29 +263,29 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
             int4 q;
             if (cal && c + 3 < n) q = *reinterpret_cast<const int4*>(cp + c);
             else { const int last = n - 1; q = make_int4(cp[min(c, last)], cp[min(c + 1, last)], cp[min(c + 2, last)], cp[min(c + 3, last)]); }
-            if (q.x == kc) { v[r].x = dead; hit |= n0 + c + 0 == cbi; }
-            if (q.y == kc) { v[r].y = dead; hit |= n0 + c + 1 == cbi; }
-            if (q.z == kc) { v[r].z = dead; hit |= n0 + c + 2 == cbi; }
-            if (q.w == kc) { v[r].w = dead; hit |= n0 + c + 3 == cbi; }
+            if (q.x == kc) { v[r].x = dead; hit |= n0 + c + 0 == core.cbi; }
+            if (q.y == kc) { v[r].y = dead; hit |= n0 + c + 1 == core.cbi; }
+            if (q.z == kc) { v[r].z = dead; hit |= n0 + c + 2 == core.cbi; }
+            if (q.w == kc) { v[r].w = dead; hit |= n0 + c + 3 == core.cbi; }
           }
           if ((r & 3) == 3) __builtin_amdgcn_sched_barrier(0);     // four category loads in flight, not 4 R registers of them
         }
-        if (si >= 0 && sc == kc) { hit |= si == cbi; sv = dead; si = -1; }
+        if (si >= 0 && sc == kc) { hit |= si == core.cbi; sv = dead; si = -1; }
       };
       // A kill pass reads the whole category slice, so stage 2 starts LAZY: the categories that are full keep their columns, and an
       // extracted best of such a category is rejected (one wasted round; its owner rescans).  Typically a handful of entries are
       // missing and the next bests are acceptable.  After k rejected rounds the fold stops being lazy: every full category is killed,
       // one pass each (at most k / cap of them, now and later), and from then on every extracted best is acceptable again.  So
       // stage 2 spends at most k accepting and k + 1 rejecting rounds whatever the slice holds.
-      scan(pv, pi, cbv, cbi);
+      core.scan(pv, pi);
       bool lazy = true;
       int rejected = 0;
       while (taken < k) {
         float fv; int fi;
-        block_best(cbv, cbi, fv, fi);
+        core.best(core.cbv, core.cbi, fv, fi);
         if (fi < 0) break;
         const int fc = cat[__builtin_amdgcn_readfirstlane(fi)];
-        hit = cbi == fi;
+        hit = core.cbi == fi;
         int j0 = 0, j1 = 0;                     // list entries whose category is to be killed now, if it is full
         bool one = false;
         if (lazy && __popcll(__ballot(lane < taken && mycat == fc)) >= cap) {
@@ -403,34 +300,10 @@ __global__ __launch_bounds__(SEL_NT) void select_panel_kernel(int n0, int n, con
           const bool same = mycat == cj;
           if ((one || __ballot(lane < j && same) == 0) && __popcll(__ballot(lane < taken && same)) >= cap) kill_pass(cj);
         }
-        if (hit) scan(fv, fi, cbv, cbi);
+        if (hit) core.scan(fv, fi);
       }
     }
     if (tid >= taken && tid < k) { st[tid] = ninf; sti[k + tid] = -1; }
-    return;
-  }
-  if (nc <= CAP) {
-    // k rounds over <= 2 candidates per thread
-    float c0v = tid < nc ? candv[tid] : ninf, c1v = tid + NT < nc ? candv[tid + NT] : ninf;
-    int c0i = tid < nc ? candi[tid] : -1, c1i = tid + NT < nc ? candi[tid + NT] : -1;
-    for (int r = 0; r < k; ++r) {
-      const bool first = key_gt(c0v, c0i, c1v, c1i);
-      float fv; int fi;
-      block_best(first ? c0v : c1v, first ? c0i : c1i, fv, fi);
-      if (tid == 0) { st[r] = fv; sti[k + r] = fi; }
-      if (c0i == fi) { c0v = ninf; c0i = -1; }
-      if (c1i == fi) { c1v = ninf; c1i = -1; }
-    }
-    return;
-  }
-  // Fallback (more than CAP candidates tie with or exceed L, e.g. a constant row): one entry per round; only the owner of the
-  // extracted entry rescans its registers
-  if (!scanned) scan(INFINITY, 0x7fffffff, cbv, cbi);
-  for (int r = 0; r < k; ++r) {
-    float fv; int fi;
-    block_best(cbv, cbi, fv, fi);
-    if (tid == 0) { st[r] = fv; sti[k + r] = fi; }
-    if (fi >= 0 && cbi == fi) scan(fv, fi, cbv, cbi);
   }
 }
 
@@ -563,18 +436,20 @@ __global__ __launch_bounds__(64) void label_score_bf16_kernel(int N, int K, cons
 
 // a cap goes with a category table (then >= 1), and with nothing else
 inline bool bad_quota(const int32_t* cat, int cap) { return cat ? cap < 1 : cap != 0; }
+// the (B, k) every entry point of the streamed selection takes
+inline bool bad_bk(int B, int k) { return B < 0 || k < 1 || k > SEL_MAX_K; }
 
 }  // namespace
 
 extern "C" int tcar_serve_abi_version(void) { return TCAR_SERVE_ABI_VERSION; }
 
 extern "C" int64_t tcar_select_state_bytes(int B, int k) {
-  if (B < 0 || k < 1 || k > SEL_MAX_K) return -1;
+  if (bad_bk(B, k)) return -1;
   return (int64_t)B * sel_row_words(k) * 4;
 }
 
 extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) {
-  if (B < 0 || k < 1 || k > SEL_MAX_K) return TCAR_E_ARG;
+  if (bad_bk(B, k)) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;
   if (!state || ((uintptr_t)state & 3)) return TCAR_E_ARG;
   long blocks = ((long)B * sel_row_words(k) + 255) / 256;
@@ -593,26 +468,22 @@ extern "C" int tcar_select_panel_quota(int B, int n0, int n, const float* panel,
                                        const int32_t* key, const int32_t* lo, const int32_t* hi, const int32_t* cat, int cap) {
   if (bad_quota(cat, cap)) return TCAR_E_ARG;
   if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
-  if (B < 0 || k < 1 || k > SEL_MAX_K || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
+  if (bad_bk(B, k) || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
   if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
   if (B == 0 || n == 0) return TCAR_OK;
   if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  float* st = (float*)state;
+  // the kernel: [rung of the R ladder that holds n columns][windowed][capped]
+  static constexpr decltype(&select_panel_kernel<2>) fold[3][2][2] = {
+      {{select_panel_kernel<TOPK_R_SMALL, false, false>, select_panel_kernel<TOPK_R_SMALL, false, true>},
+       {select_panel_kernel<TOPK_R_SMALL, true, false>, select_panel_kernel<TOPK_R_SMALL, true, true>}},
+      {{select_panel_kernel<TOPK_R_MID, false, false>, select_panel_kernel<TOPK_R_MID, false, true>},
+       {select_panel_kernel<TOPK_R_MID, true, false>, select_panel_kernel<TOPK_R_MID, true, true>}},
+      {{select_panel_kernel<TOPK_R_WIDE, false, false>, select_panel_kernel<TOPK_R_WIDE, false, true>},
+       {select_panel_kernel<TOPK_R_WIDE, true, false>, select_panel_kernel<TOPK_R_WIDE, true, true>}}};
+  const int rung = n <= topk_cols(TOPK_R_SMALL) ? 0 : n <= topk_cols(TOPK_R_MID) ? 1 : 2;
   const bool capped = cat && cap < k;
-#define SEL_FOLD(R, W, Q)                                                                                                         \
-  TCAR_LAUNCH((select_panel_kernel<R, W, Q>), dim3(B), dim3(SEL_NT), 0, s, n0, n, panel, (long)ld, k, label, lab_score, excl, X, st, key, \
-              lo, hi, cat, cap)
-#define SEL_FOLD_R(R)                                            \
-  do {                                                           \
-    if (capped) { if (key) SEL_FOLD(R, true, true); else SEL_FOLD(R, false, true); } \
-    else { if (key) SEL_FOLD(R, true, false); else SEL_FOLD(R, false, false); }      \
-  } while (0)
-  if (n <= SEL_NT * 4 * 2) SEL_FOLD_R(2);
-  else if (n <= SEL_NT * 4 * 8) SEL_FOLD_R(8);
-  else SEL_FOLD_R(24);
-#undef SEL_FOLD_R
-#undef SEL_FOLD
+  TCAR_LAUNCH(fold[rung][key != nullptr][capped], dim3(B), dim3(TOPK_NT), 0, (hipStream_t)stream, n0, n, panel, (long)ld, k, label,
+              lab_score, excl, X, (float*)state, key, lo, hi, cat, cap);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
 }
@@ -630,7 +501,7 @@ extern "C" int tcar_select_panel(int B, int n0, int n, const float* panel, int64
 
 extern "C" int tcar_select_finish(int B, int k, const void* state, const float* lab_score, int32_t* topk, float* score, int32_t* rank,
                                   float* ce, void* stream) {
-  if (B < 0 || k < 1 || k > SEL_MAX_K || (ce && !lab_score)) return TCAR_E_ARG;
+  if (bad_bk(B, k) || (ce && !lab_score)) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;
   if (!state || !topk) return TCAR_E_ARG;
   TCAR_LAUNCH(select_finish_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, k, (const float*)state, lab_score, topk, score, rank, ce);
@@ -643,7 +514,7 @@ extern "C" int tcar_serve_shard_abi_version(void) { return TCAR_SERVE_SHARD_ABI_
 extern "C" int tcar_select_merge(int B, int k, int S, const void* states, int64_t stride_words, void* out, const int32_t* cat, int cap,
                                  void* stream) {
   if (bad_quota(cat, cap)) return TCAR_E_ARG;
-  if (B < 0 || k < 1 || k > SEL_MAX_K || S < 1 || S > 64) return TCAR_E_ARG;
+  if (bad_bk(B, k) || S < 1 || S > 64) return TCAR_E_ARG;
   const int64_t rows = (int64_t)B * sel_row_words(k);
   if (S > 1 && stride_words < rows) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;

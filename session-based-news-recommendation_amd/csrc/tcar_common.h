@@ -25,8 +25,14 @@
 
 static inline bool tcar_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Sizes of the row-resident top-k (topk_rows.h): a workgroup of TOPK_NT threads keeps a row slice in registers, R float4 per thread.
+// The launchers pick the smallest rung of the R ladder that holds the row: tcar_eval_rows (score.hip) from 8 and 24 by ld, the fold
+// (select.hip) from 2, 8 and 24 by n; tcar_eval_step (step.hip) takes the row-resident kernel up to the widest rung.
+constexpr int TOPK_NT = 512;
+constexpr int TOPK_R_SMALL = 2, TOPK_R_MID = 8, TOPK_R_WIDE = 24;
+constexpr int topk_cols(int R) { return TOPK_NT * 4 * R; }
 // Limits of the streamed selection (select.hip), which the serve entry points of step.hip check too
-constexpr int SEL_MAX_N = 512 * 4 * 24;  // columns of a fold (row slice in registers: 24 float4 per thread)
+constexpr int SEL_MAX_N = topk_cols(TOPK_R_WIDE);  // columns of a fold: 49,152
 constexpr int SEL_MAX_K = 64;
 
 // One-time, per-DEVICE kernel attributes (hipFuncSetAttribute for > 64 KB of dynamic LDS).  One bit per device ordinal:
