@@ -4,6 +4,7 @@
 // tcar_eval_step == sess.run([softmax_input, cross_loss]) + util.cau_metrics + top-k (model_combine.py:283,296,301).
 #include "tcar_common.h"
 #include "../../include/tcar_serve_shard.h"
+#include "../../include/tcar_cand.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1320,6 +1321,27 @@ extern "C" int tcar_serve_step_window(const tcar_ctx_t* c, const tcar_batch_t* b
 
 extern "C" int tcar_serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s, void* stream) {
   return tcar_serve_step_quota(c, bt, refresh_time, s, nullptr, nullptr, stream);
+}
+
+// Candidate-list scoring (include/tcar_cand.h): the head of a forward pass as tcar_serve_step_quota runs it, then the [B, C] gathered
+// dots from the operands the panel GEMM would contract and, when the descriptor asks for any of them, the ranks and metrics.
+extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_cand_t* d, void* stream) {
+  if (!c || !bt || bt->B < 0 || !d) return TCAR_E_ARG;
+  if (d->C < 1 || d->C > CAND_MAX_C || d->ld_cand < d->C || !d->cand || !d->score) return TCAR_E_ARG;
+  if (!d->clicked && (d->counts || d->metrics)) return TCAR_E_ARG;
+  if (bt->B == 0) return TCAR_OK;
+  RET(check_ctx(c, bt));
+  if (c->scoring ? (!c->a16h || !c->e16h || (c->scoring == 3 && (!c->a16l || !c->e16l))) : !c->attout) return TCAR_E_ARG;
+  const Geo g(c->d);
+  const int B = bt->B, C = d->C;
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
+  RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
+                       c->scoring, d->cand, d->ld_cand, d->score, C, stream));
+  if (!d->rank_of && !d->order && !d->counts && !d->metrics) return TCAR_OK;
+  return tcar_cand_rank(B, C, d->score, C, d->cand, d->ld_cand, d->clicked, d->ld_cand, d->rank_of, d->order, d->counts, d->metrics,
+                        stream);
 }
 
 

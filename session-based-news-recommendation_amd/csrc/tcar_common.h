@@ -34,6 +34,8 @@ constexpr int topk_cols(int R) { return TOPK_NT * 4 * R; }
 // Limits of the streamed selection (select.hip), which the serve entry points of step.hip check too
 constexpr int SEL_MAX_N = topk_cols(TOPK_R_WIDE);  // columns of a fold: 49,152
 constexpr int SEL_MAX_K = 64;
+// Slots of one candidate list (cand.hip; include/tcar_cand.h): the ranking kernel keeps a list's scores and ids in LDS
+constexpr int CAND_MAX_C = 1024;
 
 // One-time, per-DEVICE kernel attributes (hipFuncSetAttribute for > 64 KB of dynamic LDS).  One bit per device ordinal:
 // correct with several devices in one process and safe from several host threads (two threads may both set the

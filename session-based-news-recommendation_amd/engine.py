@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Dims, Grads, Segments, Quota, Serve, Tables, Window, check
+from ._lib import Batch, Cand, Dims, Grads, Segments, Quota, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -1036,3 +1036,79 @@ class TcarEngine(OpLevelStep):
         bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
         _, topk, _, scores = self._serve(bt, k, panel, excl, False, window, max_per_category)
         return topk, scores
+
+    # ---- candidate-list scoring (include/tcar_cand.h): only the rows a session names are read
+    CAND_MAX_C = 1024              # slots of one list (CAND_MAX_C of csrc/tcar_common.h)
+
+    @staticmethod
+    def _cand_request(B: int, candidates, clicked):
+        """The request of a score_candidates call, validated before anything is launched -> (cand, clicked): contiguous int32 host
+        arrays [B, C] (clicked: None when the call has none)."""
+        def ints(x, what):
+            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            if not np.issubdtype(x.dtype, np.integer):
+                raise ValueError("%s must be an integer array" % what)
+            return x
+        cand = ints(candidates, "candidates")
+        if cand.ndim != 2 or cand.shape[0] != B:
+            raise ValueError("candidates must be [B, C] with B = %d sessions" % B)
+        if not 1 <= cand.shape[1] <= TcarEngine.CAND_MAX_C:
+            raise ValueError("C must be in [1, %d]" % TcarEngine.CAND_MAX_C)
+        # (ids beyond int32 cannot be catalog items: they become empty slots like every id outside [0, N))
+        c64 = cand.astype(np.int64)
+        cand = np.ascontiguousarray(np.where((c64 < 0) | (c64 >= 2 ** 31), -1, c64), dtype=np.int32)
+        if clicked is not None:
+            clicked = ints(clicked, "clicked")
+            if clicked.shape != cand.shape:
+                raise ValueError("clicked must have the shape of candidates, [%d, %d]" % cand.shape)
+            clicked = np.ascontiguousarray(clicked != 0, dtype=np.int32)
+        return cand, clicked
+
+    def score_candidates(self, batch, candidates, clicked=None, bt: Optional[Batch] = None) -> "CandResult":
+        """Score and rank the C items every session names: candidates int [B, C], 0-based ids, -1 (any id outside the catalog) = an
+        empty slot, repeats allowed.  One tcar_cand_step: the session forward, then B C gathered dots — no [B, N] matrix, no panel;
+        `batch` needs no "label" and no "neg".  Returns CandResult(scores [B, C] f32 (-inf in empty slots), rank_of [B, C] int32
+        (1-based, 0 = empty), order [B, C] int32 (slots best first, -1 behind the last), counts, metrics): views of the workspace,
+        valid until the next call.  List order: score, then item id, descending, then slot ascending.  With clicked int [B, C]
+        (0 / 1): counts [B, 3] int32 = (npos, nneg, auc2) and metrics [B, 3] f32 = (mrr, ndcg5, ndcg10) over each list's non-empty
+        slots (host.metrics.impression_metrics divides); without: None."""
+        if self.shard != (0, self.geo.N):
+            raise _lib.TcarError("candidate scoring needs the whole catalog on one engine (no shard)")
+        if bt is None:
+            if "label" not in batch:
+                batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
+            batch = {n: v for n, v in batch.items() if n != "neg"}
+        B = bt.B if bt is not None else int(np.asarray(batch["seq"]).shape[0])
+        cand, clk = self._cand_request(B, candidates, clicked)
+        self.flush()
+        bt = self._without_neg(bt if bt is not None else self.upload(batch), label=False)
+        C_ = cand.shape[1]
+        self._ensure_work(B, bt.T)
+        wb = self.work_B
+        # cand and clicked are the two planes of ONE workspace entry: they go up in one copy
+        self.ws.ensure([Spec("cand_in", (2, wb, C_), I32), Spec("cand_score", (wb, C_), F32), Spec("cand_rank", (2, wb, C_), I32),
+                        Spec("cand_counts", (wb, 3), I32), Spec("cand_metrics", (wb, 3), F32)])
+        if clk is None:
+            self.cand_in[0, :B].copy_(torch.from_numpy(cand))
+        else:
+            self.cand_in[:, :B].copy_(torch.from_numpy(np.stack([cand, clk])))
+        d = Cand()
+        d.C, d.cand, d.ld_cand = C_, self.cand_in[0].data_ptr(), C_
+        d.score, d.rank_of, d.order = self.cand_score.data_ptr(), self.cand_rank[0].data_ptr(), self.cand_rank[1].data_ptr()
+        if clk is not None:
+            d.clicked, d.counts, d.metrics = self.cand_in[1].data_ptr(), self.cand_counts.data_ptr(), self.cand_metrics.data_ptr()
+        check(self.lib.tcar_cand_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), self._stream()),
+              "tcar_cand_step")
+        self._time_dirty = False
+        self.poll_fork_errors()
+        return CandResult(self.cand_score[:B], self.cand_rank[0, :B], self.cand_rank[1, :B],
+                          self.cand_counts[:B] if clk is not None else None, self.cand_metrics[:B] if clk is not None else None)
+
+
+class CandResult(NamedTuple):
+    """what TcarEngine.score_candidates returns: device views, valid until the next call"""
+    scores: torch.Tensor
+    rank_of: torch.Tensor
+    order: torch.Tensor
+    counts: Optional[torch.Tensor]
+    metrics: Optional[torch.Tensor]

@@ -47,6 +47,9 @@ REFERENCE_FLAGS = [
 MAX_PANEL = 49152          # the widest panel a fold takes (SEL_MAX_N of csrc/tcar_common.h; engine.TcarEngine.SERVE_MAX_PANEL)
 
 
+MAX_CANDIDATES = 1024      # slots of one candidate list (CAND_MAX_C of csrc/tcar_common.h; engine.TcarEngine.CAND_MAX_C)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="TCAR trainer (MI355X-native hot path)")
     for name, default, typ, hlp in REFERENCE_FLAGS:
@@ -85,6 +88,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
                          "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  "
                          "0: the materialised evaluation of the catalog-sharded engine")
+    ap.add_argument("--eval_candidates", default=0, type=int,
+                    help="C > 0: evaluation additionally ranks every label among C - 1 other items drawn uniformly from the catalog "
+                         "(include/tcar_cand.h: only those C rows are scored) and prints their AUC / MRR / nDCG@5 / nDCG@10; "
+                         "2 <= C <= " + str(MAX_CANDIDATES) + ".  Not with --dp_mode sharded; combines with everything else.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -133,6 +140,18 @@ def check_shard_eval_panel(shard_eval_panel, dp_mode):
     if shard_eval_panel and dp_mode != "sharded":
         raise ValueError("--shard_eval_panel streams the shards of the catalog-sharded engine: it needs --dp_mode sharded "
                          "(one engine with the whole catalog: --eval_panel)")
+
+
+def check_eval_candidates(eval_candidates, dp_mode):
+    """--eval_candidates ranks the label among sampled items through candidate-list scoring (include/tcar_cand.h), which takes the
+    whole catalog on one engine"""
+    if not eval_candidates:
+        return
+    if eval_candidates < 2 or eval_candidates > MAX_CANDIDATES:
+        raise ValueError("--eval_candidates must be in [2, %d] (0: off)" % MAX_CANDIDATES)
+    if dp_mode == "sharded":
+        raise ValueError("--eval_candidates scores candidate lists against the WHOLE catalog on one engine; it cannot be combined with "
+                         "--dp_mode sharded")
 
 
 def load_datas(args):
@@ -194,6 +213,7 @@ def main(argv=None):
     check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
     check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
+    check_eval_candidates(args.eval_candidates, args.dp_mode)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -70,6 +70,27 @@ def diversity_from_counts(ild_cnt, unexp_cnt, n_rec, T: int):
     return ild, unexp
 
 
+def impression_metrics(counts, metrics):
+    """Per-session impression metrics from what TcarEngine.score_candidates returns with `clicked`: counts [B, 3] int = (npos, nneg,
+    auc2) and metrics [B, 3] = (mrr, ndcg5, ndcg10) -> (auc, mrr, ndcg5, ndcg10), float64 arrays [B].  auc = auc2 / (2 npos nneg), the
+    ROC AUC with ties at one half; it is NaN where a session has no positive or no negative — the usual rule for impressions without
+    both classes — and `impression_means` drops such sessions from every mean."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 3)
+    metrics = np.asarray(metrics, dtype=np.float64).reshape(-1, 3)
+    pairs = counts[:, 0] * counts[:, 1]
+    auc = np.where(pairs > 0, counts[:, 2] / np.maximum(2 * pairs, 1).astype(np.float64), np.nan)
+    return auc, metrics[:, 0], metrics[:, 1], metrics[:, 2]
+
+
+def impression_means(counts, metrics):
+    """The four means of impression_metrics over the sessions that hold both classes -> {"auc", "mrr", "ndcg5", "ndcg10", "sessions"};
+    NaN means when no session qualifies."""
+    auc, mrr, n5, n10 = impression_metrics(counts, metrics)
+    keep = ~np.isnan(auc)
+    mean = lambda x: float(x[keep].mean()) if keep.any() else float("nan")
+    return {"auc": mean(auc), "mrr": mean(mrr), "ndcg5": mean(n5), "ndcg10": mean(n10), "sessions": int(keep.sum())}
+
+
 def category_table(reverse_item: dict, category_id, n_items: int) -> np.ndarray:
     """int table cat[item0] = code of category_id[reverse_item[item0]] (the double lookup of model_combine.py:180).
     The reference only ever compares categories with `!=`, so any label type works (MIND's categories are strings): the

@@ -140,6 +140,7 @@ class Seq2SeqAttNN():
         # test(): eval_panel > 0 selects while the catalog streams by in panels, shard_eval_panel > 0 (dp_mode sharded) streams every
         # rank's shard, fresh_hours > 0 ranks every session inside its publish-time pool, cat_cap > 0 caps the items of one category
         self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
+        self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -190,6 +191,22 @@ class Seq2SeqAttNN():
         cli.check_cat_cap(cap, panel, dp_mode)
         cli.check_shard_eval_panel(spanel, dp_mode)
         return panel, spanel, fresh, cap
+
+    def _eval_candidates(self, args) -> int:
+        """eval_candidates of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        ncand = int(args.get('eval_candidates', getattr(self, 'eval_candidates', 0)) or 0)
+        cli.check_eval_candidates(ncand, args.get('dp_mode', 'replica'))
+        return ncand
+
+    def _label_among_sampled(self, labels, ncand: int, rng):
+        """candidate lists [B, ncand] of the "label among sampled negatives" protocol: the label in slot 0, then ncand - 1 items drawn
+        uniformly from the catalog without the label (repeats among them allowed), and the matching clicked flags"""
+        lab = np.asarray(labels, dtype=np.int64).reshape(-1, 1)
+        others = rng.randint(0, self.candidate_n - 2, size=(lab.shape[0], ncand - 1)).astype(np.int64)
+        others += others >= lab                      # uniform over the N - 1 items that are not the label
+        clicked = np.zeros((lab.shape[0], ncand), dtype=np.int32)
+        clicked[:, 0] = 1
+        return np.concatenate([lab, others], axis=1).astype(np.int32), clicked
 
     # ------------------------------------------------------------------------------------------ helpers
     def _category_table(self):
@@ -373,6 +390,11 @@ class Seq2SeqAttNN():
         print('Measuring...')
         eng = self.engine
         panel, spanel, fresh, cap = self._eval_options(args)
+        ncand = self._eval_candidates(args)
+        if ncand and self.candidate_n - 1 < 2:
+            raise ValueError("eval_candidates ranks the label among OTHER items: the catalog holds fewer than two")
+        cand_rng = np.random.RandomState(self.seed) if ncand else None       # a stream of its own: no other random stream of the run moves
+        cand_pending = []
         if spanel and not hasattr(eng, "xch"):
             raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         time_dict = test_data[2] if len(test_data) > 2 else None
@@ -417,6 +439,9 @@ class Seq2SeqAttNN():
                 print('input_click_week:', int(feed["cw"][0]))
                 print('batch_out:', int(feed["label"][0]), args['publish_time'][int(feed["label"][0])])
                 print('batch pred:', tk[:10])
+            if ncand:            # the label among ncand - 1 sampled items: only those rows are scored (include/tcar_cand.h)
+                res = eng.score_candidates(None, *self._label_among_sampled(feed["label"], ncand, cand_rng), bt=bt)
+                cand_pending.append((res.counts.clone(), res.metrics.clone()))
         eng.check_forks()             # (synchronises) nothing below is reported from a run whose flag forks timed out
         for feed, rank, topk, ce, ild_c, unexp_c, n_rec in pending:
             r = rank.cpu().numpy()
@@ -451,6 +476,14 @@ class Seq2SeqAttNN():
         print('MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(m_mrr, m_hit, m_ndcg))
         self.last_metrics = {"mrr": m_mrr, "recall": m_hit, "ndcg": m_ndcg, "loss": m_loss, "ild": m_ild,
                              "unexp": m_unexp, "coverage": n_covered}
+        if ncand:
+            per = [M.impression_metrics(c.cpu().numpy(), m.cpu().numpy()) for c, m in cand_pending]
+            cols = [np.concatenate([p[i] for p in per]) if per else np.zeros(0) for i in range(4)]
+            keep = ~np.isnan(cols[0])                # (a label and its negatives always hold both classes; kept for the rule's sake)
+            tot = self._allsum([float(np.sum(x[keep])) for x in cols] + [float(keep.sum())])
+            c_auc, c_mrr, c_n5, c_n10 = [v / max(tot[4], 1.0) for v in tot[:4]]
+            print('candidates ({} per session): AUC: {}, MRR: {}, nDCG@5: {}, nDCG@10: {}'.format(ncand, c_auc, c_mrr, c_n5, c_n10))
+            self.last_metrics["candidates"] = {"auc": c_auc, "mrr": c_mrr, "ndcg5": c_n5, "ndcg10": c_n10}
         if fresh:           # (these labels are still scored: a label is always in its session's pool)
             share = self._allsum([float(np.sum(outside))])[0] / n
             print('labels outside their window: {}'.format(share))
@@ -475,3 +508,11 @@ class Seq2SeqAttNN():
         if max_per_category is not None:
             self._install_categories()
         return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)
+
+    def score_candidates(self, sessions, candidates, clicked=None):
+        """Score and rank the items every session of `sessions` names — a feed dict as `recommend` takes it; candidates int [B, C],
+        0-based ids, -1 = an empty slot — without touching the rest of the catalog: engine.CandResult(scores, rank_of, order, counts,
+        metrics) on the device (engine.TcarEngine.score_candidates).  With clicked [B, C] (0 / 1) the counts and metrics of each
+        list are those of an impression: host.metrics.impression_metrics turns them into AUC / MRR / nDCG@5 / nDCG@10.  Not with
+        the catalog-sharded engine."""
+        return self.engine.score_candidates(sessions, candidates, clicked)

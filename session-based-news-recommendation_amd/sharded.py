@@ -715,6 +715,10 @@ class ShardedEngine(TcarEngine):
         _, topk, _, self.last_scores = self._exchange(pc)
         return topk, self.last_scores
 
+    def score_candidates(self, batch, candidates, clicked=None, bt: Optional[Batch] = None):
+        """not on the catalog-sharded engine: a candidate's row lives on one rank only (include/tcar_cand.h takes the whole catalog)"""
+        raise _lib.TcarError("candidate scoring needs the whole catalog on one engine (no shard): the catalog-sharded engine has none")
+
     # ------------------------------------------------------------------------------ inspection (tests, export)
     def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:
         """this rank's [nl, ldh] rows of a candidate-side table -> the whole [N + 1, H] table in the reference's shape (row 0

@@ -17,7 +17,15 @@ rounds so that the spread between rounds is visible; the streamed results are co
 catalog for every session, timed beside the unwindowed one at every panel size.
 --cap M: also the capped streamed step (include/tcar_quota.h) with at most M items of one category in a list, timed beside the uncapped
 one.  The categories are the synthetic fold's own table if it has one, else C = --cats random codes.  --cap_skew adds the catalog
-whose items all share ONE category at cap 1: one accepted item and one kill pass per fold, however wide the panel."""
+whose items all share ONE category at cap 1: one accepted item and one kill pass per fold, however wide the panel.
+
+       python tools/eval_bench.py [iters] [--n_items N] --candidates C[,C...] [--panel P[,P...]] [--rounds R]
+
+--candidates C: TcarEngine.score_candidates (include/tcar_cand.h) with C uniformly drawn candidates per session and a clicked flag on
+slot 0, beside eval_step_streamed of the same engine, alternating for `rounds` rounds.  Per C it prints the whole step (session forward,
+the upload of the lists, scores, ranks and metrics) and the two kernels alone (device events around tcar_cand_scores and
+tcar_cand_rank on the step's operands), with the gathered bytes — B C rows of ek columns in two bf16 planes — over the scores
+kernel's time as a share of the 8 TB/s HBM specification."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -37,6 +45,7 @@ ap.add_argument("--cap", type=str, default="", help="comma-separated caps: at mo
 ap.add_argument("--cats", type=int, default=300, help="number of category codes when the synthetic fold carries no category table")
 ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog whose items all share one category")
 ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (needs --streamed)")
+ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -70,6 +79,48 @@ def timed(step):
 
 
 plain = lambda bt: eng.eval_step(None, bt=bt)
+cands = [int(c) for c in a.candidates.split(",") if c]
+if cands:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--candidates needs the whole catalog on one engine: not with --sharded")
+    panels = [int(p) for p in a.panel.split(",") if p] or [0]
+    g, rng = eng.geo, np.random.RandomState(3)
+    lists = {c: rng.randint(0, N, (B, c)).astype(np.int32) for c in cands}
+    clicked = {c: np.concatenate([np.ones((B, 1), np.int32), np.zeros((B, c - 1), np.int32)], 1) for c in cands}
+
+    def kernels_alone(c):
+        """ms of tcar_cand_scores and of tcar_cand_rank alone, on the operands and buffers the last step left on the engine"""
+        lib, p, st = eng.lib, eng._p, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            lib.tcar_cand_scores(B, c, g.N, g.ek, None, 0, None, 0, vp(eng.a16h), vp(eng.a16l), g.ek, vp(eng.e16h), vp(eng.e16l), g.ek, 3,
+                                 vp(eng.cand_in[0]), c, vp(eng.cand_score), c, st)
+        ev[1].record()
+        for it in range(iters):
+            lib.tcar_cand_rank(B, c, vp(eng.cand_score), c, vp(eng.cand_in[0]), c, vp(eng.cand_in[1]), c, vp(eng.cand_rank[0]),
+                               vp(eng.cand_rank[1]), vp(eng.cand_counts), vp(eng.cand_metrics), st)
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters, ev[1].elapsed_time(ev[2]) / iters
+
+    for rnd in range(a.rounds):
+        for P in panels:
+            dt = timed(lambda bt: eng.eval_step_streamed(None, bt=bt, panel=P or None))
+            print("N=%d round %d eval_step_streamed panel=%d: %.3f ms = %.0f sessions/s" % (N, rnd, P or eng.default_panel(), dt * 1e3, B / dt))
+        for c in cands:
+            dc = timed(lambda bt: eng.score_candidates(None, lists[c], clicked[c], bt=bt))
+            ks, kr = kernels_alone(c)
+            gathered = B * c * g.ek * 4                       # hi + lo plane, 2 bytes each, of every named row
+            print("N=%d round %d score_candidates C=%d: %.3f ms per step = %.0f sessions/s, %.3f of the streamed step; kernels alone: "
+                  "scores %.4f ms (%.1f MB gathered = %.2f TB/s = %.3f of 8 TB/s), rank %.4f ms" % (
+                      N, rnd, c, dc * 1e3, B / dc, dc / dt, ks, gathered / 1e6, gathered / (ks * 1e-3) / 1e12,
+                      gathered / (ks * 1e-3) / 8e12, kr))
+        sys.stdout.flush()
+    sys.exit(0)
 if not a.streamed:
     dt = timed(plain)
     print("eval step: %.3f ms  = %.0f sessions/s" % (dt * 1e3, B / dt))
