@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 # (TCAR_LIB: load THIS binary instead — a diagnostic build of the same sources, e.g. tools/obs1_probe.py's -DTCAR_OBS1_DIAG library;
 #  it must carry the same source digest and ABI, and it is never built or overwritten by build())
 LIB_PATH = os.environ.get("TCAR_LIB") or os.path.join(PKG_DIR, "libtcar_hip.so")
-SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "embed.hip", "pool.hip", "score.hip", "optim.hip", "step.hip", "mha.hip",
+SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "embed.hip", "pool.hip", "score.hip", "ce.hip", "optim.hip", "step.hip", "mha.hip",
            "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "select.hip", "cand.hip", "buildid.hip"]
 BUILD_ID_TU = "buildid.hip"        # the one translation unit that carries the digest of all sources
 
@@ -45,7 +45,8 @@ def _name(prefix: str, name: str) -> str:
 
 for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER, CAND_HEADER
     globals()[_name(_prefix, "HEADER")] = os.path.join(PKG_DIR, "..", "include", _file)
-HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), os.path.join(CSRC, "topk_rows.h")] + \
+HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), os.path.join(CSRC, "topk_rows.h"),
+           os.path.join(CSRC, "ce_rows.h")] + \
     [globals()[_name(_prefix, "HEADER")] for _prefix, _ in ABI_LAYERS]
 _ID_MARK = b"TCAR_BUILD_ID="
 

@@ -674,7 +674,7 @@ struct FinishArgs {
   float* out; long ld_out;
   __bf16* a_hi; __bf16* a_lo; int a_in32;                 // planes of attout (may be NULL)
   __bf16* ap_hi; __bf16* ap_lo; int ap_in32;              // packed [item | time] planes (may be NULL)
-  // anchor of the anchored softmax form (score.hip: ce_anchor_fold_kernel; label NULL: none): per row and 64-column block j of the
+  // anchor of the anchored softmax form (ce.hip: ce_anchor_fold_kernel; label NULL: none): per row and 64-column block j of the
   // item | content columns, the partial sum of attout[b, :] . E[label[b], :] — the label's score without its time part — leaves as
   // P[b, 139 + j] = -partial (hi / lo), against the ones of the one-hot plane's anchor columns (time_onehot_kernel)
   const int32_t* label; const float* E; long ldE;

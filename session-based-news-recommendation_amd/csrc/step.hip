@@ -320,7 +320,7 @@ bool onehot_bwd(const tcar_ctx_t* c, const tcar_batch_t* bt) {
   return onehot_fwd(c, bt->B) && tn(c).onehot_time >= 2 && c->tclip && c->dP && c->qz && c->d.ldt == 64 && c->et_perm && c->inv_off &&
          c->ct_ws && c->stream3 && c->ev3 && c->gw_rows && sorted_rows(c, bt) && tn(c).det_small != 0;
 }
-// anchored softmax form (score.hip: ce_anchor_fold_kernel): the one-hot step with the buffers of the form and at most eight 64-column
+// anchored softmax form (ce.hip: ce_anchor_fold_kernel): the one-hot step with the buffers of the form and at most eight 64-column
 // anchor partials per row (the anchor columns of the one-hot K segment: embed.hip)
 bool ce_anchored(const tcar_ctx_t* c, const tcar_batch_t* bt) {
   return onehot_bwd(c, bt) && tn(c).fused_ce >= 2 && c->ce_rowscale && c->aps16h && c->ce_form && 2 * c->d.ldh / 64 <= TCAR_ANCHOR_COLS;
@@ -1412,7 +1412,7 @@ bool shard_onehot(const tcar_ctx_t* c, const tcar_shard_t* s, CeWs* w) {
   return c->scoring == 3 && c->d.ldt == 64 && fused_ce(&cc, s->world * s->cap, w) && c->ce_geo && c->oh16 && c->p16h && c->p16l &&
          c->tclip && c->dP && c->qz && c->inv_off && c->ct_ws && c->mwdhm && tn(c).onehot_time >= 2;
 }
-// anchored softmax form on the shard (score.hip: ce_anchor_apply_kernel): the shard's one-hot schedule with the two buffers of the form
+// anchored softmax form on the shard (ce.hip: ce_anchor_apply_kernel): the shard's one-hot schedule with the two buffers of the form
 // in the shard descriptor
 bool shard_anchored(const tcar_ctx_t* c, const tcar_shard_t* s) {
   return tn(c).fused_ce >= 2 && s->aps16h && s->scale2 && s->n_total >= s->n0 + s->n_loc;

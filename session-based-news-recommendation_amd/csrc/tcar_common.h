@@ -129,7 +129,7 @@ __device__ __forceinline__ float ld1_sc1(const float* p) { return __hip_atomic_l
 // sets `carried` when the kernel form it chose publishes the flag (flag-capable forms: the latency form of the forward gather,
 // the click-query MLP, small-GEMM launches WITHOUT bf16 plane outputs, the softmax-epilogue logits GEMM, sqnorm_seg, the
 // small-table norm fold); a launch that cannot carry it leaves `carried` false and the driver forks with an event.
-// Anchored softmax form, dX side (score.hip: ce_anchor_fold_kernel / reduce_dact_onehot_kernel).  The slabs hold the UNSCALED plane
+// Anchored softmax form, dX side (ce.hip: ce_anchor_fold_kernel; score.hip: reduce_dact_onehot_kernel).  The slabs hold the UNSCALED plane
 // times [E | OH]; scale2[m] = (1 / S_m, r_m): the slab sums (and dP) of row m are multiplied by 1 / S_m, and r_m — the part of the
 // one-hot's -1 that the bf16 label entry of the plane could not hold, already divided by S_m — comes back in fp32 as
 // r_m * [E[label[m], :] | onehot(publish time of label[m])].  E: fp32 candidate rows [n_items, ldE] (item | content columns first).
