@@ -289,3 +289,26 @@ class TcarOracle:
 
     def export(self) -> "OrderedDict[str, np.ndarray]":
         return OrderedDict((k, v.detach().cpu().numpy().copy()) for k, v in self.p.items())
+
+    def export_state(self) -> Dict[str, np.ndarray]:
+        """The optimizer state under the keys of TcarEngine.export_state — `var/<name>`, `m/<name>`, `v/<name>`, `meta/step`,
+        `meta/beta_pow` — as the fp32 roundings of this oracle's values (a TF checkpoint holds fp32 too)."""
+        out = {}
+        for tag, d in (("var/", self.p), ("m/", self.m), ("v/", self.v)):
+            out.update({tag + k: v.detach().cpu().numpy().astype(np.float32) for k, v in d.items()})
+        out["meta/step"] = np.asarray(self.step, dtype=np.int64)
+        out["meta/beta_pow"] = np.asarray([self.b1_pow, self.b2_pow], dtype=np.float32)
+        return out
+
+    def load_state(self, st) -> None:
+        """Inverse of export_state, as TcarEngine.load_state: moments, powers and step are optional."""
+        with torch.no_grad():
+            for tag, d in (("var/", self.p), ("m/", self.m), ("v/", self.v)):
+                for k, v in d.items():
+                    if tag + k in st:
+                        v.copy_(torch.as_tensor(np.asarray(st[tag + k]), dtype=self.dtype).reshape(v.shape))
+        if "meta/step" in st:
+            self.step = int(np.asarray(st["meta/step"]))
+        if "meta/beta_pow" in st:
+            bp = np.asarray(st["meta/beta_pow"], dtype=np.float32)
+            self.b1_pow, self.b2_pow = np.float32(bp[0]), np.float32(bp[1])

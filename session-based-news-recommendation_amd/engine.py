@@ -752,6 +752,13 @@ class TcarEngine(OpLevelStep):
             lr, self._pending_lr = self._pending_lr, None
             check(self.lib.tcar_step_update(C.byref(self._update_ctx()), lr, self._stream()), "tcar_step_update")
 
+    def discard_pending_update(self) -> bool:
+        """Forget a deferred optimizer update WITHOUT applying it; returns whether one was owed.  The step count and the beta powers
+        have already advanced for it, so this is for a caller that replaces the whole state next (load_state) or reads the state in
+        front of the owed update (tests)."""
+        owed, self._pending_lr = self._pending_lr is not None, None
+        return owed
+
     def _step_deferred(self, enqueue, defer_update: bool):
         """The deferred-update protocol: enqueue(lr) runs one step WITHOUT its optimizer update, applying the owed update of the step
         before (rate lr; None: nothing owed) at its start; this step's update is then owed in turn — to the next step or to flush()."""
