@@ -128,8 +128,11 @@ class TcarOracle:
 
     def __init__(self, params: Dict[str, np.ndarray], content_emb: np.ndarray, mwdhm: np.ndarray,
                  lr: float = 1e-3, max_grad: Optional[float] = 150.0, dtype=torch.float64,
-                 neg_weight: float = 0.01, use_interval: bool = True, neg_fp32: bool = True):
+                 neg_weight: float = 0.01, use_interval: bool = True, neg_fp32: bool = True, straight_through=()):
         self.dtype = dtype
+        # (table, site) pairs, site in {"seq", "cand", "click"}, whose row clip (S1) keeps its forward value but passes the gradient
+        # through unchanged: the WRONG gradient of a backward pass that forgets the clip Jacobian (tests plant it to show a gate rejects it)
+        self.straight_through = frozenset(straight_through)
         self.p = OrderedDict((k, torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True))
                              for k, v in params.items())
         self.content = torch.tensor(np.asarray(content_emb), dtype=dtype)          # frozen, model_combine.py:67
@@ -160,11 +163,13 @@ class TcarOracle:
             raise IndexError("session longer than the 40-row position table (model_combine.py:57)")
         vals = {}  # IndexedSlices value blocks (S5), filled only when keep=True
 
-        def gather(name, table, ids):
+        def gather(name, table, ids, site="seq"):
             rows = table[ids]
             if keep:
                 rows.retain_grad()
                 vals.setdefault(name, []).append(rows)
+            if (name, site) in self.straight_through:
+                return rows + (clip_rows(rows) - rows).detach()
             return clip_rows(rows)
 
         # INPUT-CONTEXT  (model_combine.py:53-69)
@@ -175,9 +180,9 @@ class TcarOracle:
         # TEMPORAL-INFO (:72-97)
         tkeys = ["pm", "pd", "pw", "ph", "pmi"]
         seq_pt = torch.cat([gather(n, P[n], L(k)) for n, k in zip(TIME_TABLES, tkeys)], -1)
-        cand_pt = torch.cat([gather(n, P[n], self.mwdhm[:, i]) for i, n in enumerate(TIME_TABLES)], -1)
-        click_t = torch.cat([gather("week_embedding", P["week_embedding"], L("cw")),
-                             gather("hour_embedding", P["hour_embedding"], L("ch"))], -1)
+        cand_pt = torch.cat([gather(n, P[n], self.mwdhm[:, i], "cand") for i, n in enumerate(TIME_TABLES)], -1)
+        click_t = torch.cat([gather("week_embedding", P["week_embedding"], L("cw"), "click"),
+                             gather("hour_embedding", P["hour_embedding"], L("ch"), "click")], -1)
         # duration (:106-107); id >= 11 -> zero row, zero grad (S7)
         gap = L("gap")
         dur_ext = torch.cat([P["duration_embedding"], torch.zeros(1, self.Ht, dtype=dt)], 0)
@@ -201,6 +206,9 @@ class TcarOracle:
         # single_attention_layer / count_alpha_s (modules.py:72-101)
         pre2 = seq_pt @ P["cont_attention/input_linear_trans/w_3d"] \
             + seq_content @ P["cont_attention/cont_linear_trans/w_3d"]
+        if keep:
+            pre1.retain_grad()                        # d(loss)/d(pre1), d(loss)/d(pre2): the dy of the five weights used as x @ W
+            pre2.retain_grad()
         e3 = (torch.sigmoid(pre2) @ P["cont_attention/res_linear_trans/w_3d"]).reshape(B, T)
         alpha_t = expnorm(e3)
         pooled_t = torch.bmm(alpha_t.unsqueeze(1), seq_pt).reshape(B, -1)
@@ -221,7 +229,7 @@ class TcarOracle:
         ce = lse - logits.gather(1, label.unsqueeze(1)).squeeze(1)                     # :145
         out = {"logits": logits, "ce": ce, "attout": attout, "pooled_ic": pooled_ic, "pooled_t": pooled_t,
                "alpha1": alpha - alpha2, "alpha2": alpha2, "alpha_t": alpha_t, "q": q,
-               "seq_ic": seq_ic, "seq_pt": seq_pt, "seq_act": seq_act, "click_t": click_t,
+               "seq_ic": seq_ic, "seq_content": seq_content, "seq_pt": seq_pt, "seq_act": seq_act, "click_t": click_t,
                "pre1": pre1, "pre2": pre2, "cand_pt": cand_pt}
         neg = batch.get("neg", None)
         if with_neg and neg is not None and np.asarray(neg).size > 0:

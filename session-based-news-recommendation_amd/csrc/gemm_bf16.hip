@@ -187,7 +187,9 @@ __global__ __launch_bounds__(64 * WMW * WNW, (EPI == 2 ? (WMW * WNW == 9 ? 5 : 4
 #pragma unroll
     for (int t2 = 0; t2 < TNW; ++t2) {
       qz_row[t2] = 0; qz_pos[t2] = -1;
-      if (tw) {
+      // (a wave whose 64 columns lie beyond N — the ragged last N tile when ldh + 320 is no multiple of the tile's 192 columns — has
+      //  no table: k would be >= 5 and index perm, and through it qz, out of bounds)
+      if (tw && n0 + wn * (32 * TNW) < g.N) {
         const int k = (n0 + wn * (32 * TNW) - g.csplit) >> 6;
         const long n = m0 + wm * (32 * TMW) + t2 * 32 + (lane & 31);
         if (n < g.M) { qz_row[t2] = cand_row(g.mwdhm, n, k); qz_pos[t2] = g.perm[(long)k * g.M + n]; }

@@ -222,7 +222,8 @@ def a_inputs(shape, seed=11):
 #    has an absolute floor of 1e-9 for them; the gates here have none.
 #  * The lone session clicks two DIFFERENT items (tweak "distinct"; _case would repeat the first).  With one item clicked twice the two
 #    positions differ by dec_pos only, and the attention weights' gradients are differences of nearly equal terms: the split-bf16 modes'
-#    noise in the forward pass then puts them outside the gradient gate (docs/KERNELS.md, "Known gap").  That is no property of the update.
+#    noise in the forward pass then puts them outside the gradient gate.  That is no property of the update: the batch itself is held to
+#    the oracle by test_gpu_fused_step.py (case `lone_twice`, at a gate with a cancellation floor derived from the oracle: fused_ref.py).
 #  * The wide case runs at max_grad 4: its 64-session steps leave two variables below 0.8 * 2, but seven below 0.8 * 4.
 B_CASES = {
     "base": (300, 40, 16, 4, 5, 2.0, [(24, 3, 5, None), (24, 2, 6, "label"), (1, 2, 53, "distinct"), (40, 7, 8, None)]),
