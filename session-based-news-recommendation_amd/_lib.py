@@ -20,7 +20,8 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 #  it must carry the same source digest and ABI, and it is never built or overwritten by build())
 LIB_PATH = os.environ.get("TCAR_LIB") or os.path.join(PKG_DIR, "libtcar_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "embed.hip", "pool.hip", "score.hip", "ce.hip", "optim.hip", "step.hip", "mha.hip",
-           "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "select.hip", "cand.hip", "buildid.hip"]
+           "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "select.hip", "cand.hip", "retrieve.hip",
+           "buildid.hip"]
 BUILD_ID_TU = "buildid.hip"        # the one translation unit that carries the digest of all sources
 
 
@@ -33,9 +34,10 @@ def _hipcc() -> str:
 
 # The C ABI, one row per layer: (prefix of the layer's names in this module, its header under include/).  Every header is compiled
 # into the library AND read by _bind(), and each builds on the rows above it: the core; streamed score-and-select; its publish-time
-# windows; its per-category caps; the state merge and the shard's fold of the catalog-sharded serving path; candidate-list scoring.
+# windows; its per-category caps; the state merge and the shard's fold of the catalog-sharded serving path; candidate-list scoring;
+# the streamed top-C shortlist and the two-stage step.
 ABI_LAYERS = [("", "tcar_hip.h"), ("SERVE", "tcar_serve.h"), ("WINDOW", "tcar_window.h"), ("QUOTA", "tcar_quota.h"),
-              ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h")]
+              ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"), ("RETRIEVE", "tcar_retrieve.h")]
 
 
 def _name(prefix: str, name: str) -> str:
@@ -43,7 +45,7 @@ def _name(prefix: str, name: str) -> str:
     return prefix + "_" + name if prefix else name
 
 
-for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER, CAND_HEADER
+for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER, CAND_HEADER, ...
     globals()[_name(_prefix, "HEADER")] = os.path.join(PKG_DIR, "..", "include", _file)
 HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), os.path.join(CSRC, "topk_rows.h"),
            os.path.join(CSRC, "ce_rows.h")] + \

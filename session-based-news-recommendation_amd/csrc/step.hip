@@ -5,6 +5,7 @@
 #include "tcar_common.h"
 #include "../../include/tcar_serve_shard.h"
 #include "../../include/tcar_cand.h"
+#include "../../include/tcar_retrieve.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1342,6 +1343,71 @@ extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
   if (!d->rank_of && !d->order && !d->counts && !d->metrics) return TCAR_OK;
   return tcar_cand_rank(B, C, d->score, C, d->cand, d->ld_cand, d->clicked, d->ld_cand, d->rank_of, d->order, d->counts, d->metrics,
                         stream);
+}
+
+namespace {
+int check_retrieve_desc(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_retrieve_t* d) {
+  if (!c || !bt || bt->B < 0 || !d) return TCAR_E_ARG;
+  if (d->C < 1 || d->C > CAND_MAX_C || d->panel <= 0 || (d->panel & 127) || d->panel > SEL_MAX_N) return TCAR_E_ARG;
+  if (d->window && (!d->window->key || !d->window->lo || !d->window->hi)) return TCAR_E_ARG;
+  if (!d->panel_buf || !d->state || !d->ids || !tcar_aligned16(d->panel_buf) || d->X < 0 || (d->excl && d->X <= 0)) return TCAR_E_ARG;
+  if (d->state_bytes < tcar_retrieve_state_bytes(bt->B, d->C)) return TCAR_E_ARG;
+  return TCAR_OK;
+}
+
+// The body of a retrieval step behind its argument checks: the head of a forward pass as tcar_serve_step_quota runs it, a fold
+// shaped like serve_fold — per panel the evaluation form of the logits GEMM in the COARSE precision (the hi planes alone on a
+// split-bf16 engine, whatever its nsplit; the fp32 GEMM on the fp32 engine, which has no cheaper operands) into d->panel_buf, folded
+// by tcar_retrieve_panel while the panel is cache-warm — and the finishing launch.
+int retrieve_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d, void* stream) {
+  RET(check_ctx(c, bt));
+  if (c->scoring ? (!c->a16h || !c->e16h) : !c->attout) return TCAR_E_ARG;
+  const Geo g(c->d);
+  const int B = bt->B, C = d->C;
+  const tcar_window_t* w = d->window;
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
+  RET(tcar_retrieve_reset(B, C, d->state, stream));
+  for (int n0 = 0; n0 < g.N; n0 += d->panel) {
+    const int n = g.N - n0 < d->panel ? g.N - n0 : d->panel;
+    if (c->scoring) {
+      TcarOpt ol = opt_of(c);
+      const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
+      RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, c->a16h, nullptr, g.ek, B, (const char*)c->e16h + off, nullptr, g.ek, g.Npad - n0,
+                                d->panel_buf, d->panel, nullptr, 0, 0, nullptr, 0, 1, 1, stream, &ol));
+    } else {
+      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, d->panel_buf, d->panel, nullptr, 0, 0, 1, stream));
+    }
+    RET(tcar_retrieve_panel(B, n0, n, d->panel_buf, d->panel, C, d->excl, d->X, w ? w->key : nullptr, w ? w->lo : nullptr,
+                            w ? w->hi : nullptr, d->state, stream));
+  }
+  return tcar_retrieve_finish(B, C, d->state, d->ids, d->scores, stream);
+}
+}  // namespace
+
+// Retrieval (include/tcar_retrieve.h): a shortlist of C items per session from coarse scores, without the [B, N] logits.
+extern "C" int tcar_retrieve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d, void* stream) {
+  RET(check_retrieve_desc(c, bt, d));
+  if (bt->B == 0) return TCAR_OK;
+  return retrieve_impl(c, bt, refresh_time, d, stream);
+}
+
+// Two-stage recommendation with one session forward: the retrieval step, the shortlist's exact scores from the context's own
+// operands (as tcar_cand_step calls tcar_cand_scores), its list order, and the first k of it.
+extern "C" int tcar_retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d,
+                                         const tcar_rerank_t* r, void* stream) {
+  RET(check_retrieve_desc(c, bt, d));
+  if (!r || r->k < 1 || r->k > SEL_MAX_K || r->k > d->C || !r->cand_score || !r->order || !r->topk) return TCAR_E_ARG;
+  if (bt->B == 0) return TCAR_OK;
+  if (c->scoring == 3 && (!c->a16l || !c->e16l)) return TCAR_E_ARG;
+  RET(retrieve_impl(c, bt, refresh_time, d, stream));
+  const Geo g(c->d);
+  const int B = bt->B, C = d->C;
+  RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
+                       c->scoring, d->ids, C, r->cand_score, C, stream));
+  RET(tcar_cand_rank(B, C, r->cand_score, C, d->ids, C, nullptr, 0, r->rank_of, r->order, nullptr, nullptr, stream));
+  return tcar_rerank_take(B, C, r->k, d->ids, r->cand_score, r->order, r->topk, r->score, stream);
 }
 
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Cand, Dims, Grads, Segments, Quota, Serve, Tables, Window, check
+from ._lib import Batch, Cand, Dims, Grads, Rerank, Retrieve, Segments, Quota, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -948,12 +948,17 @@ class TcarEngine(OpLevelStep):
         if not 1 <= k <= 64:
             raise ValueError("k must be in [1, 64]")
         quota = self._quota(max_per_category) if max_per_category is not None else None
+        return k, self._panel_request(panel, window, width), quota
+
+    def _panel_request(self, panel: Optional[int], window, width: int) -> int:
+        """what every panel-streaming call checks of its request -> the columns per panel (`panel`, None or 0: default_panel())
+        clipped to `width`.  A `window` needs the item keys."""
         if window is not None and getattr(self, "_item_keys", None) is None:
             raise ValueError("a window compares item keys: call set_item_keys(keys) first")
         panel = self.default_panel() if not panel else int(panel)
         if panel <= 0 or panel % 128 or panel > self.SERVE_MAX_PANEL:
             raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
-        return k, min(panel, width), quota
+        return min(panel, width)
 
     def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None,
                max_per_category=None):
@@ -1110,6 +1115,90 @@ class TcarEngine(OpLevelStep):
         self.poll_fork_errors()
         return CandResult(self.cand_score[:B], self.cand_rank[0, :B], self.cand_rank[1, :B],
                           self.cand_counts[:B] if clk is not None else None, self.cand_metrics[:B] if clk is not None else None)
+
+    # ---- retrieval and the two-stage call (include/tcar_retrieve.h): a shortlist of up to 1,024 items from coarse scores
+    RETRIEVE_MAX_C = 1024          # entries of one shortlist (a candidate list of tcar_cand.h: CAND_MAX_C)
+
+    def _retrieve_request(self, C_: int, k: Optional[int], panel: Optional[int], window, width: int) -> int:
+        """The request of retrieve (k None) / recommend_two_stage, validated before anything is launched -> the columns per panel
+        (`panel`, None or 0: default_panel()) clipped to `width`."""
+        if isinstance(C_, bool) or not isinstance(C_, (int, np.integer)) or not 1 <= C_ <= self.RETRIEVE_MAX_C:
+            raise ValueError("the shortlist must hold 1 to %d items" % self.RETRIEVE_MAX_C)
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64:
+                raise ValueError("k must be in [1, 64]")
+            if k > C_:
+                raise ValueError("k = %d items cannot come out of a shortlist of %d" % (k, C_))
+        return self._panel_request(panel, window, width)
+
+    def _retrieve(self, batch, C_: int, k: Optional[int], exclude_seen: bool, exclude, panel: Optional[int], window):
+        """one tcar_retrieve_step (k None) or tcar_retrieve_rerank_step; returns views of the workspace"""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("retrieval needs the whole catalog on this engine (no shard)")
+        panel = self._retrieve_request(C_, k, panel, window, g.Npad)
+        C_ = int(C_)
+        self.flush()
+        bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
+        B = bt.B
+        self._ensure_work(B, bt.T)
+        wb = self.work_B
+        state_words = 2 * C_ + 4                 # tcar_retrieve_state_bytes(B, C) / (4 B)
+        specs = [Spec("panel_buf", (wb, panel), F32), Spec("rt_state", (wb, state_words), I32), Spec("rt_ids", (wb, C_), I32),
+                 Spec("rt_scores", (wb, C_), F32)]
+        if k is not None:
+            k = int(k)
+            specs += [Spec("rt_exact", (wb, C_), F32), Spec("rt_rank", (2, wb, C_), I32), Spec("rt_topk", (wb, k), I32),
+                      Spec("rt_topscore", (wb, k), F32)]
+        if excl is not None:
+            specs.append(Spec("excl", (wb, int(excl.shape[1])), I32))
+        self.ws.ensure(specs)
+        assert self.lib.tcar_retrieve_state_bytes(B, C_) <= self.rt_state.numel() * 4
+        if excl is not None:
+            self.excl[:B].copy_(excl)
+        d = Retrieve()
+        d.C, d.panel, d.panel_buf = C_, panel, self.panel_buf.data_ptr()
+        d.state, d.state_bytes = self.rt_state.data_ptr(), self.rt_state.numel() * 4
+        if excl is not None:
+            d.excl, d.X = self.excl.data_ptr(), int(excl.shape[1])
+        d.ids, d.scores = self.rt_ids.data_ptr(), self.rt_scores.data_ptr()
+        w = self._window(window, B) if window is not None else None
+        if w is not None:
+            d.window = C.addressof(w)            # (w stays alive until the call has returned)
+        bt = self._without_neg(bt, label=False)
+        if k is None:
+            check(self.lib.tcar_retrieve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), self._stream()),
+                  "tcar_retrieve_step")
+        else:
+            r = Rerank()
+            r.k, r.cand_score = k, self.rt_exact.data_ptr()
+            r.rank_of, r.order = self.rt_rank[0].data_ptr(), self.rt_rank[1].data_ptr()
+            r.topk, r.score = self.rt_topk.data_ptr(), self.rt_topscore.data_ptr()
+            check(self.lib.tcar_retrieve_rerank_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), C.byref(r),
+                                                     self._stream()), "tcar_retrieve_rerank_step")
+        self._time_dirty = False
+        self.poll_fork_errors()
+        if k is None:
+            return self.rt_ids[:B], self.rt_scores[:B]
+        return self.rt_topk[:B], self.rt_topscore[:B]
+
+    def retrieve(self, batch, C: int, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None):      # noqa: N803
+        """A shortlist of the C best next items of every session, 1 <= C <= 1024, from COARSE scores: (ids [B, C] int32,
+        coarse_scores [B, C] f32), best first (score, then item id, descending); -1 / -inf where fewer than C items are eligible —
+        the empty slot of score_candidates, so `ids` is a valid candidate list.  On a split-bf16 engine the coarse scores contract the
+        hi planes alone (a third of the MFMA work, half of the plane bytes, about 2^-8 relative per operand); the fp32 engine has no
+        cheaper operands and retrieves from its own scores.  exclude_seen, exclude and window as recommend() takes them.  Views of
+        the workspace, valid until the next call."""
+        return self._retrieve(batch, C, None, exclude_seen, exclude, panel, window)
+
+    def recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
+                            panel: Optional[int] = None, window=None):
+        """recommend() in two stages with one session forward: retrieve(batch, shortlist) from coarse scores, then the exact scores
+        of the shortlist (score_candidates' kernel, the engine's own scoring precision) and its k best: (topk [B,k] int32, scores
+        [B,k] f32), best first; -1 where fewer than k items are eligible.  The list is the top k of the exact scores OVER THE
+        SHORTLIST: an item the coarse scores rank below `shortlist` cannot enter it.  k <= 64 and k <= shortlist <= 1024.  Views of
+        the workspace, valid until the next call; the shortlist itself is in `rt_ids` / `rt_scores`."""
+        return self._retrieve(batch, shortlist, k, exclude_seen, exclude, panel, window)
 
 
 class CandResult(NamedTuple):

@@ -47,6 +47,7 @@ REFERENCE_FLAGS = [
 MAX_PANEL = 49152          # the widest panel a fold takes (SEL_MAX_N of csrc/tcar_common.h; engine.TcarEngine.SERVE_MAX_PANEL)
 
 
+MAX_SHORTLIST = 1024       # entries of one shortlist (engine.TcarEngine.RETRIEVE_MAX_C); a list of up to 64 needs no first stage
 MAX_CANDIDATES = 1024      # slots of one candidate list (CAND_MAX_C of csrc/tcar_common.h; engine.TcarEngine.CAND_MAX_C)
 
 
@@ -92,6 +93,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="C > 0: evaluation additionally ranks every label among C - 1 other items drawn uniformly from the catalog "
                          "(include/tcar_cand.h: only those C rows are scored) and prints their AUC / MRR / nDCG@5 / nDCG@10; "
                          "2 <= C <= " + str(MAX_CANDIDATES) + ".  Not with --dp_mode sharded; combines with everything else.  0: off")
+    ap.add_argument("--eval_shortlist", default=0, type=int,
+                    help="C > 0: evaluation additionally runs the two-stage recommendation on every batch (include/tcar_retrieve.h: a "
+                         "shortlist of C items from coarse scores, re-scored exactly and cut to 20) and prints the share of labels in those "
+                         "lists and their agreement with the streamed lists; 65 <= C <= " + str(MAX_SHORTLIST) + ".  Needs --eval_panel; "
+                         "not with --dp_mode sharded, not with --cat_cap.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -154,6 +160,21 @@ def check_eval_candidates(eval_candidates, dp_mode):
                          "--dp_mode sharded")
 
 
+def check_eval_shortlist(eval_shortlist, eval_panel, dp_mode, cat_cap=0):
+    """--eval_shortlist runs the two-stage recommendation (include/tcar_retrieve.h) beside the streamed evaluation of ONE engine and
+    compares their lists: it needs --eval_panel and the whole catalog on one engine, and retrieval takes no per-category cap"""
+    if not eval_shortlist:
+        return
+    if eval_shortlist < 65 or eval_shortlist > MAX_SHORTLIST:
+        raise ValueError("--eval_shortlist must be in [65, %d] (0: off)" % MAX_SHORTLIST)
+    if dp_mode == "sharded":
+        raise ValueError("--eval_shortlist retrieves from the WHOLE catalog on one engine; it cannot be combined with --dp_mode sharded")
+    if not eval_panel:
+        raise ValueError("--eval_shortlist needs --eval_panel P: its lists are compared with those of the streamed evaluation")
+    if cat_cap:
+        raise ValueError("--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap")
+
+
 def load_datas(args):
     """main.py:14-47: returns train_data, test_data, neighbor, args(dict), item_dict."""
     print("load the datasets.")
@@ -214,6 +235,7 @@ def main(argv=None):
     check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
+    check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -141,6 +141,7 @@ class Seq2SeqAttNN():
         # rank's shard, fresh_hours > 0 ranks every session inside its publish-time pool, cat_cap > 0 caps the items of one category
         self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
         self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
+        self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -197,6 +198,12 @@ class Seq2SeqAttNN():
         ncand = int(args.get('eval_candidates', getattr(self, 'eval_candidates', 0)) or 0)
         cli.check_eval_candidates(ncand, args.get('dp_mode', 'replica'))
         return ncand
+
+    def _eval_shortlist(self, args) -> int:
+        """eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        panel, cap, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'cat_cap', 'eval_shortlist'))
+        cli.check_eval_shortlist(short, panel, args.get('dp_mode', 'replica'), cap)
+        return short
 
     def _label_among_sampled(self, labels, ncand: int, rng):
         """candidate lists [B, ncand] of the "label among sampled negatives" protocol: the label in slot 0, then ncand - 1 items drawn
@@ -395,6 +402,8 @@ class Seq2SeqAttNN():
             raise ValueError("eval_candidates ranks the label among OTHER items: the catalog holds fewer than two")
         cand_rng = np.random.RandomState(self.seed) if ncand else None       # a stream of its own: no other random stream of the run moves
         cand_pending = []
+        short = self._eval_shortlist(args)
+        short_pending = []
         if spanel and not hasattr(eng, "xch"):
             raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         time_dict = test_data[2] if len(test_data) > 2 else None
@@ -442,6 +451,10 @@ class Seq2SeqAttNN():
             if ncand:            # the label among ncand - 1 sampled items: only those rows are scored (include/tcar_cand.h)
                 res = eng.score_candidates(None, *self._label_among_sampled(feed["label"], ncand, cand_rng), bt=bt)
                 cand_pending.append((res.counts.clone(), res.metrics.clone()))
+            if short:            # the two-stage lists of the same sessions (include/tcar_retrieve.h), beside the streamed ones
+                two, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
+                                                 exclude_seen=False, panel=panel, window=window)
+                short_pending.append((feed["label"], topk.clone(), two.clone()))       # (topk: the streamed step's own buffer, untouched)
         eng.check_forks()             # (synchronises) nothing below is reported from a run whose flag forks timed out
         for feed, rank, topk, ce, ild_c, unexp_c, n_rec in pending:
             r = rank.cpu().numpy()
@@ -484,6 +497,15 @@ class Seq2SeqAttNN():
             c_auc, c_mrr, c_n5, c_n10 = [v / max(tot[4], 1.0) for v in tot[:4]]
             print('candidates ({} per session): AUC: {}, MRR: {}, nDCG@5: {}, nDCG@10: {}'.format(ncand, c_auc, c_mrr, c_n5, c_n10))
             self.last_metrics["candidates"] = {"auc": c_auc, "mrr": c_mrr, "ndcg5": c_n5, "ndcg10": c_n10}
+        if short:
+            inside, agree = [], []
+            for label, streamed, two in short_pending:
+                two, streamed = two.cpu().numpy(), streamed.cpu().numpy()
+                inside += (two == np.asarray(label)[:, None]).any(1).tolist()
+                agree += [len(set(t[t >= 0].tolist()) & set(s_.tolist())) / 20.0 for t, s_ in zip(two, streamed)]
+            t_hit, t_agree = [v / n for v in self._allsum([float(np.sum(inside)), float(np.sum(agree))])]
+            print('two-stage lists (shortlist {}): Recall@20: {}, agreement with the streamed lists: {}'.format(short, t_hit, t_agree))
+            self.last_metrics["two_stage"] = {"recall": t_hit, "agreement": t_agree, "shortlist": short}
         if fresh:           # (these labels are still scored: a label is always in its session's pool)
             share = self._allsum([float(np.sum(outside))])[0] / n
             print('labels outside their window: {}'.format(share))
@@ -495,19 +517,34 @@ class Seq2SeqAttNN():
         return m_hit
 
     # ---------------------------------------------------------------------------------------- recommend
-    def recommend(self, sessions, k=20, window=None, max_per_category=None, **kw):
+    def recommend(self, sessions, k=20, window=None, max_per_category=None, shortlist=None, **kw):
         """The k best next items of every session of `sessions` — a feed dict as the samplers build it (seq, pm, pd, pw, ph, pmi,
         gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
         has already read are left out (engine.TcarEngine.recommend has the options).  window = (lo, hi), scalars or arrays [B], in
         minutes since the earliest publish time (`minute_of(datetime)`): only items published in [lo, hi) are candidates.
         max_per_category = m >= 1: at most m items of one category (the fold's category table) in a list.
         With the catalog-sharded engine (dp_mode sharded) this is a COLLECTIVE: every rank calls it with its own sessions — None
-        where it has none, with cap= and T= (sharded.ShardedEngine.recommend)."""
+        where it has none, with cap= and T= (sharded.ShardedEngine.recommend).
+        shortlist = C (k <= C <= 1024): the two-stage form — C items retrieved from coarse scores, re-scored exactly, the k best of
+        them returned (engine.TcarEngine.recommend_two_stage); None: the streamed selection over exact scores, as ever."""
+        if shortlist is not None and max_per_category is not None:
+            raise ValueError("the two-stage recommendation takes no per-category cap (shortlist and max_per_category exclude each other)")
         if window is not None:
             self._item_keys()
         if max_per_category is not None:
             self._install_categories()
+        if shortlist is not None:
+            return self.engine.recommend_two_stage(sessions, k=k, shortlist=shortlist, window=window, **kw)
         return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)
+
+    def retrieve(self, sessions, C, window=None, **kw):      # noqa: N803
+        """A shortlist of the C best next items (1 <= C <= 1024) of every session of `sessions` — a feed dict as `recommend` takes
+        it — from coarse scores: (ids [B, C] int32, coarse_scores [B, C] f32) on the device, -1 / -inf where fewer than C items are
+        eligible; a valid `candidates` of score_candidates (engine.TcarEngine.retrieve has the options).  window as in `recommend`.
+        Not with the catalog-sharded engine."""
+        if window is not None:
+            self._item_keys()
+        return self.engine.retrieve(sessions, C, window=window, **kw)
 
     def score_candidates(self, sessions, candidates, clicked=None):
         """Score and rank the items every session of `sessions` names — a feed dict as `recommend` takes it; candidates int [B, C],

@@ -719,6 +719,18 @@ class ShardedEngine(TcarEngine):
         """not on the catalog-sharded engine: a candidate's row lives on one rank only (include/tcar_cand.h takes the whole catalog)"""
         raise _lib.TcarError("candidate scoring needs the whole catalog on one engine (no shard): the catalog-sharded engine has none")
 
+    def retrieve(self, batch, C, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None):      # noqa: N803
+        """not on the catalog-sharded engine: the shortlists of the shards would have to be merged (include/tcar_retrieve.h takes the
+        whole catalog)"""
+        raise _lib.TcarError("retrieve() needs the whole catalog on one engine (no shard): the catalog-sharded engine cannot merge "
+                             "shortlists")
+
+    def recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
+                            panel: Optional[int] = None, window=None):
+        """not on the catalog-sharded engine: its first stage is retrieve(), its second score_candidates()"""
+        raise _lib.TcarError("recommend_two_stage() needs the whole catalog on one engine (no shard): the catalog-sharded engine "
+                             "has neither retrieve() nor score_candidates()")
+
     # ------------------------------------------------------------------------------ inspection (tests, export)
     def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:
         """this rank's [nl, ldh] rows of a candidate-side table -> the whole [N + 1, H] table in the reference's shape (row 0

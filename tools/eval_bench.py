@@ -25,7 +25,16 @@ whose items all share ONE category at cap 1: one accepted item and one kill pass
 slot 0, beside eval_step_streamed of the same engine, alternating for `rounds` rounds.  Per C it prints the whole step (session forward,
 the upload of the lists, scores, ranks and metrics) and the two kernels alone (device events around tcar_cand_scores and
 tcar_cand_rank on the step's operands), with the gathered bytes — B C rows of ek columns in two bf16 planes — over the scores
-kernel's time as a share of the 8 TB/s HBM specification."""
+kernel's time as a share of the 8 TB/s HBM specification.
+
+       python tools/eval_bench.py [iters] [--n_items N] --retrieve C[,C...] [--k K] [--panel P] [--rounds R]
+
+--retrieve C: TcarEngine.recommend (the streamed selection over exact scores), retrieve (include/tcar_retrieve.h: a shortlist of C from
+coarse scores) and recommend_two_stage (shortlist C, re-scored exactly, cut to K) on the same host batches, alternating for `rounds`
+rounds: ms per step (upload included in all three), the agreement of the two-stage lists with the streamed ones (mean share of a
+streamed list found in the two-stage list, and the share of sessions whose lists are equal), and the two selectors alone — device
+events around one fold of the panel the last step left in the panel buffer into a fresh state, tcar_select_panel at K beside
+tcar_retrieve_panel at C."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -46,6 +55,8 @@ ap.add_argument("--cats", type=int, default=300, help="number of category codes 
 ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog whose items all share one category")
 ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (needs --streamed)")
 ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
+ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
+ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve)")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -119,6 +130,66 @@ if cands:
                   "scores %.4f ms (%.1f MB gathered = %.2f TB/s = %.3f of 8 TB/s), rank %.4f ms" % (
                       N, rnd, c, dc * 1e3, B / dc, dc / dt, ks, gathered / 1e6, gathered / (ks * 1e-3) / 1e12,
                       gathered / (ks * 1e-3) / 8e12, kr))
+        sys.stdout.flush()
+    sys.exit(0)
+shorts = [int(c) for c in a.retrieve.split(",") if c]
+if shorts:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--retrieve needs the whole catalog on one engine: not with --sharded")
+    P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
+    K = a.k
+    feeds = [{n: v for n, v in b.items() if n not in ("label", "neg")} for b in batches]
+
+    def timed_host(step):
+        for i in range(5):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    def folds_alone(c):
+        """ms of one tcar_select_panel (k = K) and one tcar_retrieve_panel (C = c) over the panel buffer as the last step left it,
+        each into a freshly reset state (the reset is inside the timed region of both)"""
+        lib, st = eng.lib, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        n = min(eng.panel_buf.shape[1], N)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            lib.tcar_select_reset(B, K, vp(eng.sel_state), st)
+            lib.tcar_select_panel(B, 0, n, vp(eng.panel_buf), eng.panel_buf.shape[1], K, None, None, None, 0, vp(eng.sel_state), st)
+        ev[1].record()
+        for it in range(iters):
+            lib.tcar_retrieve_reset(B, c, vp(eng.rt_state), st)
+            lib.tcar_retrieve_panel(B, 0, n, vp(eng.panel_buf), eng.panel_buf.shape[1], c, None, 0, None, None, None, vp(eng.rt_state), st)
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters, ev[1].elapsed_time(ev[2]) / iters
+
+    for c in shorts:             # agreement on every batch, outside the timed loops
+        found, same = [], []
+        for f in feeds:
+            t0 = eng.recommend(f, k=K, panel=P)[0].clone()
+            t1 = eng.recommend_two_stage(f, k=K, shortlist=c, panel=P)[0]
+            found.append(((t0[:, :, None] == t1[:, None, :]) & (t0[:, :, None] >= 0)).any(2).float().mean().item())
+            same.append((t0 == t1).all(1).float().mean().item())
+        print("N=%d k=%d shortlist=%d: share of the streamed lists found in the two-stage lists %.5f, sessions with equal lists %.4f" % (
+            N, K, c, float(np.mean(found)), float(np.mean(same))))
+    for rnd in range(a.rounds):
+        dt = timed_host(lambda f: eng.recommend(f, k=K, panel=P))
+        print("N=%d round %d recommend k=%d: %.3f ms = %.0f sessions/s" % (N, rnd, K, dt * 1e3, B / dt))
+        for c in shorts:
+            dr = timed_host(lambda f: eng.retrieve(f, c, panel=P))
+            d2 = timed_host(lambda f: eng.recommend_two_stage(f, k=K, shortlist=c, panel=P))
+            fs, fr = folds_alone(c)
+            print("N=%d round %d C=%d: retrieve %.3f ms (%.3f of recommend), recommend_two_stage %.3f ms (%.3f of recommend); one fold of "
+                  "%d columns alone: select k=%d %.4f ms, retrieve C=%d %.4f ms" % (
+                      N, rnd, c, dr * 1e3, dr / dt, d2 * 1e3, d2 / dt, min(eng.panel_buf.shape[1], N), K, fs, c, fr))
         sys.stdout.flush()
     sys.exit(0)
 if not a.streamed:
