@@ -31,6 +31,12 @@ struct EmbArgs {
   // item norm, tcar_sqnorm_det's job) beside the row gradients instead of in a launch of their own
   const float* sq_g; long sq_len; float* sq_part; int n_gather;
 };
+// ragged forward gather (include/tcar_ragged.h): R rows in all, the position of row r inside its session is rpos[r].  A kernel
+// argument of its own: EmbArgs, and with it every rectangular kernel, stays what it was.
+struct EmbRagged { int R; const int32_t* rpos; };
+__device__ __forceinline__ const EmbRagged& emb_ragged(const EmbRagged& r) { return r; }
+__device__ __forceinline__ EmbRagged emb_ragged() { return EmbRagged{0, nullptr}; }
+
 
 __device__ __forceinline__ int time_vocab(int k) {
   return k == 0 ? 13 : k == 1 ? 32 : k == 2 ? 8 : k == 3 ? 25 : k == 4 ? 61 : TCAR_DUR_VOCAB;
@@ -48,12 +54,17 @@ __device__ __forceinline__ P pick5(P const (&arr)[5], int k) {
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-template <int NCH>  // NCH = ceil(ldh / 256): 16-byte chunks per lane for an H-row
-__global__ __launch_bounds__(256) void gather_clip_fwd_kernel(const EmbArgs a) {
+// RAGGED: the rows of sessions of mixed lengths, R in all — the position row of a row is rpos[row] (clamped into the 40-row table) in
+// place of row % T; everything else is per row already
+// RG: nothing (the rectangular kernel: its signature and its code are what they were) or one EmbRagged.
+template <int NCH, class... RG>  // NCH = ceil(ldh / 256): 16-byte chunks per lane for an H-row
+__global__ __launch_bounds__(256) void gather_clip_fwd_kernel(const EmbArgs a, const RG... rg_) {
+  constexpr bool RAGGED = sizeof...(RG) > 0;
+  const EmbRagged& rg = emb_ragged(rg_...);
   const int lane = threadIdx.x & 63;
   const int wave_g = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * 4;
-  const int B = a.bt.B, T = a.bt.T, BT = B * T;
+  const int B = a.bt.B, T = a.bt.T, BT = RAGGED ? rg.R : B * T;
   const int ldh = a.d.ldh, ldt = a.d.ldt;
   const int ic = 2 * ldh, pt = 5 * ldt, ek = ic + pt, ct = 2 * ldt;
   const int sub = ldt >> 2;          // lanes per time row (16 for ldt = 64)
@@ -71,7 +82,7 @@ __global__ __launch_bounds__(256) void gather_clip_fwd_kernel(const EmbArgs a) {
       const int row = row0 + u * nwaves;
       live[u] = row < BT;
       const int rw = live[u] ? row : row0;
-      const int t = rw % T;
+      const int t = RAGGED ? clampi(rg.rpos[rw], 0, TCAR_POS_VOCAB - 1) : rw % T;
       const int n = clampi(a.bt.seq[rw], 1, a.d.n_items) - 1;
       const float* e = a.tab.E + (long)n * ek;
 #pragma unroll
@@ -168,13 +179,15 @@ __device__ __forceinline__ void st4_nt(float* p, float4 v) {
 
 // R: consecutive session rows per wave and trip; PLAIN: plain stores instead of non-temporal ones (round 5 measured R = 1 / 4 / 8 and
 // plain stores slower than the defaults: profiles/r05_ab_experiments.txt)
-template <int NCH, int R = 2, bool PLAIN = false>
-__global__ __launch_bounds__(1024) void gather_clip_fwd_big_kernel(const EmbArgs a) {
+template <int NCH, int R = 2, bool PLAIN = false, class... RG>
+__global__ __launch_bounds__(1024) void gather_clip_fwd_big_kernel(const EmbArgs a, const RG... rg_) {
+  constexpr bool RAGGED = sizeof...(RG) > 0;
+  const EmbRagged& rg = emb_ragged(rg_...);
   auto st_out = [](float* p, float4 v) { if (PLAIN) st4(p, v); else st4_nt(p, v); };
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int B = a.bt.B, T = a.bt.T, BT = B * T;
+  const int B = a.bt.B, T = a.bt.T, BT = RAGGED ? rg.R : B * T;
   const int ldh = a.d.ldh, ldt = a.d.ldt;
   const int ic = 2 * ldh, pt = 5 * ldt, ek = ic + pt, ct = 2 * ldt;
   const int sub = ldt >> 2, gpw = 64 / sub;
@@ -261,7 +274,7 @@ __global__ __launch_bounds__(1024) void gather_clip_fwd_big_kernel(const EmbArgs
       for (int c = 0; c < NCH; ++c) { si += dot4(xi[u][c], xi[u][c]); sc += dot4(xc[u][c], xc[u][c]); }
       si = clip_scale(wave_sum(si)); sc = clip_scale(wave_sum(sc));
       if (row < BT) {
-        const int t = (int)(row % T);
+        const int t = RAGGED ? clampi(rg.rpos[row], 0, TCAR_POS_VOCAB - 1) : (int)(row % T);
         float* o = a.x_icp + row * ic;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -1295,12 +1308,25 @@ extern "C" int tcar_gather_clip_fwd_tuned(const tcar_tuning_t* tune, const tcar_
 // (flag-capable in the latency form: the click rows leave write-through when the launch carries a flag; the throughput form is not)
 int tcar_gather_clip_fwd_o(const tcar_dims_t* d, const tcar_tables_t* tab, const tcar_batch_t* bt, float* x_icp, float* x_pt,
                            float* x_act, float* click_t, void* stream, TcarOpt* o) {
+  return tcar_gather_clip_fwd_rg(d, tab, bt, nullptr, x_icp, x_pt, x_act, click_t, stream, o);
+}
+extern "C" int tcar_gather_clip_fwd_ragged(const tcar_dims_t* d, const tcar_tables_t* tab, const tcar_batch_t* bt, const tcar_ragged_t* rg,
+                                           float* x_icp, float* x_pt, float* x_act, float* click_t, void* stream) {
+  if (!rg) return TCAR_E_ARG;
+  return tcar_gather_clip_fwd_rg(d, tab, bt, rg, x_icp, x_pt, x_act, click_t, stream, nullptr);
+}
+// rg NULL: the rectangular gather.  The form rule and the grids depend on the row count alone, so a ragged call of uniform lengths
+// launches what the rectangular call launches.
+int tcar_gather_clip_fwd_rg(const tcar_dims_t* d, const tcar_tables_t* tab, const tcar_batch_t* bt, const tcar_ragged_t* rg, float* x_icp,
+                            float* x_pt, float* x_act, float* click_t, void* stream, TcarOpt* o) {
   const TcarTuning& tn = tcar_tn(o);
   if (check_dims(d) || !tab || !bt || bt->B <= 0 || bt->T <= 0 || bt->T > TCAR_POS_VOCAB) return TCAR_E_ARG;
+  if (rg && (!rg->off || !rg->pos || rg->R < bt->B || (long)rg->R > (long)TCAR_POS_VOCAB * bt->B)) return TCAR_E_ARG;
   EmbArgs a{};
   a.d = *d; a.tab = *tab; a.bt = *bt;
   a.x_icp = x_icp; a.x_pt = x_pt; a.x_act = x_act; a.click_t = click_t;
-  const long rows = (long)bt->B * bt->T;
+  const EmbRagged er{rg ? rg->R : 0, rg ? rg->pos : nullptr};
+  const long rows = rg ? (long)rg->R : (long)bt->B * bt->T;
   const size_t big_lds = ((size_t)TCAR_POS_VOCAB * d->ldh + (size_t)SMALL_ROWS * d->ldt) * sizeof(float);
   if (rows >= tn.gather_big_rows && big_lds <= 160 * 1024) {
     // throughput form: one 16-wave workgroup per CU (the clipped small tables live in its LDS)
@@ -1312,7 +1338,15 @@ int tcar_gather_clip_fwd_o(const tcar_dims_t* d, const tcar_tables_t* tab, const
     long g = (rows + 16 * rpw - 1) / (16 * rpw);
     const long cap = (long)cus * tcar_fixed::gather_wg;
     if (g > cap) g = cap;
-    if (d->ldh <= 256) {
+    if (rg) {
+      if (d->ldh <= 256) {
+        TCAR_SET_LDS_ONCE((gather_clip_fwd_big_kernel<1, 2, false, EmbRagged>), 160 * 1024);
+        TCAR_LAUNCH((gather_clip_fwd_big_kernel<1, 2, false, EmbRagged>), dim3((int)g), dim3(1024), big_lds, (hipStream_t)stream, a, er);
+      } else {
+        TCAR_SET_LDS_ONCE((gather_clip_fwd_big_kernel<2, 2, false, EmbRagged>), 160 * 1024);
+        TCAR_LAUNCH((gather_clip_fwd_big_kernel<2, 2, false, EmbRagged>), dim3((int)g), dim3(1024), big_lds, (hipStream_t)stream, a, er);
+      }
+    } else if (d->ldh <= 256) {
       TCAR_SET_LDS_ONCE(gather_clip_fwd_big_kernel<1>, 160 * 1024);
       TCAR_LAUNCH(gather_clip_fwd_big_kernel<1>, dim3((int)g), dim3(1024), big_lds, (hipStream_t)stream, a);
     } else {
@@ -1322,9 +1356,12 @@ int tcar_gather_clip_fwd_o(const tcar_dims_t* d, const tcar_tables_t* tab, const
     TCAR_CHECK_LAUNCH();
     return TCAR_OK;
   }
-  const int grid = grid_for_rows((long)bt->B * bt->T + bt->B);
+  const int grid = grid_for_rows(rows + bt->B);
   a.sig = tcar_sig(o);
-  if (d->ldh <= 256) TCAR_LAUNCH(gather_clip_fwd_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  if (rg) {
+    if (d->ldh <= 256) TCAR_LAUNCH((gather_clip_fwd_kernel<1, EmbRagged>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, er);
+    else TCAR_LAUNCH((gather_clip_fwd_kernel<2, EmbRagged>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, er);
+  } else if (d->ldh <= 256) TCAR_LAUNCH(gather_clip_fwd_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   else TCAR_LAUNCH(gather_clip_fwd_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;

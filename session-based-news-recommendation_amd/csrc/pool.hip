@@ -13,6 +13,8 @@
 // re-reads the T rows (L2 hits: they were just read for the scores).  Everything stays in registers — no LDS,
 // no cross-wave traffic.  This is the only softmax-attention on the executed graph (a single query per session),
 // far too small for MFMA: it is bound by the row reads.
+// (Serving also takes RAGGED batches — sessions of mixed lengths, include/tcar_ragged.h: the forward kernel then reads every
+//  session's first row and length from a descriptor; still no padding and no mask.  Training stays rectangular.)
 #include <type_traits>
 #include "tcar_common.h"
 
@@ -35,6 +37,11 @@ struct PoolArgs {
   TcarWait wait_q; // forward, optional: the click query q comes from another stream behind a completion flag — every wave waits
                    // for it itself, after the part of its work that does not need q (the slab fold, alpha1 / alpha_t scores)
 };
+// ragged forward (include/tcar_ragged.h): R session rows in all, session b owns the rows [off[b], off[b + 1]); PoolArgs::T is unused.
+// A kernel argument of its own: PoolArgs, and with it every rectangular kernel, stays what it was.
+struct PoolRagged { int R; const int32_t* off; };
+__device__ __forceinline__ const PoolRagged& pool_ragged(const PoolRagged& r) { return r; }
+__device__ __forceinline__ PoolRagged pool_ragged() { return PoolRagged{0, nullptr}; }
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 __device__ __forceinline__ float4 sig4(float4 v) {
@@ -45,14 +52,33 @@ __device__ __forceinline__ float4 mask4(float4 v, int col, int H) {
   return make_float4(col + 0 < H ? v.x : 0.f, col + 1 < H ? v.y : 0.f, col + 2 < H ? v.z : 0.f, col + 3 < H ? v.w : 0.f);
 }
 
-template <int NCH, bool SLABS = true>  // NCH = ceil(ldh/256); SLABS: the projections arrive as split-K slabs (else: finished rows)
-__global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
+// RAGGED: sessions of mixed lengths.  The wave reads the first row and the length of ITS session from rg.off (both wave uniform:
+// kept in scalar registers) where the rectangular form computes b * T and takes T from the launch; everything behind that — the
+// loops, the register-cached first positions, the slab fold order, the late-q wait — is the same code, so a session of length L
+// gets the bits the rectangular launch with T = L gives it.  Bad contents of rg.off cannot reach outside the R rows: the length
+// is clamped into 0 .. 40 and cut at R, a first row outside [0, R) makes the session empty.
+// first row of the wave's session (the rectangular form keeps the expressions it always had)
+#define POOL_FIRST_ (RAGGED ? (long)first_ : (long)b * T)
+// RG: nothing (the rectangular kernel: its signature and its code are what they were) or one PoolRagged.
+template <int NCH, bool SLABS = true, class... RG>  // NCH = ceil(ldh/256); SLABS: the projections arrive as split-K slabs (else: finished rows)
+__global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a, const RG... rg_) {
+  constexpr bool RAGGED = sizeof...(RG) > 0;
+  const PoolRagged& rg = pool_ragged(rg_...);
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.B) return;
-  const int T = a.T, H = a.H, ldh = a.ldh, ldt = a.ldt;
+  int len_ = 0, first_ = 0;          // (ragged) the session's length and first row
+  if constexpr (RAGGED) {
+    const int o0 = __builtin_amdgcn_readfirstlane(rg.off[b]), o1 = __builtin_amdgcn_readfirstlane(rg.off[b + 1]);
+    const bool in = o0 >= 0 && o0 < rg.R;
+    long len = (long)o1 - o0;
+    len = len < 0 ? 0 : len > TCAR_POS_VOCAB ? TCAR_POS_VOCAB : len;
+    if (in && len > rg.R - o0) len = rg.R - o0;
+    len_ = in ? (int)len : 0; first_ = in ? o0 : 0;
+  }
+  const int T = RAGGED ? len_ : a.T, H = a.H, ldh = a.ldh, ldt = a.ldt;
   const int ic = 2 * ldh, pt = 5 * ldt, ek = ic + pt;
-  const int BT = a.B * T;
+  const int BT = RAGGED ? rg.R : a.B * T;
   const int ptl = pt >> 2;   // float4 lanes of a publish-time row (80 for ldt = 64)
 
   // per-lane constants
@@ -88,7 +114,7 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
 #pragma unroll
     for (int u = 0; u < TU; ++u) {
       const int t = t0 + u;
-      const long row = (long)b * T + t;
+      const long row = POOL_FIRST_ + t;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int col = c * 256 + lane * 4;
@@ -111,7 +137,7 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
     for (int u = 0; u < TU; ++u) {
       const int t = t0 + u;
       if (t >= T) break;
-      const long row = (long)b * T + t;
+      const long row = POOL_FIRST_ + t;
       float s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
@@ -169,7 +195,7 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
       float4 ra[4][NCH], rb[4][NCH];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        const long row = (long)b * T + t0 + u;
+        const long row = POOL_FIRST_ + t0 + u;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
           const int col = c * 256 + lane * 4;
@@ -199,9 +225,9 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
   const float a2 = x2 / (wave_sum(x2) + 1e-9f);
   const float a3 = x3 / (wave_sum(x3) + 1e-9f);
   if (on) {
-    a.alpha[(long)b * T + lane] = a1;
-    a.alpha[(long)BT + (long)b * T + lane] = a2;
-    a.alpha[2L * BT + (long)b * T + lane] = a3;
+    a.alpha[POOL_FIRST_ + lane] = a1;
+    a.alpha[(long)BT + POOL_FIRST_ + lane] = a2;
+    a.alpha[2L * BT + POOL_FIRST_ + lane] = a3;
   }
   const float a12 = a1 + a2;
   float4 pa[NCH], pb[NCH];
@@ -228,7 +254,7 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
     float4 ra[4][NCH], rb[4][NCH], rp[4][2];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      const long row = (long)b * T + t0 + u;
+      const long row = POOL_FIRST_ + t0 + u;
       const bool in = t0 + u < T;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
@@ -272,6 +298,8 @@ __global__ __launch_bounds__(256) void attn_pool_fwd_kernel(const PoolArgs a) {
     if (l4 < ptl) st4(o + ic + l4 * 4, pp[c]);
   }
 }
+
+#undef POOL_FIRST_
 
 template <int NCH>
 __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(const PoolArgs a) {
@@ -525,19 +553,48 @@ __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(const PoolArgs a) {
 
 }  // namespace
 
+namespace {
+// a ragged descriptor as an argument (include/tcar_ragged.h): NULL pointers, R < B, R > 40 B
+bool bad_ragged(const tcar_ragged_t* rg, int B) {
+  return !rg || !rg->off || !rg->pos || rg->R < B || (long)rg->R > (long)TCAR_POS_VOCAB * B;
+}
+
+// both forward forms, rectangular (rg NULL: T rows per session) and ragged (T unused).  Finished rows: pre1 / pre2 in `p1` / `p2`,
+// out1 NULL; slabs: n1 / n2 partial products of stride `slab_stride`, the sums written to out1 / out2.
+int pool_fwd_launch(const tcar_dims_t* d, int B, int T, const tcar_ragged_t* rg, const float* x_icp, const float* x_pt, const float* p1,
+                    int n1, const float* p2, int n2, int64_t slab_stride, float* out1, float* out2, bool slabs, const float* q,
+                    const float* w_res1, const float* w_res2, float* pooled, float* alpha, void* stream, const TcarWait& wait_q) {
+  if (!d || B <= 0 || (d->ldh & 63) || d->ldh > 512 || 5 * d->ldt > 512) return TCAR_E_ARG;
+  if (rg ? bad_ragged(rg, B) : (T <= 0 || T > TCAR_POS_VOCAB)) return TCAR_E_ARG;
+  const int64_t rows = rg ? (int64_t)rg->R : (int64_t)B * T;
+  if (slabs && (n1 < 1 || n2 < 1 || !out1 || !out2 || slab_stride < rows * d->ldh)) return TCAR_E_ARG;
+  PoolArgs a{};
+  a.wait_q = wait_q;
+  a.B = B; a.T = rg ? 0 : T; a.H = d->H; a.ldh = d->ldh; a.ldt = d->ldt;
+  a.x_icp = x_icp; a.x_pt = x_pt; a.pre1 = p1; a.pre2 = p2; a.q = q; a.w1 = w_res1; a.w2 = w_res2;
+  if (slabs) { a.n1 = n1; a.n2 = n2; a.pre_stride = slab_stride; a.pre1_out = out1; a.pre2_out = out2; }
+  a.pooled = pooled; a.alpha = alpha;
+  const PoolRagged pr{rg ? rg->R : 0, rg ? rg->off : nullptr};
+  const int grid = (B + 3) / 4;
+  const bool wide = d->ldh > 256;
+#define POOL_FWD_(NCH_, SLABS_)                                                                                          \
+  do {                                                                                                                   \
+    if (rg) TCAR_LAUNCH((attn_pool_fwd_kernel<NCH_, SLABS_, PoolRagged>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, pr); \
+    else TCAR_LAUNCH((attn_pool_fwd_kernel<NCH_, SLABS_>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);              \
+  } while (0)
+  if (slabs) { if (wide) POOL_FWD_(2, true); else POOL_FWD_(1, true); }
+  else { if (wide) POOL_FWD_(2, false); else POOL_FWD_(1, false); }
+#undef POOL_FWD_
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+}  // namespace
+
 extern "C" int tcar_attn_pool_fwd(const tcar_dims_t* d, int B, int T, const float* x_icp, const float* x_pt,
                                   const float* pre1, const float* pre2, const float* q, const float* w_res1,
                                   const float* w_res2, float* pooled, float* alpha, void* stream) {
-  if (!d || B <= 0 || T <= 0 || T > TCAR_POS_VOCAB || (d->ldh & 63) || d->ldh > 512 || 5 * d->ldt > 512) return TCAR_E_ARG;
-  PoolArgs a{};
-  a.B = B; a.T = T; a.H = d->H; a.ldh = d->ldh; a.ldt = d->ldt;
-  a.x_icp = x_icp; a.x_pt = x_pt; a.pre1 = pre1; a.pre2 = pre2; a.q = q; a.w1 = w_res1; a.w2 = w_res2;
-  a.pooled = pooled; a.alpha = alpha;
-  const int grid = (B + 3) / 4;
-  if (d->ldh <= 256) TCAR_LAUNCH((attn_pool_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else TCAR_LAUNCH((attn_pool_fwd_kernel<2, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  TCAR_CHECK_LAUNCH();
-  return TCAR_OK;
+  return pool_fwd_launch(d, B, T, nullptr, x_icp, x_pt, pre1, 0, pre2, 0, 0, nullptr, nullptr, false, q, w_res1, w_res2, pooled, alpha,
+                         stream, TcarWait{});
 }
 
 extern "C" int tcar_attn_pool_fwd_slabs(const tcar_dims_t* d, int B, int T, const float* x_icp, const float* x_pt,
@@ -552,19 +609,25 @@ int tcar_attn_pool_fwd_slabs_w(const tcar_dims_t* d, int B, int T, const float* 
                                int n1, const float* pre2_slabs, int n2, int64_t slab_stride, float* pre1, float* pre2, const float* q,
                                const float* w_res1, const float* w_res2, float* pooled, float* alpha, void* stream,
                                const TcarWait& wait_q) {
-  if (!d || B <= 0 || T <= 0 || T > TCAR_POS_VOCAB || (d->ldh & 63) || d->ldh > 512 || 5 * d->ldt > 512) return TCAR_E_ARG;
-  if (n1 < 1 || n2 < 1 || !pre1 || !pre2 || slab_stride < (int64_t)B * T * d->ldh) return TCAR_E_ARG;
-  PoolArgs a{};
-  a.wait_q = wait_q;
-  a.B = B; a.T = T; a.H = d->H; a.ldh = d->ldh; a.ldt = d->ldt;
-  a.x_icp = x_icp; a.x_pt = x_pt; a.pre1 = pre1_slabs; a.pre2 = pre2_slabs; a.q = q; a.w1 = w_res1; a.w2 = w_res2;
-  a.n1 = n1; a.n2 = n2; a.pre_stride = slab_stride; a.pre1_out = pre1; a.pre2_out = pre2;
-  a.pooled = pooled; a.alpha = alpha;
-  const int grid = (B + 3) / 4;
-  if (d->ldh <= 256) TCAR_LAUNCH(attn_pool_fwd_kernel<1>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  else TCAR_LAUNCH(attn_pool_fwd_kernel<2>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  TCAR_CHECK_LAUNCH();
-  return TCAR_OK;
+  return pool_fwd_launch(d, B, T, nullptr, x_icp, x_pt, pre1_slabs, n1, pre2_slabs, n2, slab_stride, pre1, pre2, true, q, w_res1, w_res2,
+                         pooled, alpha, stream, wait_q);
+}
+
+// ---- ragged forms (include/tcar_ragged.h)
+extern "C" int tcar_attn_pool_fwd_ragged(const tcar_dims_t* d, int B, const tcar_ragged_t* rg, const float* x_icp, const float* x_pt,
+                                         const float* pre1, const float* pre2, const float* q, const float* w_res1,
+                                         const float* w_res2, float* pooled, float* alpha, void* stream) {
+  if (!rg) return TCAR_E_ARG;
+  return pool_fwd_launch(d, B, 0, rg, x_icp, x_pt, pre1, 0, pre2, 0, 0, nullptr, nullptr, false, q, w_res1, w_res2, pooled, alpha, stream,
+                         TcarWait{});
+}
+extern "C" int tcar_attn_pool_fwd_slabs_ragged(const tcar_dims_t* d, int B, const tcar_ragged_t* rg, const float* x_icp,
+                                               const float* x_pt, const float* pre1_slabs, int n1, const float* pre2_slabs, int n2,
+                                               int64_t slab_stride, float* pre1, float* pre2, const float* q, const float* w_res1,
+                                               const float* w_res2, float* pooled, float* alpha, void* stream) {
+  if (!rg) return TCAR_E_ARG;
+  return pool_fwd_launch(d, B, 0, rg, x_icp, x_pt, pre1_slabs, n1, pre2_slabs, n2, slab_stride, pre1, pre2, true, q, w_res1, w_res2,
+                         pooled, alpha, stream, TcarWait{});
 }
 
 extern "C" int tcar_attn_pool_bwd(const tcar_dims_t* d, int B, int T, const float* x_icp, const float* x_pt,

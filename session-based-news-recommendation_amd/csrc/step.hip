@@ -346,10 +346,13 @@ struct ScoreOut {
   // forward_impl); anchor_done says so
   const int32_t* label = nullptr; const float* E = nullptr; int64_t ldE = 0; bool anchor_done = false;
 };
+// `rg`: the sessions have mixed lengths (include/tcar_ragged.h) — bt's per-row arrays are flat [R]; the row count B * T becomes R
+// everywhere (projection problems, the psplit rule, the slab stride) and the gather and the pool launch in their ragged forms.
+// Nothing else of the head looks at T.
 template <class Hook>
 int session_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const Geo& g, void* stream, bool planes, int ei, Hook hook,
-                    ScoreOut* so = nullptr) {
-  const int B = bt->B, BT = bt->B * bt->T;
+                    ScoreOut* so = nullptr, const tcar_ragged_t* rg = nullptr) {
+  const int B = bt->B, BT = rg ? rg->R : bt->B * bt->T;
   tcar_tables_t tab;
   tables_of(c, tab);
   // The click-query MLP (q1, q: modules.py:138-139) needs only the gathered click-time rows: with flag forks it runs as ONE
@@ -363,7 +366,7 @@ int session_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const Geo& g, v
   TcarOpt og = opt_of(c);
   if (sq) og.sig = fork_arm(c, FK_GATHER);
   if (ei >= 0) (void)hipEventRecord((hipEvent_t)c->ev_start[4 * c->ev_n + ei], (hipStream_t)stream);     // kind 4: the step's own gather
-  RET(tcar_gather_clip_fwd_o(&c->d, &tab, bt, c->x_icp, c->x_pt, c->x_act, c->click_t, stream, &og));
+  RET(tcar_gather_clip_fwd_rg(&c->d, &tab, bt, rg, c->x_icp, c->x_pt, c->x_act, c->click_t, stream, &og));
   if (ei >= 0) (void)hipEventRecord((hipEvent_t)c->ev_stop[4 * c->ev_n + ei], (hipStream_t)stream);
   const bool qside = sq && fork_commit(c, FK_GATHER, og);       // (the throughput form of the gather carries no flag)
   if (qside) {
@@ -435,7 +438,13 @@ int session_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const Geo& g, v
     RET(small_gemm(c, 0, 1, &p, stream));
   }
   RET(hook(2, &op));
-  if (psplit)
+  if (rg && psplit)
+    RET(tcar_attn_pool_fwd_slabs_ragged(&c->d, B, rg, c->x_icp, c->x_pt, c->proj_slabs, n1, c->proj_slabs + n1 * stride, n2, stride,
+                                        c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES), c->pooled, c->alpha, stream));
+  else if (rg)
+    RET(tcar_attn_pool_fwd_ragged(&c->d, B, rg, c->x_icp, c->x_pt, c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES),
+                                  c->pooled, c->alpha, stream));
+  else if (psplit)
     RET(tcar_attn_pool_fwd_slabs_w(&c->d, B, bt->T, c->x_icp, c->x_pt, c->proj_slabs, n1, c->proj_slabs + n1 * stride, n2, stride,
                                    c->pre1, c->pre2, c->q, W(c, TCAR_V_M_WRES), W(c, TCAR_V_S_WRES), c->pooled, c->alpha, stream, wq));
   else
@@ -547,8 +556,13 @@ struct Head {
   CeWs w{};
   hipStream_t s2 = nullptr;
 };
-int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, void* stream, float rest_lr, bool train_index, Head& h) {
+// `rg`: the head of a ragged batch (include/tcar_ragged.h) — serving only: a training head is an argument error.
+int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, void* stream, float rest_lr, bool train_index, Head& h,
+                 const tcar_ragged_t* rg = nullptr) {
   RET(check_ctx(c, bt));
+  if (rg && (train_index || rest_lr >= 0.f || !rg->off || !rg->pos || rg->R < bt->B || (int64_t)rg->R > (int64_t)TCAR_POS_VOCAB * bt->B ||
+             bt->K != 0 || bt->neg))
+    return TCAR_E_ARG;
   const Geo g(c->d);
   const int B = bt->B, BT = bt->B * bt->T;
   // The candidate-side time block of E depends only on the time tables: it is rebuilt on the auxiliary stream while
@@ -619,7 +633,7 @@ int forward_head(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, 
     RET(fork_go(c, FK_PROJ, s1, s2, c->ev[0]));      // (the rest pass reads nothing the projections write: timing only)
     // on the aux stream, behind whatever the main stream has enqueued so far; ev[1] = "aux stream ready for the logits GEMM"
     return rest_pass(c, g, rest_lr, s2, c->ev[1], [] { return (int)TCAR_OK; });
-  }, onehot ? &so : nullptr));
+  }, onehot ? &so : nullptr, rg));
   // sort index of the item rows (feed only): on the aux stream BEHIND the rest pass — the logits GEMM does not wait for it (ev[1]
   // was recorded in front of it), the backward does
   if (train_index && sorted_rows(c, bt)) {
@@ -1293,8 +1307,9 @@ int check_serve_desc(const tcar_serve_t* s, const tcar_window_t* w, const tcar_q
 
 // Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, the label scores, then
 // serve_fold over the whole catalog and the finishing launch.  w / q NULL: the unwindowed / uncapped step.
-extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
-                                     const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+namespace {
+int serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_serve_t* s,
+               const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
   if (!c || !bt || bt->B < 0) return TCAR_E_ARG;
   RET(check_serve_desc(s, w, q, true));
   if (s->state_bytes < tcar_select_state_bytes(bt->B, s->k)) return TCAR_E_ARG;
@@ -1305,7 +1320,7 @@ extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt
   const Geo g(c->d);
   const int B = bt->B, k = s->k;
   Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
   fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   const float* lab = bt->label ? s->lab_score : nullptr;
   if (lab)
@@ -1313,6 +1328,12 @@ extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt
                           g.ek, c->scoring, bt->label, s->lab_score, stream));
   RET(serve_fold(c, B, c->a16h, c->a16l, 0, bt->label, lab, s, w, q, stream));
   return tcar_select_finish(B, k, s->state, lab, s->topk, s->score, lab ? s->rank : nullptr, lab ? s->ce : nullptr, stream);
+}
+}  // namespace
+
+extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
+                                     const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  return serve_step(c, bt, nullptr, refresh_time, s, w, q, stream);
 }
 
 extern "C" int tcar_serve_step_window(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
@@ -1326,7 +1347,8 @@ extern "C" int tcar_serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int 
 
 // Candidate-list scoring (include/tcar_cand.h): the head of a forward pass as tcar_serve_step_quota runs it, then the [B, C] gathered
 // dots from the operands the panel GEMM would contract and, when the descriptor asks for any of them, the ranks and metrics.
-extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_cand_t* d, void* stream) {
+namespace {
+int cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_cand_t* d, void* stream) {
   if (!c || !bt || bt->B < 0 || !d) return TCAR_E_ARG;
   if (d->C < 1 || d->C > CAND_MAX_C || d->ld_cand < d->C || !d->cand || !d->score) return TCAR_E_ARG;
   if (!d->clicked && (d->counts || d->metrics)) return TCAR_E_ARG;
@@ -1336,13 +1358,18 @@ extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
   const Geo g(c->d);
   const int B = bt->B, C = d->C;
   Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
   fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
                        c->scoring, d->cand, d->ld_cand, d->score, C, stream));
   if (!d->rank_of && !d->order && !d->counts && !d->metrics) return TCAR_OK;
   return tcar_cand_rank(B, C, d->score, C, d->cand, d->ld_cand, d->clicked, d->ld_cand, d->rank_of, d->order, d->counts, d->metrics,
                         stream);
+}
+}  // namespace
+
+extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_cand_t* d, void* stream) {
+  return cand_step(c, bt, nullptr, refresh_time, d, stream);
 }
 
 namespace {
@@ -1359,14 +1386,15 @@ int check_retrieve_desc(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_
 // shaped like serve_fold — per panel the evaluation form of the logits GEMM in the COARSE precision (the hi planes alone on a
 // split-bf16 engine, whatever its nsplit; the fp32 GEMM on the fp32 engine, which has no cheaper operands) into d->panel_buf, folded
 // by tcar_retrieve_panel while the panel is cache-warm — and the finishing launch.
-int retrieve_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d, void* stream) {
+int retrieve_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_retrieve_t* d,
+                  void* stream) {
   RET(check_ctx(c, bt));
   if (c->scoring ? (!c->a16h || !c->e16h) : !c->attout) return TCAR_E_ARG;
   const Geo g(c->d);
   const int B = bt->B, C = d->C;
   const tcar_window_t* w = d->window;
   Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h));
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
   fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   RET(tcar_retrieve_reset(B, C, d->state, stream));
   for (int n0 = 0; n0 < g.N; n0 += d->panel) {
@@ -1384,24 +1412,21 @@ int retrieve_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time,
   }
   return tcar_retrieve_finish(B, C, d->state, d->ids, d->scores, stream);
 }
-}  // namespace
 
-// Retrieval (include/tcar_retrieve.h): a shortlist of C items per session from coarse scores, without the [B, N] logits.
-extern "C" int tcar_retrieve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d, void* stream) {
+int retrieve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_retrieve_t* d,
+                  void* stream) {
   RET(check_retrieve_desc(c, bt, d));
   if (bt->B == 0) return TCAR_OK;
-  return retrieve_impl(c, bt, refresh_time, d, stream);
+  return retrieve_impl(c, bt, rg, refresh_time, d, stream);
 }
 
-// Two-stage recommendation with one session forward: the retrieval step, the shortlist's exact scores from the context's own
-// operands (as tcar_cand_step calls tcar_cand_scores), its list order, and the first k of it.
-extern "C" int tcar_retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d,
-                                         const tcar_rerank_t* r, void* stream) {
+int retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_retrieve_t* d,
+                         const tcar_rerank_t* r, void* stream) {
   RET(check_retrieve_desc(c, bt, d));
   if (!r || r->k < 1 || r->k > SEL_MAX_K || r->k > d->C || !r->cand_score || !r->order || !r->topk) return TCAR_E_ARG;
   if (bt->B == 0) return TCAR_OK;
   if (c->scoring == 3 && (!c->a16l || !c->e16l)) return TCAR_E_ARG;
-  RET(retrieve_impl(c, bt, refresh_time, d, stream));
+  RET(retrieve_impl(c, bt, rg, refresh_time, d, stream));
   const Geo g(c->d);
   const int B = bt->B, C = d->C;
   RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
@@ -1409,7 +1434,48 @@ extern "C" int tcar_retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t
   RET(tcar_cand_rank(B, C, r->cand_score, C, d->ids, C, nullptr, 0, r->rank_of, r->order, nullptr, nullptr, stream));
   return tcar_rerank_take(B, C, r->k, d->ids, r->cand_score, r->order, r->topk, r->score, stream);
 }
+}  // namespace
 
+// Retrieval (include/tcar_retrieve.h): a shortlist of C items per session from coarse scores, without the [B, N] logits.
+extern "C" int tcar_retrieve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d, void* stream) {
+  return retrieve_step(c, bt, nullptr, refresh_time, d, stream);
+}
+
+// Two-stage recommendation with one session forward: the retrieval step, the shortlist's exact scores from the context's own
+// operands (as tcar_cand_step calls tcar_cand_scores), its list order, and the first k of it.
+extern "C" int tcar_retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d,
+                                         const tcar_rerank_t* r, void* stream) {
+  return retrieve_rerank_step(c, bt, nullptr, refresh_time, d, r, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ragged batches (include/tcar_ragged.h): the ragged head, then the body the rectangular twin runs.  A NULL descriptor is an argument
+// error here (it is what selects the rectangular head in the shared bodies); its contents are checked by forward_head.
+extern "C" int tcar_ragged_abi_version(void) { return TCAR_RAGGED_ABI_VERSION; }
+
+extern "C" int tcar_ragged_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, void* stream) {
+  if (!rg) return TCAR_E_ARG;
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
+  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
+  return TCAR_OK;
+}
+extern "C" int tcar_serve_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
+                                      const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  return rg ? serve_step(c, bt, rg, refresh_time, s, w, q, stream) : (int)TCAR_E_ARG;
+}
+extern "C" int tcar_cand_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
+                                     const tcar_cand_t* d, void* stream) {
+  return rg ? cand_step(c, bt, rg, refresh_time, d, stream) : (int)TCAR_E_ARG;
+}
+extern "C" int tcar_retrieve_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
+                                         const tcar_retrieve_t* d, void* stream) {
+  return rg ? retrieve_step(c, bt, rg, refresh_time, d, stream) : (int)TCAR_E_ARG;
+}
+extern "C" int tcar_retrieve_rerank_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
+                                                const tcar_retrieve_t* d, const tcar_rerank_t* r, void* stream) {
+  return rg ? retrieve_rerank_step(c, bt, rg, refresh_time, d, r, stream) : (int)TCAR_E_ARG;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Catalog-sharded step (sharded.py): the same op-level launchers, cut at the points where the ranks exchange data.

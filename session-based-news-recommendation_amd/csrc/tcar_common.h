@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/tcar_hip.h"
+#include "../../include/tcar_ragged.h"      // (tcar_ragged_t: the gather and the pool take it; brings the serving layers with it)
 
 #define TCAR_CHECK_LAUNCH()                                   \
   do {                                                        \
@@ -203,6 +204,9 @@ int tcar_attout_finish_scores_a(const tcar_dims_t* d, const float* const time_ta
                                 int64_t p_inner, float* tclip, const int32_t* label, const float* E, int64_t ldE, void* stream);
 int tcar_gather_clip_fwd_o(const tcar_dims_t* d, const tcar_tables_t* tab, const tcar_batch_t* bt, float* x_icp, float* x_pt,
                            float* x_act, float* click_t, void* stream, TcarOpt* o);
+// (rg NULL: the rectangular call; else the ragged one of include/tcar_ragged.h — pos[row] in place of row % T over rg->R rows)
+int tcar_gather_clip_fwd_rg(const tcar_dims_t* d, const tcar_tables_t* tab, const tcar_batch_t* bt, const tcar_ragged_t* rg, float* x_icp,
+                            float* x_pt, float* x_act, float* click_t, void* stream, TcarOpt* o);
 int tcar_query_mlp_o(const tcar_dims_t* d, int B, const float* click_t, const float* q1_w, const float* q1_b, const float* q2_w,
                      const float* q2_b, float* q1, float* q, void* stream, TcarOpt* o);
 int tcar_attn_pool_bwd_slabs_o(const tcar_dims_t* d, int B, int T, const float* x_icp, const float* x_pt, const float* pre1,

@@ -440,6 +440,7 @@ class DPEngine(TcarEngine):
     def train_step(self, batch, bt=None, cap_rows: Optional[int] = None, T: Optional[int] = None, K: Optional[int] = None):
         """`batch` may be None for a rank whose shard of the global batch is empty (it still joins the collectives).
         T / K: accepted for interface parity with sharded.ShardedEngine (an empty rank needs them there)."""
+        self._refuse_ragged(batch, bt, "train_step")
         if batch is None and bt is None:
             self.Gx.zero_()
             self.big.zero_()
@@ -479,6 +480,7 @@ class DPEngine(TcarEngine):
             self.backward_local(bt)
 
     def loss_and_grads(self, batch, bt=None, cap_rows: Optional[int] = None):
+        self._refuse_ragged(batch, bt, "loss_and_grads")
         bt = bt or self.upload(batch)
         self._local(bt)
         self.finish_backward(bt, cap_rows)

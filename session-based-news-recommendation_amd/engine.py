@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Cand, Dims, Grads, Rerank, Retrieve, Segments, Quota, Serve, Tables, Window, check
+from ._lib import Batch, Cand, Dims, Grads, Ragged, Rerank, Retrieve, Segments, Quota, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -431,11 +431,13 @@ class TcarEngine(OpLevelStep):
         return {n: float(self._use_np[i] * d[i] + p[i]) for i, n in enumerate(VAR_ORDER)}
 
     # ------------------------------------------------------------------------------------------- workspace
-    def _ensure_work(self, B: int, T: int):
-        """the workspace covers the largest B * T and the largest B seen (WORK + the materialised part of the scoring family)"""
+    def _ensure_work(self, B: int, T: int, rows: Optional[int] = None):
+        """the workspace covers the largest row count (B * T; `rows` = R of a ragged batch) and the largest B seen (WORK + the
+        materialised part of the scoring family)"""
         g, kinds = self.geo, ()
-        if B * T > self.work_rows:
-            self.work_rows, kinds = B * T, ("r", "3r")
+        rows = B * T if rows is None else int(rows)
+        if rows > self.work_rows:
+            self.work_rows, kinds = rows, ("r", "3r")
         if B > self.work_B:
             self.work_B, kinds = B, kinds + ("B",)
         if kinds:
@@ -517,18 +519,24 @@ class TcarEngine(OpLevelStep):
     # ----------------------------------------------------------------------------------------------- batch
     def upload(self, batch: Dict[str, np.ndarray]) -> Batch:
         """Pack the feed arrays into ONE int32 buffer, one H2D copy; returns the C batch descriptor."""
-        seq = np.ascontiguousarray(batch["seq"], dtype=np.int32)
-        B, T = seq.shape
-        if T > 40:
-            raise IndexError("session longer than the 40-row position table (model_combine.py:57)")
-        if seq.min() < 1 or seq.max() > self.geo.N:
-            raise IndexError("item id outside [1, N]")
-        neg = batch.get("neg", None)
-        K = 0 if neg is None or np.asarray(neg).size == 0 else np.asarray(neg).shape[1]
-        parts = [seq.reshape(-1)] + [np.asarray(batch[k], dtype=np.int32).reshape(-1) for k in
-                                     ("pm", "pd", "pw", "ph", "pmi", "gap", "cw", "ch", "label")]
-        if K:
-            parts.append(np.asarray(neg, dtype=np.int32).reshape(-1))
+        ragged = "len" in batch                  # a ragged feed (sessions of mixed lengths): flat [R] rows + len [B]
+        if ragged:
+            parts, B, T, rows = self._ragged_parts(batch)
+            K = 0
+        else:
+            seq = np.ascontiguousarray(batch["seq"], dtype=np.int32)
+            B, T = seq.shape
+            rows = B * T
+            if T > 40:
+                raise IndexError("session longer than the 40-row position table (model_combine.py:57)")
+            if seq.min() < 1 or seq.max() > self.geo.N:
+                raise IndexError("item id outside [1, N]")
+            neg = batch.get("neg", None)
+            K = 0 if neg is None or np.asarray(neg).size == 0 else np.asarray(neg).shape[1]
+            parts = [seq.reshape(-1)] + [np.asarray(batch[k], dtype=np.int32).reshape(-1) for k in
+                                         ("pm", "pd", "pw", "ph", "pmi", "gap", "cw", "ch", "label")]
+            if K:
+                parts.append(np.asarray(neg, dtype=np.int32).reshape(-1))
         total = sum(x.size for x in parts)
         if self.pin is None or self.pin[0].numel() < total:
             n = max(total, 1 << 16)
@@ -551,12 +559,12 @@ class TcarEngine(OpLevelStep):
         bt.B, bt.T, bt.K = B, T, K
         o = 0
         bt.seq = base
-        o += B * T
+        o += rows
         for k in range(5):
             bt.pub[k] = base + 4 * o
-            o += B * T
+            o += rows
         bt.gap = base + 4 * o
-        o += B * T
+        o += rows
         bt.cw = base + 4 * o
         o += B
         bt.ch = base + 4 * o
@@ -564,9 +572,61 @@ class TcarEngine(OpLevelStep):
         bt.label = base + 4 * o
         o += B
         bt.neg = (base + 4 * o) if K else None
-        bt._seq_t = self.ibufs[i][:B * T]           # tensor view of `seq` (ids of the sparse-row exchange)
+        o += B * K
+        if ragged:                               # off [B + 1] | pos [R] ride behind the feed in the same buffer
+            rg = Ragged()
+            rg.R, rg.off, rg.pos = rows, base + 4 * o, base + 4 * (o + B + 1)
+            bt._rg, bt._len = rg, parts[-2][1:] - parts[-2][:-1]
+        bt._seq_t = self.ibufs[i][:rows]            # tensor view of `seq` (ids of the sparse-row exchange)
         bt._keep = self.ibufs[i]
         return bt
+
+    @staticmethod
+    def is_ragged(batch) -> bool:
+        """is this feed a ragged one (flat rows + "len")?"""
+        return isinstance(batch, dict) and "len" in batch
+
+    @staticmethod
+    def _sessions(batch) -> int:
+        """the number of sessions of a feed, rectangular or ragged"""
+        return int(np.asarray(batch["len"]).shape[0]) if "len" in batch else int(np.asarray(batch["seq"]).shape[0])
+
+    @staticmethod
+    def _rows(bt: Batch) -> int:
+        """session rows of an uploaded batch: R of a ragged one, B * T else"""
+        rg = getattr(bt, "_rg", None)
+        return int(rg.R) if rg is not None else bt.B * bt.T
+
+    def _ragged_parts(self, batch):
+        """A ragged feed, validated before anything is uploaded -> (the int32 arrays of the packed buffer — the feed's own, then
+        off [B + 1] and pos [R] —, B, the longest length, R).  "label" is optional (zeros)."""
+        ln = np.asarray(batch["len"])
+        if ln.ndim != 1 or ln.size == 0 or not np.issubdtype(ln.dtype, np.integer):
+            raise ValueError("len must be an integer array [B] of at least one session")
+        if "neg" in batch and batch["neg"] is not None and np.asarray(batch["neg"]).size:
+            raise ValueError("a ragged feed carries no negatives (training stays rectangular)")
+        if int(ln.min()) < 1 or int(ln.max()) > 40:
+            raise IndexError("session length outside [1, 40], the 40-row position table (model_combine.py:57)")
+        B, R = int(ln.size), int(ln.sum())
+        seq = np.ascontiguousarray(batch["seq"], dtype=np.int32).reshape(-1)
+        if seq.size != R:
+            raise ValueError("sum(len) = %d, but seq holds %d rows" % (R, seq.size))
+        if seq.min() < 1 or seq.max() > self.geo.N:
+            raise IndexError("item id outside [1, N]")
+        parts = [seq]
+        for k in ("pm", "pd", "pw", "ph", "pmi", "gap"):
+            x = np.asarray(batch[k], dtype=np.int32).reshape(-1)
+            if x.size != R:
+                raise ValueError("sum(len) = %d, but %s holds %d rows" % (R, k, x.size))
+            parts.append(x)
+        for k in ("cw", "ch", "label"):
+            x = np.zeros(B, dtype=np.int32) if k == "label" and k not in batch else np.asarray(batch[k], dtype=np.int32).reshape(-1)
+            if x.size != B:
+                raise ValueError("%s must hold one entry per session, B = %d" % (k, B))
+            parts.append(x)
+        from .host.data import ragged_offsets
+        off, pos = ragged_offsets(ln)
+        return parts + [off, pos], B, int(ln.max()), R
 
     # ------------------------------------------------------------------------------ native (C++) step driver
     # second HIP stream for the independent dE / candidate-time chains (C++ driver only).  None: from TCAR_NO_OVERLAP when the engine
@@ -776,6 +836,7 @@ class TcarEngine(OpLevelStep):
         arena + the item rows that step gathers first, the other item rows on the aux stream beside its forward pass
         (tcar_train_step_deferred) — or by flush(); results are identical, the HBM-bound pass over the item table leaves
         the critical path."""
+        self._refuse_ragged(batch, bt, "train_step")
         bt = bt or self.upload(batch)
         if self.native:
             self._ensure_work(bt.B, bt.T)
@@ -796,6 +857,7 @@ class TcarEngine(OpLevelStep):
         return self._loss_view(bt)
 
     def loss_and_grads(self, batch, bt: Optional[Batch] = None) -> torch.Tensor:
+        self._refuse_ragged(batch, bt, "loss_and_grads")
         self.flush()
         bt = bt or self.upload(batch)
         if self.native:
@@ -823,14 +885,21 @@ class TcarEngine(OpLevelStep):
     def reset_coverage(self):
         self._seen.zero_()
 
-    def eval_diversity(self, bt: Batch, topk: torch.Tensor):
+    def eval_diversity(self, bt: Batch, topk: torch.Tensor, block=None):
         """getILD / getUnexp pair counts of the sessions of `bt` for their top-k lists (int32 [B] each, on the device) and
-        the recommended items marked in the coverage map; divide with host.metrics.diversity_from_counts."""
-        B, k = bt.B, int(topk.shape[1])
+        the recommended items marked in the coverage map; divide with host.metrics.diversity_from_counts.
+        block = (row0, B, T): the B sessions of one length T whose item rows start at flat row `row0` of a ragged `bt` (the sessions
+        of one packed feed, host.data.pack_sessions), `topk` their lists."""
+        if block is None and getattr(bt, "_rg", None) is not None:
+            raise ValueError("the diversity counts take sessions of one length: name a (row0, B, T) block of the ragged batch")
+        row0, B, T = (0, bt.B, bt.T) if block is None else (int(x) for x in block)
+        if row0 < 0 or B < 1 or T < 1 or row0 + B * T > self._rows(bt):
+            raise ValueError("block = (row0, B, T) must lie inside the batch's rows")
+        k = int(topk.shape[1])
         topk = topk[:B].contiguous()
         out = torch.empty(3, B, dtype=torch.int32, device=self.dev)
         p = self._p
-        check(self.lib.tcar_eval_diversity(B, bt.T, k, self.geo.N, p(topk), C.c_void_p(bt.seq), p(self._cat), p(out[0]), p(out[1]),
+        check(self.lib.tcar_eval_diversity(B, T, k, self.geo.N, p(topk), C.c_void_p(bt.seq + 4 * row0), p(self._cat), p(out[0]), p(out[1]),
                                            p(out[2]), C.c_void_p(self._seen.data_ptr()), self._stream()), "tcar_eval_diversity")
         return out[0], out[1], out[2]
 
@@ -841,6 +910,7 @@ class TcarEngine(OpLevelStep):
     def eval_step(self, batch, k: int = 20, bt: Optional[Batch] = None, keep_logits: bool = False):
         """sess.run([softmax_input, cross_loss]) (model_combine.py:283) + rank / top-k on device.
         Returns (rank[B] int32, topk[B,k] int32, ce[B] f32[, logits [B,N]])."""
+        self._refuse_ragged(batch, bt, "eval_step")
         self.flush()
         bt = bt or self.upload(batch)
         B = bt.B
@@ -969,7 +1039,7 @@ class TcarEngine(OpLevelStep):
             raise _lib.TcarError("streamed selection needs the whole catalog on this engine (no shard)")
         k, panel, quota = self._serve_request(k, panel, window, max_per_category, g.Npad)
         B = bt.B
-        self._ensure_work(B, bt.T)
+        self._ensure_work(B, bt.T, self._rows(bt))
         wb = self.work_B
         state_words = 2 * k + 4                  # tcar_select_state_bytes(B, k) / (4 B)
         specs = [Spec("panel_buf", (wb, panel), F32), Spec("sel_state", (wb, state_words), I32), Spec("lab_score", (wb,), F32),
@@ -986,11 +1056,8 @@ class TcarEngine(OpLevelStep):
         if not labelled:
             bt = self._without_neg(bt, label=False)
         w = self._window(window, B) if window is not None else None
-        check(self.lib.tcar_serve_step_quota(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(s),
-                                             C.byref(w) if w is not None else None, C.byref(quota) if quota is not None else None,
-                                             self._stream()), "tcar_serve_step_quota")
-        self._time_dirty = False
-        self.poll_fork_errors()
+        self._head_step("serve_step_quota", bt, C.byref(s), C.byref(w) if w is not None else None,
+                        C.byref(quota) if quota is not None else None)
         return self.sel_rank[:B], self.sel_topk[:B], self.sel_ce[:B], self.sel_score[:B]
 
     @staticmethod
@@ -1002,7 +1069,28 @@ class TcarEngine(OpLevelStep):
         if not label:
             nb.label = None
         nb._keep = getattr(bt, "_keep", None)
+        for n in ("_rg", "_len", "_seq_t"):          # (a ragged batch stays one)
+            if hasattr(bt, n):
+                setattr(nb, n, getattr(bt, n))
         return nb
+
+    def _refuse_ragged(self, batch, bt, what: str) -> None:
+        """training and the materialised evaluation are rectangular: a ragged feed is refused before anything is uploaded"""
+        if self.is_ragged(batch) or getattr(bt, "_rg", None) is not None:
+            raise ValueError("%s takes a rectangular feed: ragged batches are for the streamed serving calls (eval_step_streamed, "
+                             "recommend, retrieve, recommend_two_stage, score_candidates)" % what)
+
+    def _head_step(self, name: str, bt: Batch, *args) -> None:
+        """One serving step on the uploaded batch: tcar_<name>(ctx, bt, refresh_time, *args, stream), or, where `bt` is ragged, its
+        twin of include/tcar_ragged.h (`tcar_serve_step_ragged` for serve_step_quota), which takes the descriptor behind bt."""
+        rg = getattr(bt, "_rg", None)
+        if rg is None:
+            fn, head = "tcar_" + name, (C.byref(bt),)
+        else:
+            fn, head = "tcar_" + {"serve_step_quota": "serve_step"}.get(name, name) + "_ragged", (C.byref(bt), C.byref(rg))
+        check(getattr(self.lib, fn)(C.byref(self._ctx()), *head, int(self._time_dirty), *args, self._stream()), fn)
+        self._time_dirty = False
+        self.poll_fork_errors()
 
     def eval_step_streamed(self, batch, k: int = 20, bt: Optional[Batch] = None, panel: Optional[int] = None, window=None,
                            max_per_category: Optional[int] = None):
@@ -1023,12 +1111,19 @@ class TcarEngine(OpLevelStep):
     def _recommend_inputs(self, batch, exclude_seen: bool, exclude):
         """the uploaded sessions of a recommend() call and their exclusion lists [B, X] on the device (None: none)"""
         if "label" not in batch:
-            batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
-        if "neg" in batch:
+            batch = dict(batch, label=np.zeros(self._sessions(batch), dtype=np.int32))
+        if "neg" in batch and not self.is_ragged(batch):
             batch = {n: v for n, v in batch.items() if n != "neg"}
         bt = self.upload(batch)
         parts = []
-        if exclude_seen:                 # built on the device from the uploaded ids: 1-based, so id 0 (a pad) becomes -1
+        if exclude_seen and getattr(bt, "_rg", None) is not None:
+            # a ragged batch: [B, max len] on the host, -1 behind each session's own items
+            ln = bt._len
+            own = np.full((bt.B, bt.T), -1, dtype=np.int32)
+            own[np.repeat(np.arange(bt.B), ln), np.arange(int(ln.sum())) - np.repeat(np.cumsum(ln) - ln, ln)] = \
+                np.asarray(batch["seq"], dtype=np.int32).reshape(-1) - 1
+            parts.append(torch.from_numpy(own).to(self.dev))
+        elif exclude_seen:               # built on the device from the uploaded ids: 1-based, so id 0 (a pad) becomes -1
             parts.append(bt._seq_t.view(bt.B, bt.T) - 1)
         if exclude is not None:
             ex = np.ascontiguousarray(np.asarray(exclude, dtype=np.int32).reshape(bt.B, -1))
@@ -1088,14 +1183,15 @@ class TcarEngine(OpLevelStep):
             raise _lib.TcarError("candidate scoring needs the whole catalog on one engine (no shard)")
         if bt is None:
             if "label" not in batch:
-                batch = dict(batch, label=np.zeros(np.asarray(batch["seq"]).shape[0], dtype=np.int32))
-            batch = {n: v for n, v in batch.items() if n != "neg"}
-        B = bt.B if bt is not None else int(np.asarray(batch["seq"]).shape[0])
+                batch = dict(batch, label=np.zeros(self._sessions(batch), dtype=np.int32))
+            if not self.is_ragged(batch):
+                batch = {n: v for n, v in batch.items() if n != "neg"}
+        B = bt.B if bt is not None else self._sessions(batch)
         cand, clk = self._cand_request(B, candidates, clicked)
         self.flush()
         bt = self._without_neg(bt if bt is not None else self.upload(batch), label=False)
         C_ = cand.shape[1]
-        self._ensure_work(B, bt.T)
+        self._ensure_work(B, bt.T, self._rows(bt))
         wb = self.work_B
         # cand and clicked are the two planes of ONE workspace entry: they go up in one copy
         self.ws.ensure([Spec("cand_in", (2, wb, C_), I32), Spec("cand_score", (wb, C_), F32), Spec("cand_rank", (2, wb, C_), I32),
@@ -1109,10 +1205,7 @@ class TcarEngine(OpLevelStep):
         d.score, d.rank_of, d.order = self.cand_score.data_ptr(), self.cand_rank[0].data_ptr(), self.cand_rank[1].data_ptr()
         if clk is not None:
             d.clicked, d.counts, d.metrics = self.cand_in[1].data_ptr(), self.cand_counts.data_ptr(), self.cand_metrics.data_ptr()
-        check(self.lib.tcar_cand_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), self._stream()),
-              "tcar_cand_step")
-        self._time_dirty = False
-        self.poll_fork_errors()
+        self._head_step("cand_step", bt, C.byref(d))
         return CandResult(self.cand_score[:B], self.cand_rank[0, :B], self.cand_rank[1, :B],
                           self.cand_counts[:B] if clk is not None else None, self.cand_metrics[:B] if clk is not None else None)
 
@@ -1141,7 +1234,7 @@ class TcarEngine(OpLevelStep):
         self.flush()
         bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
         B = bt.B
-        self._ensure_work(B, bt.T)
+        self._ensure_work(B, bt.T, self._rows(bt))
         wb = self.work_B
         state_words = 2 * C_ + 4                 # tcar_retrieve_state_bytes(B, C) / (4 B)
         specs = [Spec("panel_buf", (wb, panel), F32), Spec("rt_state", (wb, state_words), I32), Spec("rt_ids", (wb, C_), I32),
@@ -1167,17 +1260,13 @@ class TcarEngine(OpLevelStep):
             d.window = C.addressof(w)            # (w stays alive until the call has returned)
         bt = self._without_neg(bt, label=False)
         if k is None:
-            check(self.lib.tcar_retrieve_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), self._stream()),
-                  "tcar_retrieve_step")
+            self._head_step("retrieve_step", bt, C.byref(d))
         else:
             r = Rerank()
             r.k, r.cand_score = k, self.rt_exact.data_ptr()
             r.rank_of, r.order = self.rt_rank[0].data_ptr(), self.rt_rank[1].data_ptr()
             r.topk, r.score = self.rt_topk.data_ptr(), self.rt_topscore.data_ptr()
-            check(self.lib.tcar_retrieve_rerank_step(C.byref(self._ctx()), C.byref(bt), int(self._time_dirty), C.byref(d), C.byref(r),
-                                                     self._stream()), "tcar_retrieve_rerank_step")
-        self._time_dirty = False
-        self.poll_fork_errors()
+            self._head_step("retrieve_rerank_step", bt, C.byref(d), C.byref(r))
         if k is None:
             return self.rt_ids[:B], self.rt_scores[:B]
         return self.rt_topk[:B], self.rt_topscore[:B]

@@ -98,6 +98,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "shortlist of C items from coarse scores, re-scored exactly and cut to 20) and prints the share of labels in those "
                          "lists and their agreement with the streamed lists; 65 <= C <= " + str(MAX_SHORTLIST) + ".  Needs --eval_panel; "
                          "not with --dp_mode sharded, not with --cat_cap.  0: off")
+    ap.add_argument("--eval_mixed", default=0, type=int,
+                    help="1: evaluation packs consecutive batches of DIFFERENT session lengths into one ragged batch of at most "
+                         "--batch_size sessions (include/tcar_ragged.h) and streams the catalog once per pack instead of once per batch.  "
+                         "Needs --eval_panel; combines with --fresh_hours and --cat_cap; not with --dp_mode sharded, --gpus > 1, "
+                         "--eval_candidates, --eval_shortlist.  0: one call per batch")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -175,6 +180,25 @@ def check_eval_shortlist(eval_shortlist, eval_panel, dp_mode, cat_cap=0):
         raise ValueError("--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap")
 
 
+def check_eval_mixed(eval_mixed, eval_panel, dp_mode, gpus=1, eval_candidates=0, eval_shortlist=0):
+    """--eval_mixed packs the batches of the streamed evaluation of ONE engine into ragged batches (include/tcar_ragged.h): it needs
+    --eval_panel and one process; the candidate and two-stage passes keep their rectangular batches"""
+    if not eval_mixed:
+        return
+    if eval_mixed not in (0, 1):
+        raise ValueError("--eval_mixed must be 0 or 1")
+    if dp_mode == "sharded":
+        raise ValueError("--eval_mixed packs the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
+    if gpus and gpus > 1:
+        raise ValueError("--eval_mixed cannot be combined with --gpus > 1: the ranks split every batch by rows")
+    if not eval_panel:
+        raise ValueError("--eval_mixed needs --eval_panel P: only the streamed evaluation takes a ragged batch")
+    if eval_candidates:
+        raise ValueError("--eval_mixed cannot be combined with --eval_candidates")
+    if eval_shortlist:
+        raise ValueError("--eval_mixed cannot be combined with --eval_shortlist")
+
+
 def load_datas(args):
     """main.py:14-47: returns train_data, test_data, neighbor, args(dict), item_dict."""
     print("load the datasets.")
@@ -236,6 +260,7 @@ def main(argv=None):
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
     check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
+    check_eval_mixed(args.eval_mixed, args.eval_panel, args.dp_mode, args.gpus, args.eval_candidates, args.eval_shortlist)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -128,6 +128,61 @@ class SessionStore:
             "gap": gap.astype(np.int32),
         }
 
+    def ragged_arrays(self, idx: np.ndarray, gap_mode: str = "active_t") -> Dict[str, np.ndarray]:
+        """The RAGGED feed of the examples `idx`, of any input lengths (serving only): the per-click arrays of batch_arrays flat
+        over all sessions, [R] with R = sum of the lengths, session after session in the order of `idx`; the per-session ones [B];
+        "len" [B] the input lengths.  On examples of one length: batch_arrays, its [B, T] arrays flattened."""
+        idx = np.asarray(idx, dtype=np.int64)
+        ln = self.in_len[idx].astype(np.int64)
+        if idx.size == 0 or ln.min() < 1:
+            raise ValueError("a ragged feed holds at least one session, each of at least one input click")
+        base = self.off[idx]
+        start = np.cumsum(ln) - ln                                   # first flat row of every session
+        pos = np.repeat(base - start, ln) + np.arange(int(ln.sum()), dtype=np.int64)      # store index of every flat row
+        last = base + ln - 1                     # last INPUT click (sampler.py:86,105-109)
+        pub = self.pub[pos]                      # [R,5]
+        gap = (self.gap_active if gap_mode == "active_t" else self.gap_delta)[pos]
+        out = {"seq": self.items[pos].astype(np.int32), "label": (self.items[base + ln] - 1).astype(np.int32),
+               "gap": gap.astype(np.int32), "len": ln.astype(np.int32)}
+        out.update({n: pub[:, j].astype(np.int32) for j, n in enumerate(PER_ROW[1:6])})
+        out.update({n: self.clk[last, j].astype(np.int32) for j, n in enumerate(("cmo", "cd", "cw", "ch", "cmi"))})
+        return out
+
+
+PER_ROW = ("seq", "pm", "pd", "pw", "ph", "pmi", "gap")      # the per-click arrays of a feed: [B, T], or flat [R] in a ragged one
+
+
+def pack_sessions(feeds: Sequence[Dict[str, np.ndarray]]) -> Dict[str, np.ndarray]:
+    """A list of rectangular feeds (batch_arrays: [B_g, T_g] each, any mix of lengths) -> ONE ragged feed for the serving calls:
+    the per-click arrays flat [R], the per-session ones [B], "len" [B].  Sessions keep list order, feed after feed, so the sessions
+    of feed g are contiguous and their flat rows are its [B_g, T_g] block, row-major.  Negatives are dropped (serving has none);
+    a label must be in every feed or in none."""
+    feeds = list(feeds)
+    if not feeds:
+        raise ValueError("pack_sessions needs at least one feed")
+    if len({"label" in f for f in feeds}) != 1:
+        raise ValueError("pack_sessions: some feeds carry a label and some do not")
+    shapes = [np.asarray(f["seq"]).shape for f in feeds]
+    if any(len(s) != 2 for s in shapes):
+        raise ValueError("pack_sessions takes rectangular feeds, seq [B, T]")
+    out = {n: np.concatenate([np.asarray(f[n], dtype=np.int32).reshape(-1) for f in feeds]) for n in PER_ROW}
+    def per_b(f, n):             # an integer vector with one entry per session (cw, ch, label, the other click fields)
+        v = np.asarray(f[n]) if f.get(n) is not None else np.zeros((0, 0))
+        return v.ndim == 1 and np.issubdtype(v.dtype, np.integer) and v.shape[0] == np.asarray(f["seq"]).shape[0]
+    per_session = [n for n in feeds[0] if n not in PER_ROW and n not in ("neg", "len") and all(per_b(f, n) for f in feeds)]
+    out.update({n: np.concatenate([np.asarray(f[n], dtype=np.int32).reshape(-1) for f in feeds]) for n in per_session})
+    out["len"] = np.concatenate([np.full(b, t, dtype=np.int32) for b, t in shapes])
+    return out
+
+
+def ragged_offsets(length) -> tuple:
+    """len [B] -> (off [B + 1], pos [R]) of a ragged feed: the first flat row of every session and the position of every row in its
+    session (what the engine uploads beside the feed, include/tcar_ragged.h)"""
+    ln = np.asarray(length, dtype=np.int64)
+    off = np.zeros(ln.size + 1, dtype=np.int32)
+    np.cumsum(ln, out=off[1:])
+    return off, (np.arange(int(ln.sum())) - np.repeat(off[:-1].astype(np.int64), ln)).astype(np.int32)
+
 
 def build_neighbor(publish_time, window: int = 100) -> Dict[int, np.ndarray]:
     """`get_neighbor` (generate_neighbor.py:7-21): the negative source of `Sampler.neg_neighbor` (sampler.py:133-140).

@@ -25,6 +25,7 @@ import torch
 
 from ..engine import TIME_NAMES, TIME_VOCAB, TcarEngine, VAR_ORDER
 from . import cli, metrics as M
+from .data import pack_sessions
 from .sampler import Sampler
 
 
@@ -142,6 +143,7 @@ class Seq2SeqAttNN():
         self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
         self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
         self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
+        self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -204,6 +206,27 @@ class Seq2SeqAttNN():
         panel, cap, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'cat_cap', 'eval_shortlist'))
         cli.check_eval_shortlist(short, panel, args.get('dp_mode', 'replica'), cap)
         return short
+
+    def _eval_mixed(self, args) -> int:
+        """eval_mixed of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        panel, ncand, short, mixed = (int(args.get(n, getattr(self, n, 0)) or 0)
+                                      for n in ('eval_panel', 'eval_candidates', 'eval_shortlist', 'eval_mixed'))
+        cli.check_eval_mixed(mixed, panel, args.get('dp_mode', 'replica'), max(int(args.get('gpus', 1) or 1), getattr(self, 'dp_world', 1)), ncand, short)
+        return mixed
+
+    def _packs(self, feeds, mixed: bool):
+        """test(): the sampler's feeds grouped into the packs of one streamed call each — consecutive feeds, never splitting one,
+        while the pack holds at most batch_size sessions (eval_mixed); without the flag every feed is its own pack"""
+        pack, n = [], 0
+        for feed in feeds:
+            b = int(feed["seq"].shape[0])
+            if pack and (not mixed or n + b > self.batch_size):
+                yield pack
+                pack, n = [], 0
+            pack.append(feed)
+            n += b
+        if pack:
+            yield pack
 
     def _label_among_sampled(self, labels, ncand: int, rng):
         """candidate lists [B, ncand] of the "label among sampled negatives" protocol: the label in slot 0, then ncand - 1 items drawn
@@ -393,6 +416,15 @@ class Seq2SeqAttNN():
         return path
 
     # --------------------------------------------------------------------------------------------- test
+    @staticmethod
+    def _print_batch(feed, tk, args):
+        """the lines test() prints for its first two feeds (tk: the top-k list of the feed's first session)"""
+        print('batch_in:', feed["seq"][0].tolist())
+        print('active_interval:', feed["gap"][0].tolist())
+        print('input_click_week:', int(feed["cw"][0]))
+        print('batch_out:', int(feed["label"][0]), args['publish_time'][int(feed["label"][0])])
+        print('batch pred:', tk[:10])
+
     def test(self, sess, test_data, args):
         print('Measuring...')
         eng = self.engine
@@ -420,8 +452,34 @@ class Seq2SeqAttNN():
         # ILD / unexp pair counts and the set of recommended items stay on the device (tcar_eval_diversity)
         self._install_categories()
         eng.reset_coverage()
-        for feed in prefetch_batches(sampler):
+        mixed = self._eval_mixed(args)
+        eval_calls = 0
+        for pack in (self._packs(prefetch_batches(sampler), True) if mixed else ()):
+            # eval_mixed: ONE streamed call per pack of feeds (a ragged batch, include/tcar_ragged.h); a pack of one feed goes the
+            # rectangular way.  The sessions of a feed are contiguous in the pack and their flat rows are its [B_g, T_g] block, so
+            # the diversity counts are taken per feed on that block of the uploaded batch and on the feed's rows of topk.
+            bt = eng.upload(pack_sessions(pack) if len(pack) > 1 else pack[0])
+            window = None
+            if fresh:
+                wins = [self._fresh_window(feed, time_dict, fresh) for feed in pack]
+                outside += [o for w in wins for o in w[2].tolist()]
+                window = (np.concatenate([w[0] for w in wins]), np.concatenate([w[1] for w in wins]))
+            rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=window, max_per_category=cap or None)
+            eval_calls += 1
+            s0 = r0 = 0
+            for feed in pack:
+                batch += 1
+                b, T = feed["seq"].shape
+                tk = topk[s0:s0 + b]
+                ild_c, unexp_c, n_rec = eng.eval_diversity(bt, tk, block=(r0, b, T))
+                pending.append((feed, rank[s0:s0 + b].clone(), tk.clone() if args.get('is_print') or cap else None, ce[s0:s0 + b].clone(),
+                                ild_c, unexp_c, n_rec))
+                if batch < 3:
+                    self._print_batch(feed, tk[0].cpu().numpy().tolist(), args)
+                s0, r0 = s0 + b, r0 + b * T
+        for feed in (() if mixed else prefetch_batches(sampler)):
             batch += 1
+            eval_calls += 1          # one evaluation call per feed (data parallel: a collective step, the same count on every rank)
             T = feed["seq"].shape[1]
             feed, _cap = self._shard(feed)           # data parallel: every rank scores its shard of the batch
             if feed is None:
@@ -442,12 +500,7 @@ class Seq2SeqAttNN():
             ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)
             pending.append((feed, rank.clone(), topk.clone() if args.get('is_print') or cap else None, ce.clone(), ild_c, unexp_c, n_rec))     # device results; drained below
             if batch < 3:
-                tk = topk[0].cpu().numpy().tolist()
-                print('batch_in:', feed["seq"][0].tolist())
-                print('active_interval:', feed["gap"][0].tolist())
-                print('input_click_week:', int(feed["cw"][0]))
-                print('batch_out:', int(feed["label"][0]), args['publish_time'][int(feed["label"][0])])
-                print('batch pred:', tk[:10])
+                self._print_batch(feed, topk[0].cpu().numpy().tolist(), args)
             if ncand:            # the label among ncand - 1 sampled items: only those rows are scored (include/tcar_cand.h)
                 res = eng.score_candidates(None, *self._label_among_sampled(feed["label"], ncand, cand_rng), bt=bt)
                 cand_pending.append((res.counts.clone(), res.metrics.clone()))
@@ -488,7 +541,7 @@ class Seq2SeqAttNN():
         print('len of result dict: ', n_covered)
         print('MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(m_mrr, m_hit, m_ndcg))
         self.last_metrics = {"mrr": m_mrr, "recall": m_hit, "ndcg": m_ndcg, "loss": m_loss, "ild": m_ild,
-                             "unexp": m_unexp, "coverage": n_covered}
+                             "unexp": m_unexp, "coverage": n_covered, "eval_calls": eval_calls, "sessions": int(sums[6])}
         if ncand:
             per = [M.impression_metrics(c.cpu().numpy(), m.cpu().numpy()) for c, m in cand_pending]
             cols = [np.concatenate([p[i] for p in per]) if per else np.zeros(0) for i in range(4)]
@@ -529,6 +582,7 @@ class Seq2SeqAttNN():
         them returned (engine.TcarEngine.recommend_two_stage); None: the streamed selection over exact scores, as ever."""
         if shortlist is not None and max_per_category is not None:
             raise ValueError("the two-stage recommendation takes no per-category cap (shortlist and max_per_category exclude each other)")
+        sessions = self._feed(sessions)
         if window is not None:
             self._item_keys()
         if max_per_category is not None:
@@ -544,7 +598,7 @@ class Seq2SeqAttNN():
         Not with the catalog-sharded engine."""
         if window is not None:
             self._item_keys()
-        return self.engine.retrieve(sessions, C, window=window, **kw)
+        return self.engine.retrieve(self._feed(sessions), C, window=window, **kw)
 
     def score_candidates(self, sessions, candidates, clicked=None):
         """Score and rank the items every session of `sessions` names — a feed dict as `recommend` takes it; candidates int [B, C],
@@ -552,4 +606,13 @@ class Seq2SeqAttNN():
         metrics) on the device (engine.TcarEngine.score_candidates).  With clicked [B, C] (0 / 1) the counts and metrics of each
         list are those of an impression: host.metrics.impression_metrics turns them into AUC / MRR / nDCG@5 / nDCG@10.  Not with
         the catalog-sharded engine."""
-        return self.engine.score_candidates(sessions, candidates, clicked)
+        return self.engine.score_candidates(self._feed(sessions), candidates, clicked)
+
+    @staticmethod
+    def _feed(sessions):
+        """what recommend / retrieve / score_candidates take as `sessions`: a feed dict — rectangular, or a ragged one (flat rows +
+        "len", host.data.ragged_arrays / pack_sessions) — or a LIST of rectangular feeds of any lengths, which becomes one ragged
+        feed (sessions in list order, feed after feed): one call and one stream of the catalog for all of them"""
+        if isinstance(sessions, (list, tuple)):
+            return pack_sessions(sessions)
+        return sessions

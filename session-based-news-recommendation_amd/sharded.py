@@ -567,6 +567,7 @@ class ShardedEngine(TcarEngine):
         # defer_update (TcarEngine's split update): on ONE rank the update of this step is applied at the start of the next one
         # (tcar_shard_begin) or by flush(), as in the single-GPU step; with more ranks it is ignored — the sharded update is followed
         # by the all-gather of the updated rows, which the next step's gathers need: there is nothing to defer it behind
+        self._refuse_ragged(batch, bt, "train_step")
         if bt is None and batch is not None:
             bt = self.upload(batch)
         if bt is not None:
@@ -593,6 +594,7 @@ class ShardedEngine(TcarEngine):
         return self.s_ce[self.dp_rank * cap:self.dp_rank * cap + bt.B] + float(np.float32(self.neg_weight) * np.float32(np.log(2.0)))
 
     def loss_and_grads(self, batch, bt: Optional[Batch] = None, cap_rows: Optional[int] = None, cap: Optional[int] = None):
+        self._refuse_ragged(batch, bt, "loss_and_grads")
         bt = bt or self.upload(batch)
         if cap is None:
             cap = (cap_rows // max(bt.T, 1)) if cap_rows else bt.B
@@ -608,6 +610,7 @@ class ShardedEngine(TcarEngine):
 
     def eval_step(self, batch, k: int = 20, bt: Optional[Batch] = None, keep_logits: bool = False):
         """local sessions against the WHOLE catalog on the fp32 GEMM (evaluation runs once per epoch)"""
+        self._refuse_ragged(batch, bt, "eval_step")
         self.flush()
         bt = bt or self.upload(batch)
         g, lib, st, p = self.geo, self.lib, self._stream(), self._p
@@ -639,6 +642,9 @@ class ShardedEngine(TcarEngine):
         itself calls begin / prepare / label_scores / fold / finish in that order.  No buffer of the catalog's width is touched:
         every rank scores its shard's rows only."""
         g = self.geo
+        if self.is_ragged(batch) or getattr(bt, "_rg", None) is not None:      # (the sharded session forward is rectangular)
+            raise ValueError("the catalog-sharded engine takes rectangular feeds: ragged batches (sessions of mixed lengths) are for "
+                             "the single-engine serving calls")
         k, panel, quota = self._serve_request(k, panel, window, max_per_category, _ru(self.nl, 128))
         self.flush()
         excl = None

@@ -34,7 +34,15 @@ coarse scores) and recommend_two_stage (shortlist C, re-scored exactly, cut to K
 rounds: ms per step (upload included in all three), the agreement of the two-stage lists with the streamed ones (mean share of a
 streamed list found in the two-stage list, and the share of sessions whose lists are equal), and the two selectors alone — device
 events around one fold of the panel the last step left in the panel buffer into a fresh state, tcar_select_panel at K beside
-tcar_retrieve_panel at C."""
+tcar_retrieve_panel at C.
+
+       python tools/eval_bench.py [iters] [--n_items N] --ragged LMAX [--k K] [--panel P] [--rounds R]
+
+--ragged LMAX: B = 512 sessions whose lengths are drawn uniformly from 1 .. LMAX (fixed seed).  TcarEngine.recommend once per length
+bucket — what a caller of the rectangular entry points has to do, one stream of the catalog per bucket — beside ONE recommend on the
+ragged feed of the same sessions (include/tcar_ragged.h), alternating for `rounds` rounds; ms per request batch, uploads included in
+both.  Then the head alone, device events around tcar_ragged_forward on resident batches: one ragged head of all 512 sessions beside
+the heads of the buckets (each a ragged call of uniform lengths, which runs exactly the launches of the rectangular head)."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -57,6 +65,7 @@ ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded e
 ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
 ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve)")
+ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -191,6 +200,81 @@ if shorts:
                   "%d columns alone: select k=%d %.4f ms, retrieve C=%d %.4f ms" % (
                       N, rnd, c, dr * 1e3, dr / dt, d2 * 1e3, d2 / dt, min(eng.panel_buf.shape[1], N), K, fs, c, fr))
         sys.stdout.flush()
+    sys.exit(0)
+if a.ragged:
+    import ctypes as C_
+    from tcar_amd.host.data import PER_ROW, pack_sessions
+    if a.sharded:
+        sys.exit("--ragged needs the whole catalog on one engine: not with --sharded")
+    if not 1 <= a.ragged <= 40:
+        sys.exit("--ragged LMAX: 1 .. 40")
+    P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
+    K, LMAX = a.k, a.ragged
+    rng = np.random.RandomState(5)
+    lens = rng.randint(1, LMAX + 1, B).astype(np.int32)
+    R = int(lens.sum())
+    hi = dict(seq=(1, N + 1), pm=(1, 13), pd=(1, 32), pw=(1, 8), ph=(1, 25), pmi=(1, 61), gap=(0, 12))
+    ragged = {n: rng.randint(hi[n][0], hi[n][1], R).astype(np.int32) for n in PER_ROW}
+    ragged.update(cw=rng.randint(0, 7, B).astype(np.int32), ch=rng.randint(0, 24, B).astype(np.int32), len=lens)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    buckets, members = [], []
+    for L in np.unique(lens):                 # the same sessions, one rectangular feed per length
+        idx = np.where(lens == L)[0]
+        rows = off[idx][:, None] + np.arange(L)[None, :]
+        f = {n: ragged[n][rows] for n in PER_ROW}
+        f.update(cw=ragged["cw"][idx], ch=ragged["ch"][idx])
+        buckets.append(f)
+        members.append(idx)
+    print("N=%d B=%d LMAX=%d: %d rows, %d length buckets of %d .. %d sessions" % (
+        N, B, LMAX, R, len(buckets), min(len(m) for m in members), max(len(m) for m in members)))
+    # the same lists?  (a bucket's panel GEMM has other row counts than the ragged call's: the scores may differ in the last bits)
+    tr = eng.recommend(ragged, k=K, panel=P)[0].clone()
+    same = np.zeros(B, bool)
+    for f, idx in zip(buckets, members):
+        same[idx] = (eng.recommend(f, k=K, panel=P)[0] == tr[torch.as_tensor(idx, device=tr.device)]).all(1).cpu().numpy()
+    print("N=%d LMAX=%d: sessions whose bucketed and ragged lists are equal %.4f" % (N, LMAX, same.mean()))
+
+    def timed_calls(step):
+        for i in range(3):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    def bucketed():
+        for f in buckets:
+            eng.recommend(f, k=K, panel=P)
+
+    # the heads alone, on resident batches
+    bt_all = eng.make_resident(ragged)
+    bt_buckets = [eng.make_resident(pack_sessions([f])) for f in buckets]
+    eng._ensure_work(B, LMAX, R)
+
+    def heads_alone(bts):
+        lib, st, ctx = eng.lib, eng._stream(), eng._ctx()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for it in range(3 + iters):
+            if it == 3:
+                ev[0].record()
+            for bt in bts:
+                rc = lib.tcar_ragged_forward(C_.byref(ctx), C_.byref(bt), C_.byref(bt._rg), 0, st)
+                assert rc == 0, rc
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters
+
+    for rnd in range(a.rounds):              # the two forms alternate: the spread between rounds is visible
+        db = timed_calls(bucketed)
+        dr = timed_calls(lambda: eng.recommend(ragged, k=K, panel=P))
+        hb, hr = heads_alone(bt_buckets), heads_alone([bt_all])
+        print("N=%d LMAX=%d round %d: recommend per bucket (%d calls) %.3f ms, ragged recommend (1 call) %.3f ms = %.3f of the bucketed "
+              "form = %.2f bucket calls; heads alone: %d bucket heads %.4f ms, one ragged head %.4f ms" % (
+                  N, LMAX, rnd, len(buckets), db * 1e3, dr * 1e3, dr / db, dr / (db / len(buckets)), len(buckets), hb, hr))
+        sys.stdout.flush()
+    eng.check_forks()
     sys.exit(0)
 if not a.streamed:
     dt = timed(plain)
