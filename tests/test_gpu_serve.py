@@ -13,6 +13,7 @@ import torch
 import tcar_amd  # noqa: F401
 
 from select_util import _need_gpu, close
+from serve_shapes_ref import check_band  # noqa: F401  (rules (a)-(d); the tests of the other serving calls import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,20 +46,6 @@ def reference():
             a.setflags(write=False)
         _REF.update(params=params, content=content, mw=mw, batch=b, s=s, ce=ce, delta=1e-3 * np.abs(s).max(1))
     return _REF
-
-
-def check_band(s, delta, topk, k, gone=None, name=""):
-    """(a)-(d): k distinct in-range ids, sorted within 2 delta, everything clearly above the k-th score in, nothing clearly below"""
-    for b in range(s.shape[0]):
-        row, d2 = s[b].copy(), 2 * delta[b]
-        if gone is not None:
-            row[gone[b][gone[b] >= 0]] = -np.inf
-        t = topk[b].astype(np.int64)
-        assert len(set(t.tolist())) == k and t.min() >= 0 and t.max() < s.shape[1], (name, b, t)            # (a)
-        assert (row[t[:-1]] >= row[t[1:]] - d2).all(), (name, b)                                            # (b)
-        kth = np.sort(row)[-k]
-        assert set(np.where(row > kth + d2)[0].tolist()) <= set(t.tolist()), (name, b)                      # (c)
-        assert (row[t] >= kth - d2).all(), (name, b)                                                        # (d)
 
 
 @pytest.mark.parametrize("scoring", ["f32", "bf16x3-mixed"])
