@@ -49,7 +49,7 @@ def _name(prefix: str, name: str) -> str:
 for _prefix, _file in ABI_LAYERS:          # HEADER, SERVE_HEADER, WINDOW_HEADER, QUOTA_HEADER, SERVE_SHARD_HEADER, CAND_HEADER, ...
     globals()[_name(_prefix, "HEADER")] = os.path.join(PKG_DIR, "..", "include", _file)
 HEADERS = [os.path.join(CSRC, "tcar_common.h"), os.path.join(CSRC, "tcar_bf16_layout.h"), os.path.join(CSRC, "topk_rows.h"),
-           os.path.join(CSRC, "ce_rows.h")] + \
+           os.path.join(CSRC, "ce_rows.h"), os.path.join(CSRC, "panel_fold.h")] + \
     [globals()[_name(_prefix, "HEADER")] for _prefix, _ in ABI_LAYERS]
 _ID_MARK = b"TCAR_BUILD_ID="
 

@@ -10,6 +10,7 @@
 // admitted elements landed in the buffer (the LDS counter decides positions, the sort forgets them).
 #include "tcar_common.h"
 #include "topk_rows.h"
+#include "panel_fold.h"
 #include "../../include/tcar_retrieve.h"
 
 namespace {
@@ -23,8 +24,7 @@ constexpr int RT_MAX_CAP = 2 * RT_MAX_C;       // 2,048 keys: 16 KB
 
 typedef unsigned long long rt_key_t;
 
-// state row of one session, 2 C + 4 words: score[C] | id[C] (-1: empty) | held, threshold key (low word, high word), pad
-__host__ __device__ inline int rt_row_words(int C) { return 2 * C + 4; }
+// state row (fold_row_words of panel_fold.h): score[C] | id[C] (-1: empty) | held, threshold key (low, high word), pad; reset: zeros
 __host__ __device__ inline int rt_cap(int C) {
   int p = 1;
   while (p < C) p <<= 1;
@@ -50,17 +50,6 @@ __device__ __forceinline__ float rt_score(rt_key_t k) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-__global__ __launch_bounds__(256) void retrieve_reset_kernel(int B, int C, float* __restrict__ state) {
-  const int rw = rt_row_words(C);
-  const long n = (long)B * rw;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int w = (int)(i % rw);
-    if (w < C) state[i] = -INFINITY;
-    else if (w < 2 * C) reinterpret_cast<int*>(state)[i] = -1;
-    else reinterpret_cast<int*>(state)[i] = 0;
-  }
-}
-
 // One workgroup per session.  LDS: the key buffer (cap = max(2 Cp, 256) entries used, Cp = C rounded up to a power of two) and the
 // exclusion bitmap of the slice.  The buffer starts as the state's entries; the row slice streams by in sweeps of 8,192 columns
 // (16-byte loads, the next sweep's in flight while this one is tested); an element is admitted iff it is eligible and its key beats
@@ -83,26 +72,18 @@ __global__ __launch_bounds__(RT_NT) void retrieve_panel_kernel(int n0, int n, co
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   const int cap = rt_cap(C);
   const float* row = panel + (long)b * ld;
-  float* st = state + (long)b * rt_row_words(C);
+  float* st = state + (long)b * fold_row_words(C);
   int* sti = reinterpret_cast<int*>(st);
   int held = sti[2 * C];            // uniform: entries of the buffer that are settled (after a prune: all of them)
   rt_key_t thr = ((rt_key_t)(unsigned)sti[2 * C + 2] << 32) | (unsigned)sti[2 * C + 1];
   for (int i = tid; i < held; i += RT_NT) buf[i] = rt_key(st[i], sti[C + i]);
   if (tid == 0) cnt = held;
-  if (excl) {
-    for (int i = tid; i < (n + 31) / 32; i += RT_NT) exb[i] = 0u;
-  }
-  __syncthreads();
-  if (excl) {
-    for (int i = tid; i < X; i += RT_NT) {
-      const int e = excl[(long)b * X + i] - n0;
-      if (e >= 0 && e < n) atomicOr(&exb[e >> 5], 1u << (e & 31));
-    }
-  }
+  const ExclBitmap ex{exb};
+  ex.build(excl, X, b, n0, n, tid, RT_NT);
   int wl = 0, wh = 0;
   if constexpr (W) { wl = wlo[b]; wh = whi[b]; }
   const int32_t* kp = W ? key + n0 : nullptr;
-  const bool kal = W && (reinterpret_cast<uintptr_t>(kp) & 15) == 0;
+  const bool kal = W && slice_aligned(kp);
   __syncthreads();
 
   // the buffer's first `m` entries -> the best min(m, C) of them in list order; returns how many.  Uniform control flow.
@@ -155,15 +136,8 @@ __global__ __launch_bounds__(RT_NT) void retrieve_panel_kernel(int n0, int n, co
       unsigned ok = (unsigned)(v[u].x == v[u].x) | (unsigned)(v[u].y == v[u].y) << 1 | (unsigned)(v[u].z == v[u].z) << 2 |
                     (unsigned)(v[u].w == v[u].w) << 3;                               // not NaN
       ok &= (c + 3 < n) ? 15u : (1u << (n - c)) - 1u;
-      if (excl) ok &= ~(exb[c >> 5] >> (c & 31));                                    // (c % 4 == 0: the four bits sit in one word)
-      if constexpr (W) {
-        const int last = n - 1;
-        int4 q;
-        if (kal && c + 3 < n) q = *reinterpret_cast<const int4*>(kp + c);
-        else q = make_int4(kp[min(c, last)], kp[min(c + 1, last)], kp[min(c + 2, last)], kp[min(c + 3, last)]);
-        ok &= (unsigned)((wl <= q.x) & (q.x < wh)) | (unsigned)((wl <= q.y) & (q.y < wh)) << 1 |
-              (unsigned)((wl <= q.z) & (q.z < wh)) << 2 | (unsigned)((wl <= q.w) & (q.w < wh)) << 3;
-      }
+      if (excl) ok &= ~ex.excl_bits4(c);
+      if constexpr (W) ok &= window_bits4(wl, wh, slice4(kp, c, n, kal));
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if ((ok >> j & 1u) && key_of(4 * u + j) > thr) pend |= 1u << (4 * u + j);
@@ -221,7 +195,7 @@ __global__ __launch_bounds__(RT_NT) void retrieve_panel_kernel(int n0, int n, co
 __global__ __launch_bounds__(256) void retrieve_finish_kernel(int C, const float* __restrict__ state, int32_t* __restrict__ ids,
                                                               float* __restrict__ scores) {
   const int b = blockIdx.x;
-  const float* st = state + (long)b * rt_row_words(C);
+  const float* st = state + (long)b * fold_row_words(C);
   const int* sti = reinterpret_cast<const int*>(st);
   for (int i = threadIdx.x; i < C; i += 256) {
     const int id = sti[C + i];
@@ -242,7 +216,7 @@ __global__ __launch_bounds__(64) void rerank_take_kernel(int C, int k, const int
   if (score && in) score[(long)b * k + j] = cand_score[(long)b * C + s];
 }
 
-inline bool bad_bc(int B, int C) { return B < 0 || C < 1 || C > RT_MAX_C; }
+inline bool bad_bc(int B, int C) { return bad_fold_bm(B, C, RT_MAX_C); }
 
 }  // namespace
 
@@ -250,33 +224,20 @@ extern "C" int tcar_retrieve_abi_version(void) { return TCAR_RETRIEVE_ABI_VERSIO
 
 extern "C" int64_t tcar_retrieve_state_bytes(int B, int C) {
   if (bad_bc(B, C)) return -1;
-  return (int64_t)B * rt_row_words(C) * 4;
+  return (int64_t)B * fold_row_words(C) * 4;
 }
 
 extern "C" int tcar_retrieve_reset(int B, int C, void* state, void* stream) {
-  if (bad_bc(B, C)) return TCAR_E_ARG;
-  if (B == 0) return TCAR_OK;
-  if (!state || ((uintptr_t)state & 3)) return TCAR_E_ARG;
-  long blocks = ((long)B * rt_row_words(C) + 255) / 256;
-  if (blocks > 1024) blocks = 1024;
-  TCAR_LAUNCH(retrieve_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, C, (float*)state);
-  TCAR_CHECK_LAUNCH();
-  return TCAR_OK;
+  return tcar_fold_reset(B, C, RT_MAX_C, FoldTail{}, state, stream);
 }
 
 extern "C" int tcar_retrieve_panel(int B, int n0, int n, const float* panel, int64_t ld, int C, const int32_t* excl, int X,
                                    const int32_t* key, const int32_t* lo, const int32_t* hi, void* state, void* stream) {
-  if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
-  if (bad_bc(B, C) || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
-  if ((ld & 3) || ld < n || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
-  if (B == 0 || n == 0) return TCAR_OK;
-  if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
-  if (key)
-    TCAR_LAUNCH((retrieve_panel_kernel<true>), dim3(B), dim3(RT_NT), 0, (hipStream_t)stream, n0, n, panel, (long)ld, C, excl, X,
-                (float*)state, key, lo, hi);
-  else
-    TCAR_LAUNCH((retrieve_panel_kernel<false>), dim3(B), dim3(RT_NT), 0, (hipStream_t)stream, n0, n, panel, (long)ld, C, excl, X,
-                (float*)state, key, lo, hi);
+  bool empty;
+  if (const int rc = check_fold_args(B, C, RT_MAX_C, n0, n, panel, ld, excl, X, key, lo, hi, state, &empty); rc != TCAR_OK || empty)
+    return rc;
+  TCAR_LAUNCH((key ? retrieve_panel_kernel<true> : retrieve_panel_kernel<false>), dim3(B), dim3(RT_NT), 0, (hipStream_t)stream, n0, n,
+              panel, (long)ld, C, excl, X, (float*)state, key, lo, hi);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
 }

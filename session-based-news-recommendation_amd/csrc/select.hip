@@ -8,22 +8,21 @@
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
 #include "topk_rows.h"
+#include "panel_fold.h"
 #include "../../include/tcar_serve_shard.h"
 
 namespace {
 
-// state row of one session, 2k + 4 words: score[k] | index[k] (-1: empty) | count, max, sum, pad
-__host__ __device__ inline int sel_row_words(int k) { return 2 * k + 4; }
+// state row of one session (fold_row_words of panel_fold.h): score[k] | index[k] (-1: empty) | count, max, sum, pad
+constexpr FoldTail SEL_TAIL = {{0u, 0xff800000u, 0u, 0u}};       // count 0, max -inf, sum 0
 
-__global__ __launch_bounds__(256) void select_reset_kernel(int B, int k, float* __restrict__ state) {
-  const int rw = sel_row_words(k);
+// the reset of every streamed fold: m empty entries (-inf, -1), then the selector's tail
+__global__ __launch_bounds__(256) void fold_reset_kernel(int B, int m, FoldTail tail, uint32_t* __restrict__ state) {
+  const int rw = fold_row_words(m);
   const long n = (long)B * rw;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int w = (int)(i % rw);
-    if (w < k) state[i] = -INFINITY;
-    else if (w < 2 * k) reinterpret_cast<int*>(state)[i] = -1;
-    else if (w == 2 * k) reinterpret_cast<int*>(state)[i] = 0;
-    else state[i] = (w == 2 * k + 1) ? -INFINITY : 0.f;
+    state[i] = w < m ? 0xff800000u : w < 2 * m ? 0xffffffffu : tail.w[w - 2 * m];
   }
 }
 
@@ -55,43 +54,39 @@ __global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, co
   __shared__ unsigned exb[SEL_MAX_N / 32];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* row = panel + (long)b * ld;
-  float* st = state + (long)b * sel_row_words(k);
+  float* st = state + (long)b * fold_row_words(k);
   int* sti = reinterpret_cast<int*>(st);
   const float ninf = -INFINITY, dead = __builtin_nanf("");
   unsigned pool[W ? (4 * R + 31) / 32 : 1] = {};      // W: bit 4 r + j = column (tid + r NT) 4 + j is in the pool
   if constexpr (W) {
-    // The key slice key[n0 .. n0 + n), read once: 16-byte loads where key + n0 is aligned, with scalar loads for a last group of
-    // fewer than four columns; scalar loads (index clamped into the slice, no branch) where it is not.  No load leaves the slice.
+    // The key slice key[n0 .. n0 + n), read once; no load leaves the slice
     const int32_t* kp = key + n0;
     const int lo = wlo[b], hi = whi[b];
     const int labc = lab_score ? label[b] - n0 : -1;          // a labelled call: the label's column is always in the pool
-    auto bits4 = [&](int c, int kx, int ky, int kz, int kw) __attribute__((always_inline)) -> unsigned {
-      return (unsigned)((((lo <= kx) & (kx < hi)) | (c + 0 == labc)) & (c + 0 < n)) |
-             (unsigned)((((lo <= ky) & (ky < hi)) | (c + 1 == labc)) & (c + 1 < n)) << 1 |
-             (unsigned)((((lo <= kz) & (kz < hi)) | (c + 2 == labc)) & (c + 2 < n)) << 2 |
-             (unsigned)((((lo <= kw) & (kw < hi)) | (c + 3 == labc)) & (c + 3 < n)) << 3;
+    auto bits4 = [&](int c, int4 q) __attribute__((always_inline)) -> unsigned {
+      const unsigned lab = (unsigned)(c + 0 == labc) | (unsigned)(c + 1 == labc) << 1 | (unsigned)(c + 2 == labc) << 2 |
+                           (unsigned)(c + 3 == labc) << 3;
+      const unsigned cols = (unsigned)(c + 0 < n) | (unsigned)(c + 1 < n) << 1 | (unsigned)(c + 2 < n) << 2 | (unsigned)(c + 3 < n) << 3;
+      return (window_bits4(lo, hi, q) | lab) & cols;
     };
-    auto scalar4 = [&](int c) __attribute__((always_inline)) -> unsigned {
-      const int last = n - 1;
-      return bits4(c, kp[min(c + 0, last)], kp[min(c + 1, last)], kp[min(c + 2, last)], kp[min(c + 3, last)]);
+    auto clamped = [&](bool tail) __attribute__((always_inline)) {       // every group, or the one partial group at the end alone
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int c = (tid + r * NT) * 4;
+        if (!tail || (c < n && c + 3 >= n)) pool[(4 * r) >> 5] |= bits4(c, slice4(kp, c, n, false)) << ((4 * r) & 31);
+      }
     };
-    if ((reinterpret_cast<uintptr_t>(kp) & 15) == 0) {
+    // Aligned: straight 16-byte loads of the whole groups, then the partial one.  (slice4 alone with `aligned` set compiles to four
+    // 4-byte loads per group: the compiler folds its two arms into the clamped form.  All 4 R reads are in flight here.)
+    if (!slice_aligned(kp)) clamped(false);
+    else {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const int c = (tid + r * NT) * 4;
         const int4 q = (c + 3 < n) ? *reinterpret_cast<const int4*>(kp + c) : make_int4(0, 0, 0, 0);
-        pool[(4 * r) >> 5] |= (c + 3 < n ? bits4(c, q.x, q.y, q.z, q.w) : 0u) << ((4 * r) & 31);
+        pool[(4 * r) >> 5] |= (c + 3 < n ? bits4(c, q) : 0u) << ((4 * r) & 31);
       }
-      if (n & 3) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-          const int c = (tid + r * NT) * 4;
-          if (c < n && c + 3 >= n) pool[(4 * r) >> 5] |= scalar4(c) << ((4 * r) & 31);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < R; ++r) pool[(4 * r) >> 5] |= scalar4((tid + r * NT) * 4) << ((4 * r) & 31);
+      if (n & 3) clamped(true);
     }
     __builtin_amdgcn_sched_barrier(0);               // the keys are bits before the slice takes its 4 R registers
   }
@@ -117,18 +112,9 @@ __global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, co
   const bool full = sti[2 * k - 1] >= 0;          // k entries so far: the last one bounds what can still enter
   const float lastv = st[k - 1];
   const int lasti = sti[2 * k - 1];
-  // exclusion bitmap of this slice (integer LDS atomics; idempotent)
-  if (tid == 0) any_excl = 0;
-  if (excl) {
-    for (int i = tid; i < (n + 31) / 32; i += NT) exb[i] = 0u;
-  }
-  __syncthreads();
-  if (excl) {
-    for (int i = tid; i < X; i += NT) {
-      const int e = excl[(long)b * X + i] - n0;
-      if (e >= 0 && e < n) { atomicOr(&exb[e >> 5], 1u << (e & 31)); any_excl = 1; }
-    }
-  }
+  // exclusion bitmap of this slice; any_excl: it has a bit set at all (read behind the statistics' barrier)
+  const ExclBitmap ex{exb};
+  ex.build<true>(excl, X, b, n0, n, tid, NT, &any_excl);
   // ---- statistics of the slice: strict-greater count (the label's own column left out by index), max, sum exp
   const bool counting = lab_score != nullptr;
   const float xl = counting ? lab_score[b] : 0.f;
@@ -205,7 +191,7 @@ __global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, co
   for (int r = 0; r < R; ++r) {
     const int c = (tid + r * NT) * 4;
     unsigned bits = 0u;
-    if (has_excl && c < n) bits = exb[c >> 5] >> (c & 31);
+    if (has_excl && c < n) bits = ex.excl_bits4(c);
     if constexpr (W) bits |= ~(pool[(4 * r) >> 5] >> ((4 * r) & 31));
     if (c + 0 >= n || (bits & 1u)) v[r].x = dead;
     if (c + 1 >= n || (bits & 2u)) v[r].y = dead;
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, co
     //            below the last key walked, from the registers, one entry per round as in the core's fallback
     //            (kills there cost a pass over the category slice, so they are put off: see below)
     const int32_t* cp = cat + n0;
-    const bool cal = (reinterpret_cast<uintptr_t>(cp) & 15) == 0;
+    const bool cal = slice_aligned(cp);
     int taken = 0, mycat = 0;
     auto accept = [&](float fv, int fi, int fc) __attribute__((always_inline)) -> bool {      // true: fc has reached the cap
       if (tid == 0) { st[taken] = fv; sti[k + taken] = fi; }
@@ -260,9 +246,7 @@ __global__ __launch_bounds__(TOPK_NT) void select_panel_kernel(int n0, int n, co
         for (int r = 0; r < R; ++r) {
           const int c = t4 + r * NT * 4;
           if (c < n) {
-            int4 q;
-            if (cal && c + 3 < n) q = *reinterpret_cast<const int4*>(cp + c);
-            else { const int last = n - 1; q = make_int4(cp[min(c, last)], cp[min(c + 1, last)], cp[min(c + 2, last)], cp[min(c + 3, last)]); }
+            const int4 q = slice4(cp, c, n, cal);
             if (q.x == kc) { v[r].x = dead; hit |= n0 + c + 0 == core.cbi; }
             if (q.y == kc) { v[r].y = dead; hit |= n0 + c + 1 == core.cbi; }
             if (q.z == kc) { v[r].z = dead; hit |= n0 + c + 2 == core.cbi; }
@@ -311,7 +295,7 @@ __global__ __launch_bounds__(64) void select_finish_kernel(int k, const float* _
                                                            int32_t* __restrict__ topk, float* __restrict__ score,
                                                            int32_t* __restrict__ rank, float* __restrict__ ce) {
   const int b = blockIdx.x, t = threadIdx.x;
-  const float* st = state + (long)b * sel_row_words(k);
+  const float* st = state + (long)b * fold_row_words(k);
   const int* sti = reinterpret_cast<const int*>(st);
   if (t < k) {
     const int i = sti[k + t];
@@ -336,7 +320,7 @@ __global__ __launch_bounds__(64) void select_finish_kernel(int k, const float* _
 template <bool Q>
 __global__ __launch_bounds__(64) void select_merge_kernel(int k, int S, const float* __restrict__ states, long stride,
                                                           float* __restrict__ out, const int32_t* __restrict__ cat, int cap) {
-  const int b = blockIdx.x, lane = threadIdx.x, rw = sel_row_words(k);
+  const int b = blockIdx.x, lane = threadIdx.x, rw = fold_row_words(k);
   const float ninf = -INFINITY;
   const bool live = lane < S;
   const float* st = states + (live ? (long)lane * stride : 0L) + (long)b * rw;       // (lanes >= S point at shard 0 and read nothing)
@@ -437,7 +421,7 @@ __global__ __launch_bounds__(64) void label_score_bf16_kernel(int N, int K, cons
 // a cap goes with a category table (then >= 1), and with nothing else
 inline bool bad_quota(const int32_t* cat, int cap) { return cat ? cap < 1 : cap != 0; }
 // the (B, k) every entry point of the streamed selection takes
-inline bool bad_bk(int B, int k) { return B < 0 || k < 1 || k > SEL_MAX_K; }
+inline bool bad_bk(int B, int k) { return bad_fold_bm(B, k, SEL_MAX_K); }
 
 }  // namespace
 
@@ -445,19 +429,21 @@ extern "C" int tcar_serve_abi_version(void) { return TCAR_SERVE_ABI_VERSION; }
 
 extern "C" int64_t tcar_select_state_bytes(int B, int k) {
   if (bad_bk(B, k)) return -1;
-  return (int64_t)B * sel_row_words(k) * 4;
+  return (int64_t)B * fold_row_words(k) * 4;
 }
 
-extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) {
-  if (bad_bk(B, k)) return TCAR_E_ARG;
+int tcar_fold_reset(int B, int m, int m_max, FoldTail tail, void* state, void* stream) {
+  if (bad_fold_bm(B, m, m_max)) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;
   if (!state || ((uintptr_t)state & 3)) return TCAR_E_ARG;
-  long blocks = ((long)B * sel_row_words(k) + 255) / 256;
+  long blocks = ((long)B * fold_row_words(m) + 255) / 256;
   if (blocks > 1024) blocks = 1024;
-  TCAR_LAUNCH(select_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, k, (float*)state);
+  TCAR_LAUNCH(fold_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, B, m, tail, (uint32_t*)state);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
 }
+
+extern "C" int tcar_select_reset(int B, int k, void* state, void* stream) { return tcar_fold_reset(B, k, SEL_MAX_K, SEL_TAIL, state, stream); }
 
 extern "C" int tcar_window_abi_version(void) { return TCAR_WINDOW_ABI_VERSION; }
 extern "C" int tcar_quota_abi_version(void) { return TCAR_QUOTA_ABI_VERSION; }
@@ -467,11 +453,10 @@ extern "C" int tcar_select_panel_quota(int B, int n0, int n, const float* panel,
                                        const float* lab_score, const int32_t* excl, int X, void* state, void* stream,
                                        const int32_t* key, const int32_t* lo, const int32_t* hi, const int32_t* cat, int cap) {
   if (bad_quota(cat, cap)) return TCAR_E_ARG;
-  if (key ? (!lo || !hi) : (lo || hi)) return TCAR_E_ARG;
-  if (bad_bk(B, k) || n0 < 0 || n < 0 || n > SEL_MAX_N || (long)n0 + n > 0x7fffffffL) return TCAR_E_ARG;
-  if ((ld & 3) || ld < n || (lab_score && !label) || X < 0 || (excl && X <= 0)) return TCAR_E_ARG;
-  if (B == 0 || n == 0) return TCAR_OK;
-  if (!panel || !state || !tcar_aligned16(panel) || ((uintptr_t)state & 3)) return TCAR_E_ARG;
+  if (lab_score && !label) return TCAR_E_ARG;
+  bool empty;
+  if (const int rc = check_fold_args(B, k, SEL_MAX_K, n0, n, panel, ld, excl, X, key, lo, hi, state, &empty); rc != TCAR_OK || empty)
+    return rc;
   // the kernel: [rung of the R ladder that holds n columns][windowed][capped]
   static constexpr decltype(&select_panel_kernel<2>) fold[3][2][2] = {
       {{select_panel_kernel<TOPK_R_SMALL, false, false>, select_panel_kernel<TOPK_R_SMALL, false, true>},
@@ -515,7 +500,7 @@ extern "C" int tcar_select_merge(int B, int k, int S, const void* states, int64_
                                  void* stream) {
   if (bad_quota(cat, cap)) return TCAR_E_ARG;
   if (bad_bk(B, k) || S < 1 || S > 64) return TCAR_E_ARG;
-  const int64_t rows = (int64_t)B * sel_row_words(k);
+  const int64_t rows = (int64_t)B * fold_row_words(k);
   if (S > 1 && stride_words < rows) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;
   if (!states || !out || ((uintptr_t)states & 3) || ((uintptr_t)out & 3)) return TCAR_E_ARG;

@@ -1266,48 +1266,74 @@ extern "C" int tcar_eval_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
 }
 
 namespace {
-// The fold of one evaluation / recommendation step: reset the state, then the catalog rows the context's candidate side covers in
-// column panels — the evaluation form of the logits GEMM into s->panel_buf, folded by tcar_select_panel_quota while the panel is
-// cache-warm.  A panel start that is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row
-// blocks).  a16h / a16l: the planes of the B session rows (split-bf16 modes).  id0: the catalog id of the context's first candidate
-// row — 0, or the first row of a shard (tcar_shard_serve_fold), whose folds then carry GLOBAL item ids.
-int serve_fold(const tcar_ctx_t* c, int B, const void* a16h, const void* a16l, int id0, const int32_t* label, const float* lab,
-               const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+// the head of a forward pass, and what every forward pass does behind it
+int forward_disarm(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, void* stream) {
+  Head h;
+  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
+  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
+  return TCAR_OK;
+}
+
+// What every serving step starts with: the context checks, "does it hold the operands this step's scoring contracts", the head.
+// need: the nsplit of that scoring on a split-bf16 engine — c->scoring (the mode's planes) or 1 (the hi planes alone).
+int serve_head(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, void* stream, int need) {
+  RET(check_ctx(c, bt));
+  if (c->scoring ? (!c->a16h || !c->e16h || (need == 3 && (!c->a16l || !c->e16l))) : !c->attout) return TCAR_E_ARG;
+  return forward_disarm(c, bt, rg, refresh_time, stream);
+}
+
+// The panel loop of every streamed fold: the catalog rows the context's candidate side covers in column panels — the evaluation
+// form of the logits GEMM into panel_buf, then fold(n0, n), the caller's launch, while the panel is cache-warm.  A panel start that
+// is a multiple of 128 is a plain pointer offset into E (fp32) or its KB32 planes (whole 128-row blocks).  a16h / a16l: the planes
+// of the B session rows; nsplit: c->scoring, or 1 with a16l = NULL — the hi planes alone.  (fp32 engine: its fp32 GEMM either way.)
+template <class Fold>
+int for_panels(const tcar_ctx_t* c, int B, const void* a16h, const void* a16l, int nsplit, int panel, float* panel_buf, void* stream,
+               Fold fold) {
   const Geo g(c->d);
-  const int k = s->k;
-  RET(tcar_select_reset(B, k, s->state, stream));
-  for (int n0 = 0; n0 < g.N; n0 += s->panel) {
-    const int n = g.N - n0 < s->panel ? g.N - n0 : s->panel;
+  for (int n0 = 0; n0 < g.N; n0 += panel) {
+    const int n = g.N - n0 < panel ? g.N - n0 : panel;
     if (c->scoring) {
       TcarOpt ol = opt_of(c);
       const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
       RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, a16h, a16l, g.ek, B, (const char*)c->e16h + off,
-                                c->e16l ? (const char*)c->e16l + off : nullptr, g.ek, g.Npad - n0, s->panel_buf, s->panel, nullptr, 0, 0,
-                                nullptr, 0, c->scoring, 1, stream, &ol));
+                                a16l && c->e16l ? (const char*)c->e16l + off : nullptr, g.ek, g.Npad - n0, panel_buf, panel, nullptr, 0, 0,
+                                nullptr, 0, nsplit, 1, stream, &ol));
     } else {
-      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, s->panel_buf, s->panel, nullptr, 0, 0, 1, stream));
+      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, panel_buf, panel, nullptr, 0, 0, 1, stream));
     }
-    RET(tcar_select_panel_quota(B, id0 + n0, n, s->panel_buf, s->panel, k, label, lab, s->excl, s->X, s->state, stream,
-                                w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, q ? q->cat : nullptr, q ? q->cap : 0));
+    RET(fold(n0, n));
   }
   return TCAR_OK;
+}
+
+// The fold of one evaluation / recommendation step: reset, then every panel folded by tcar_select_panel_quota.  id0: the catalog id
+// of the context's first candidate row — 0, or the first row of a shard (tcar_shard_serve_fold), whose folds carry GLOBAL item ids.
+int serve_fold(const tcar_ctx_t* c, int B, const void* a16h, const void* a16l, int id0, const int32_t* label, const float* lab,
+               const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
+  RET(tcar_select_reset(B, s->k, s->state, stream));
+  return for_panels(c, B, a16h, a16l, c->scoring, s->panel, s->panel_buf, stream, [&](int n0, int n) {
+    return tcar_select_panel_quota(B, id0 + n0, n, s->panel_buf, s->panel, s->k, label, lab, s->excl, s->X, s->state, stream,
+                                   w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, q ? q->cat : nullptr, q ? q->cap : 0);
+  });
+}
+
+// what the descriptors of every panel-streaming call share: the panel and its buffer, the exclusion lists, the window's pointers
+int check_panel_desc(int panel, const float* panel_buf, const int32_t* excl, int X, const tcar_window_t* w) {
+  if ((w && (!w->key || !w->lo || !w->hi)) || panel <= 0 || (panel & 127) || panel > SEL_MAX_N) return TCAR_E_ARG;
+  return !panel_buf || !tcar_aligned16(panel_buf) || X < 0 || (excl && X <= 0) ? TCAR_E_ARG : TCAR_OK;
 }
 
 // the descriptors of a streamed call; need_topk: the call finishes the state itself (a whole step, not a shard's fold)
 int check_serve_desc(const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, bool need_topk) {
   if (!s) return TCAR_E_ARG;
-  if (w && (!w->key || !w->lo || !w->hi)) return TCAR_E_ARG;
+  RET(check_panel_desc(s->panel, s->panel_buf, s->excl, s->X, w));
   if (q && (!q->cat || q->cap < 1)) return TCAR_E_ARG;
-  if (s->k < 1 || s->k > SEL_MAX_K || s->panel <= 0 || (s->panel & 127) || s->panel > SEL_MAX_N) return TCAR_E_ARG;
-  if (!s->panel_buf || !s->state || (need_topk && !s->topk) || !tcar_aligned16(s->panel_buf) || s->X < 0 || (s->excl && s->X <= 0))
-    return TCAR_E_ARG;
+  if (s->k < 1 || s->k > SEL_MAX_K || !s->state || (need_topk && !s->topk)) return TCAR_E_ARG;
   return TCAR_OK;
 }
-}  // namespace
 
 // Evaluation / recommendation without the [B, N] logits (include/tcar_serve.h): the head of a forward pass, the label scores, then
 // serve_fold over the whole catalog and the finishing launch.  w / q NULL: the unwindowed / uncapped step.
-namespace {
 int serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_serve_t* s,
                const tcar_window_t* w, const tcar_quota_t* q, void* stream) {
   if (!c || !bt || bt->B < 0) return TCAR_E_ARG;
@@ -1315,13 +1341,9 @@ int serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t*
   if (s->state_bytes < tcar_select_state_bytes(bt->B, s->k)) return TCAR_E_ARG;
   if (bt->label && !s->lab_score) return TCAR_E_ARG;
   if (bt->B == 0) return TCAR_OK;
-  RET(check_ctx(c, bt));
-  if (c->scoring ? (!c->a16h || !c->e16h || (c->scoring == 3 && (!c->a16l || !c->e16l))) : !c->attout) return TCAR_E_ARG;
+  RET(serve_head(c, bt, rg, refresh_time, stream, c->scoring));
   const Geo g(c->d);
   const int B = bt->B, k = s->k;
-  Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
-  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   const float* lab = bt->label ? s->lab_score : nullptr;
   if (lab)
     RET(tcar_label_scores(B, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l,
@@ -1353,13 +1375,9 @@ int cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* 
   if (d->C < 1 || d->C > CAND_MAX_C || d->ld_cand < d->C || !d->cand || !d->score) return TCAR_E_ARG;
   if (!d->clicked && (d->counts || d->metrics)) return TCAR_E_ARG;
   if (bt->B == 0) return TCAR_OK;
-  RET(check_ctx(c, bt));
-  if (c->scoring ? (!c->a16h || !c->e16h || (c->scoring == 3 && (!c->a16l || !c->e16l))) : !c->attout) return TCAR_E_ARG;
+  RET(serve_head(c, bt, rg, refresh_time, stream, c->scoring));
   const Geo g(c->d);
   const int B = bt->B, C = d->C;
-  Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
-  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
                        c->scoring, d->cand, d->ld_cand, d->score, C, stream));
   if (!d->rank_of && !d->order && !d->counts && !d->metrics) return TCAR_OK;
@@ -1375,41 +1393,24 @@ extern "C" int tcar_cand_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int r
 namespace {
 int check_retrieve_desc(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_retrieve_t* d) {
   if (!c || !bt || bt->B < 0 || !d) return TCAR_E_ARG;
-  if (d->C < 1 || d->C > CAND_MAX_C || d->panel <= 0 || (d->panel & 127) || d->panel > SEL_MAX_N) return TCAR_E_ARG;
-  if (d->window && (!d->window->key || !d->window->lo || !d->window->hi)) return TCAR_E_ARG;
-  if (!d->panel_buf || !d->state || !d->ids || !tcar_aligned16(d->panel_buf) || d->X < 0 || (d->excl && d->X <= 0)) return TCAR_E_ARG;
+  RET(check_panel_desc(d->panel, d->panel_buf, d->excl, d->X, d->window));
+  if (d->C < 1 || d->C > CAND_MAX_C || !d->state || !d->ids) return TCAR_E_ARG;
   if (d->state_bytes < tcar_retrieve_state_bytes(bt->B, d->C)) return TCAR_E_ARG;
   return TCAR_OK;
 }
 
-// The body of a retrieval step behind its argument checks: the head of a forward pass as tcar_serve_step_quota runs it, a fold
-// shaped like serve_fold — per panel the evaluation form of the logits GEMM in the COARSE precision (the hi planes alone on a
-// split-bf16 engine, whatever its nsplit; the fp32 GEMM on the fp32 engine, which has no cheaper operands) into d->panel_buf, folded
-// by tcar_retrieve_panel while the panel is cache-warm — and the finishing launch.
+// The body of a retrieval step behind its argument checks: the head, for_panels in the COARSE precision (the hi planes alone on a
+// split-bf16 engine, whatever its nsplit; the fp32 engine has no cheaper operands) folded by tcar_retrieve_panel, and the finish.
 int retrieve_impl(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_retrieve_t* d,
                   void* stream) {
-  RET(check_ctx(c, bt));
-  if (c->scoring ? (!c->a16h || !c->e16h) : !c->attout) return TCAR_E_ARG;
-  const Geo g(c->d);
+  RET(serve_head(c, bt, rg, refresh_time, stream, 1));
   const int B = bt->B, C = d->C;
   const tcar_window_t* w = d->window;
-  Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
-  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
   RET(tcar_retrieve_reset(B, C, d->state, stream));
-  for (int n0 = 0; n0 < g.N; n0 += d->panel) {
-    const int n = g.N - n0 < d->panel ? g.N - n0 : d->panel;
-    if (c->scoring) {
-      TcarOpt ol = opt_of(c);
-      const int64_t off = (int64_t)(n0 >> 7) * (g.ek >> 5) * 4096 * 2;        // bytes: bf16 planes, block row n0 / 128
-      RET(tcar_gemm_bf16_perm_o(1, B, n, g.ek, c->a16h, nullptr, g.ek, B, (const char*)c->e16h + off, nullptr, g.ek, g.Npad - n0,
-                                d->panel_buf, d->panel, nullptr, 0, 0, nullptr, 0, 1, 1, stream, &ol));
-    } else {
-      RET(tcar_gemm_f32(1, B, n, g.ek, c->attout, g.ek, c->E + (int64_t)n0 * g.ek, g.ek, d->panel_buf, d->panel, nullptr, 0, 0, 1, stream));
-    }
-    RET(tcar_retrieve_panel(B, n0, n, d->panel_buf, d->panel, C, d->excl, d->X, w ? w->key : nullptr, w ? w->lo : nullptr,
-                            w ? w->hi : nullptr, d->state, stream));
-  }
+  RET(for_panels(c, B, c->a16h, nullptr, 1, d->panel, d->panel_buf, stream, [&](int n0, int n) {
+    return tcar_retrieve_panel(B, n0, n, d->panel_buf, d->panel, C, d->excl, d->X, w ? w->key : nullptr, w ? w->lo : nullptr,
+                               w ? w->hi : nullptr, d->state, stream);
+  }));
   return tcar_retrieve_finish(B, C, d->state, d->ids, d->scores, stream);
 }
 
@@ -1454,11 +1455,7 @@ extern "C" int tcar_retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t
 extern "C" int tcar_ragged_abi_version(void) { return TCAR_RAGGED_ABI_VERSION; }
 
 extern "C" int tcar_ragged_forward(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, void* stream) {
-  if (!rg) return TCAR_E_ARG;
-  Head h;
-  RET(forward_head(c, bt, refresh_time, stream, -1.f, false, h, rg));
-  fork_disarm(c, FK_LOGITS);           // (as every forward pass does)
-  return TCAR_OK;
+  return rg ? forward_disarm(c, bt, rg, refresh_time, stream) : (int)TCAR_E_ARG;
 }
 extern "C" int tcar_serve_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
                                       const tcar_serve_t* s, const tcar_window_t* w, const tcar_quota_t* q, void* stream) {

@@ -1030,6 +1030,15 @@ class TcarEngine(OpLevelStep):
             raise ValueError("panel must be a positive multiple of 128, at most %d" % self.SERVE_MAX_PANEL)
         return min(panel, width)
 
+    def _ensure_fold(self, specs, excl: Optional[torch.Tensor], B: int):
+        """the workspace `specs` of a panel-streaming call and, for its exclusion lists (`excl` [B, X] on the device; None: none),
+        the entry `excl` [work_B, X] with the lists copied in -> the (excl, X) fields of the call's descriptor"""
+        self.ws.ensure(specs + ([Spec("excl", (self.work_B, int(excl.shape[1])), I32)] if excl is not None else []))
+        if excl is None:
+            return None, 0
+        self.excl[:B].copy_(excl)
+        return self.excl.data_ptr(), int(excl.shape[1])
+
     def _serve(self, bt: Batch, k: int, panel: Optional[int], excl: Optional[torch.Tensor], labelled: bool, window=None,
                max_per_category=None):
         """one tcar_serve_step_quota (its window / quota NULL where the request has none); returns (rank, topk, ce, scores) views of
@@ -1041,18 +1050,13 @@ class TcarEngine(OpLevelStep):
         B = bt.B
         self._ensure_work(B, bt.T, self._rows(bt))
         wb = self.work_B
-        state_words = 2 * k + 4                  # tcar_select_state_bytes(B, k) / (4 B)
+        state_words = int(self.lib.tcar_select_state_bytes(1, k)) // 4
         specs = [Spec("panel_buf", (wb, panel), F32), Spec("sel_state", (wb, state_words), I32), Spec("lab_score", (wb,), F32),
                  Spec("sel_score", (wb, k), F32), Spec("sel_topk", (wb, k), I32), Spec("sel_rank", (wb,), I32), Spec("sel_ce", (wb,), F32)]
-        if excl is not None:
-            specs.append(Spec("excl", (wb, int(excl.shape[1])), I32))
-        self.ws.ensure(specs)
-        assert self.lib.tcar_select_state_bytes(B, k) <= self.sel_state.numel() * 4
-        if excl is not None:
-            self.excl[:B].copy_(excl)
-        s = self._serve_desc(k, panel, self.panel_buf, self.sel_state, self.excl if excl is not None else None,
-                             int(excl.shape[1]) if excl is not None else 0, self.lab_score,
+        ex = self._ensure_fold(specs, excl, B)
+        s = self._serve_desc(k, panel, self.panel_buf, self.sel_state, None, 0, self.lab_score,
                              (self.sel_topk, self.sel_score, self.sel_rank, self.sel_ce))
+        s.excl, s.X = ex
         if not labelled:
             bt = self._without_neg(bt, label=False)
         w = self._window(window, B) if window is not None else None
@@ -1236,24 +1240,17 @@ class TcarEngine(OpLevelStep):
         B = bt.B
         self._ensure_work(B, bt.T, self._rows(bt))
         wb = self.work_B
-        state_words = 2 * C_ + 4                 # tcar_retrieve_state_bytes(B, C) / (4 B)
+        state_words = int(self.lib.tcar_retrieve_state_bytes(1, C_)) // 4
         specs = [Spec("panel_buf", (wb, panel), F32), Spec("rt_state", (wb, state_words), I32), Spec("rt_ids", (wb, C_), I32),
                  Spec("rt_scores", (wb, C_), F32)]
         if k is not None:
             k = int(k)
             specs += [Spec("rt_exact", (wb, C_), F32), Spec("rt_rank", (2, wb, C_), I32), Spec("rt_topk", (wb, k), I32),
                       Spec("rt_topscore", (wb, k), F32)]
-        if excl is not None:
-            specs.append(Spec("excl", (wb, int(excl.shape[1])), I32))
-        self.ws.ensure(specs)
-        assert self.lib.tcar_retrieve_state_bytes(B, C_) <= self.rt_state.numel() * 4
-        if excl is not None:
-            self.excl[:B].copy_(excl)
         d = Retrieve()
+        d.excl, d.X = self._ensure_fold(specs, excl, B)
         d.C, d.panel, d.panel_buf = C_, panel, self.panel_buf.data_ptr()
         d.state, d.state_bytes = self.rt_state.data_ptr(), self.rt_state.numel() * 4
-        if excl is not None:
-            d.excl, d.X = self.excl.data_ptr(), int(excl.shape[1])
         d.ids, d.scores = self.rt_ids.data_ptr(), self.rt_scores.data_ptr()
         w = self._window(window, B) if window is not None else None
         if w is not None:
