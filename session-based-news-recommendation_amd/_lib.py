@@ -35,10 +35,11 @@ def _hipcc() -> str:
 # The C ABI, one row per layer: (prefix of the layer's names in this module, its header under include/).  Every header is compiled
 # into the library AND read by _bind(), and each builds on the rows above it: the core; streamed score-and-select; its publish-time
 # windows; its per-category caps; the state merge and the shard's fold of the catalog-sharded serving path; candidate-list scoring;
-# the streamed top-C shortlist and the two-stage step; ragged batches (sessions of mixed lengths) under every serving step.
+# the streamed top-C shortlist and the two-stage step; the shortlist merge, the owner-aware candidate gather and the shard's side
+# of both on the catalog-sharded engine; ragged batches (sessions of mixed lengths) under every serving step.
 ABI_LAYERS = [("", "tcar_hip.h"), ("SERVE", "tcar_serve.h"), ("WINDOW", "tcar_window.h"), ("QUOTA", "tcar_quota.h"),
               ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"), ("RETRIEVE", "tcar_retrieve.h"),
-              ("RAGGED", "tcar_ragged.h")]
+              ("RETRIEVE_SHARD", "tcar_retrieve_shard.h"), ("RAGGED", "tcar_ragged.h")]
 
 
 def _name(prefix: str, name: str) -> str:

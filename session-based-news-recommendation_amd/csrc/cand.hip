@@ -9,7 +9,7 @@
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
 #include "topk_rows.h"
-#include "../../include/tcar_cand.h"
+#include "../../include/tcar_retrieve_shard.h"
 
 namespace {
 
@@ -51,12 +51,13 @@ __device__ __forceinline__ float cs_chain(float4 a, float4 e, float acc) {
 }
 
 // grid (B, ceil(C / CS_WG)).  NI > 0: the register form for K <= 256 NI; NI == 0: any K.  a0 / a1, e0 / e1: hi / lo planes (a1, e1 read
-// by CS_X3 only), or the fp32 matrices in a0 / e0.
+// by CS_X3 only), or the fp32 matrices in a0 / e0.  id0: the catalog id of the operands' first row (0: the whole catalog) — slot id i reads
+// local row i - id0 iff (unsigned)(i - id0) < N; the dot itself knows nothing of it.
 template <int MODE, int NI>
 __global__ __launch_bounds__(CS_NT) void cand_scores_kernel(int C, int N, int K, const void* __restrict__ a0, const void* __restrict__ a1,
                                                             long a_ld, const void* __restrict__ e0, const void* __restrict__ e1, long e_ld,
                                                             const int32_t* __restrict__ cand, long ld_cand, float* __restrict__ out,
-                                                            long ld_out) {
+                                                            long ld_out, int id0) {
   typedef typename CsRaw<MODE>::T raw_t;
   constexpr bool X3 = MODE == CS_X3;
   constexpr int NR = NI > 0 ? NI : 1;
@@ -79,8 +80,9 @@ __global__ __launch_bounds__(CS_NT) void cand_scores_kernel(int C, int N, int K,
     bool ok[CS_U];                 // wave-uniform: an id outside the catalog reads no row
 #pragma unroll
     for (int u = 0; u < CS_U; ++u) {
-      id[u] = c + u < c1 ? __builtin_amdgcn_readfirstlane(cb[c + u]) : -1;
-      ok[u] = (unsigned)id[u] < (unsigned)N;
+      const unsigned loc = (unsigned)(c + u < c1 ? __builtin_amdgcn_readfirstlane(cb[c + u]) : -1) - (unsigned)id0;
+      ok[u] = c + u < c1 && loc < (unsigned)N;
+      id[u] = (int)loc;
     }
     float acc[CS_U], acs[CS_U];
 #pragma unroll
@@ -245,25 +247,64 @@ inline bool bad_bc(int B, int C) { return B < 0 || C < 1 || C > CAND_MAX_C; }
 
 template <int MODE>
 void launch_scores(int B, int C, int N, int K, const void* a0, const void* a1, long a_ld, const void* e0, const void* e1, long e_ld,
-                   const int32_t* cand, long ld_cand, float* out, long ld_out, hipStream_t s) {
+                   const int32_t* cand, long ld_cand, float* out, long ld_out, int id0, hipStream_t s) {
   const dim3 grid((unsigned)B, (unsigned)((C + CS_WG - 1) / CS_WG)), block(CS_NT);
   if (K <= 256)
-    TCAR_LAUNCH((cand_scores_kernel<MODE, 1>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out);
+    TCAR_LAUNCH((cand_scores_kernel<MODE, 1>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out, id0);
   else if (K <= 512)
-    TCAR_LAUNCH((cand_scores_kernel<MODE, 2>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out);
+    TCAR_LAUNCH((cand_scores_kernel<MODE, 2>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out, id0);
   else if (K <= 256 * CS_NI)
-    TCAR_LAUNCH((cand_scores_kernel<MODE, CS_NI>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out);
+    TCAR_LAUNCH((cand_scores_kernel<MODE, CS_NI>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out, id0);
   else
-    TCAR_LAUNCH((cand_scores_kernel<MODE, 0>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out);
+    TCAR_LAUNCH((cand_scores_kernel<MODE, 0>), grid, block, 0, s, C, N, K, a0, a1, a_ld, e0, e1, e_ld, cand, ld_cand, out, ld_out, id0);
+}
+
+// ---- the shards' score parts of a list -> the list's scores (include/tcar_retrieve_shard.h): slot (b, c) takes the WORD its owner wrote,
+// owner = id / rows_per_shard; an id outside [0, N) or an owner >= S: -inf.  A copy of bits (NaN payloads and -0.0 included), one thread
+// per slot.  Bounds: c < C <= ld of every matrix, owner < S, the part's row b starts at owner * stride + b * C.
+constexpr int CC_NT = 256;
+__global__ __launch_bounds__(CC_NT) void cand_combine_kernel(int C, int S, int rows_per_shard, int N, const int32_t* __restrict__ cand,
+                                                             long ld_cand, const uint32_t* __restrict__ parts, long stride,
+                                                             uint32_t* __restrict__ out, long ld_out) {
+  const int b = blockIdx.x;
+  for (int c = blockIdx.y * CC_NT + threadIdx.x; c < C; c += gridDim.y * CC_NT) {
+    const int id = cand[(long)b * ld_cand + c];
+    const int owner = (unsigned)id < (unsigned)N ? id / rows_per_shard : S;
+    out[(long)b * ld_out + c] = owner < S ? parts[(long)owner * stride + (long)b * C + c] : 0xff800000u;
+  }
 }
 
 }  // namespace
+
+extern "C" int tcar_cand_combine(int B, int C, int S, int rows_per_shard, int N, const int32_t* cand, int64_t ld_cand, const float* parts,
+                                 int64_t stride, float* out, int64_t ld_out, void* stream) {
+  if (bad_bc(B, C) || S < 1 || S > 64 || rows_per_shard < 1 || N < 1 || ld_cand < C || ld_out < C) return TCAR_E_ARG;
+  if (S > 1 && stride < (int64_t)B * C) return TCAR_E_ARG;
+  if (B == 0) return TCAR_OK;
+  if (!cand || !parts || !out || ((uintptr_t)parts & 3) || ((uintptr_t)out & 3)) return TCAR_E_ARG;
+  const uintptr_t in0 = (uintptr_t)parts, in1 = in0 + (uintptr_t)(((int64_t)(S - 1) * stride + (int64_t)B * C) * 4);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)((((int64_t)B - 1) * ld_out + C) * 4);
+  if (o0 < in1 && in0 < o1) return TCAR_E_ARG;            // out overlaps the parts
+  TCAR_LAUNCH(cand_combine_kernel, dim3((unsigned)B, (unsigned)((C + CC_NT - 1) / CC_NT)), dim3(CC_NT), 0, (hipStream_t)stream, C, S,
+              rows_per_shard, N, cand, (long)ld_cand, (const uint32_t*)parts, (long)stride, (uint32_t*)out, (long)ld_out);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
 
 extern "C" int tcar_cand_abi_version(void) { return TCAR_CAND_ABI_VERSION; }
 
 extern "C" int tcar_cand_scores(int B, int C, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE,
                                 const void* a_hi, const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner,
                                 int nsplit, const int32_t* cand, int64_t ld_cand, float* out, int64_t ld_out, void* stream) {
+  return tcar_cand_scores_owned(B, C, N, K, att, ld_att, E, ldE, a_hi, a_lo, a_inner, e_hi, e_lo, e_inner, nsplit, cand, ld_cand, out,
+                                ld_out, 0, stream);
+}
+
+extern "C" int tcar_cand_scores_owned(int B, int C, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE,
+                                      const void* a_hi, const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo,
+                                      int64_t e_inner, int nsplit, const int32_t* cand, int64_t ld_cand, float* out, int64_t ld_out,
+                                      int id0, void* stream) {
+  if (id0 < 0 || (int64_t)id0 + N > 0x7fffffffL) return TCAR_E_ARG;
   if (bad_bc(B, C) || N <= 0 || K <= 0 || (K & 3) || ld_cand < C || ld_out < C) return TCAR_E_ARG;
   if (B == 0) return TCAR_OK;
   if (a_hi) {
@@ -278,13 +319,13 @@ extern "C" int tcar_cand_scores(int B, int C, int N, int K, const float* att, in
   if (a_hi) {
     if (nsplit == 3)
       launch_scores<CS_X3>(B, C, N, K, a_hi, a_lo, (long)(a_inner >> 5), e_hi, e_lo, (long)(e_inner >> 5), cand, (long)ld_cand, out,
-                           (long)ld_out, s);
+                           (long)ld_out, id0, s);
     else
       launch_scores<CS_HI>(B, C, N, K, a_hi, nullptr, (long)(a_inner >> 5), e_hi, nullptr, (long)(e_inner >> 5), cand, (long)ld_cand, out,
-                           (long)ld_out, s);
+                           (long)ld_out, id0, s);
   } else {
     if (!att || !E || !tcar_aligned16(att) || !tcar_aligned16(E)) return TCAR_E_ARG;
-    launch_scores<CS_F32>(B, C, N, K, att, nullptr, (long)ld_att, E, nullptr, (long)ldE, cand, (long)ld_cand, out, (long)ld_out, s);
+    launch_scores<CS_F32>(B, C, N, K, att, nullptr, (long)ld_att, E, nullptr, (long)ldE, cand, (long)ld_cand, out, (long)ld_out, id0, s);
   }
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;

@@ -11,7 +11,7 @@
 #include "tcar_common.h"
 #include "topk_rows.h"
 #include "panel_fold.h"
-#include "../../include/tcar_retrieve.h"
+#include "../../include/tcar_retrieve_shard.h"
 
 namespace {
 
@@ -60,16 +60,18 @@ __device__ __forceinline__ float rt_score(rt_key_t k) {
 //
 // Bounds: a buffer index is < cap <= RT_MAX_CAP by the `pos < cap` test of the append and the loops of the prune; the bitmap index is
 // < (n + 31) / 32 <= SEL_MAX_N / 32 by the 0 <= e < n test; row loads are guarded by c < n (c % 4 == 0, ld % 4 == 0, n <= ld); key
-// loads are clamped into [0, n).
+// loads are clamped into [0, n).  live: NULL, or one word per session — live[b] < 0: the session is padding, its workgroup returns
+// before it reads anything else (uniform: ahead of every barrier) and its state stays as it was.
 template <bool W>
 __global__ __launch_bounds__(RT_NT) void retrieve_panel_kernel(int n0, int n, const float* __restrict__ panel, long ld, int C,
                                                                const int32_t* __restrict__ excl, int X, float* __restrict__ state,
                                                                const int32_t* __restrict__ key, const int32_t* __restrict__ wlo,
-                                                               const int32_t* __restrict__ whi) {
+                                                               const int32_t* __restrict__ whi, const int32_t* __restrict__ live) {
   __shared__ rt_key_t buf[RT_MAX_CAP];
   __shared__ unsigned exb[SEL_MAX_N / 32];
   __shared__ int cnt;               // entries in the buffer + elements that asked for a place
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  if (live && live[b] < 0) return;
   const int cap = rt_cap(C);
   const float* row = panel + (long)b * ld;
   float* st = state + (long)b * fold_row_words(C);
@@ -216,6 +218,69 @@ __global__ __launch_bounds__(64) void rerank_take_kernel(int C, int k, const int
   if (score && in) score[(long)b * k + j] = cand_score[(long)b * C + s];
 }
 
+// S states of one session -> one (include/tcar_retrieve_shard.h).  One workgroup per session.  Every input list is already in list
+// order, so a shard is taken in by ONE bitonic merge step, not a sort: the running best sits in buf[0, Cp) descending, zero-padded at
+// the end (Cp = C rounded up to a power of two; 0 = "nothing" sorts below every key); shard s's entries go REVERSED into buf[Cp, 2 Cp),
+// zero-padded at the front — descending then ascending is a bitonic sequence —, the log2(2 Cp) compare-exchange stages leave
+// buf[0, 2 Cp) descending, and what lies past the first C is dropped.  11 stages per shard at C = 1,024 against 66 of a full sort.
+// A shard that holds nothing is skipped, and so is one whose best key does not beat the C-th key once C entries are held (its list
+// is descending: nothing of it can enter); both tests read one word every thread sees alike, so control flow stays uniform.  The
+// items of the shards are disjoint, so all keys differ and the result does not depend on the order of the shards.
+//
+// Bounds: a buffer index is < 2 Cp <= RT_MAX_CAP (the loops run over [0, Cp) and the pair (i, i + j) of stage j has i + j < 2 Cp);
+// of an input row the words [0, hs), [C, C + hs) and 2 C are read with hs clamped into [0, C]; the row of (s, b) starts at
+// s * stride + b * (2 C + 4) words, inside what the host checked; the output row takes its 2 C + 4 words and nothing else.
+__global__ __launch_bounds__(RT_NT) void retrieve_merge_kernel(int C, int S, const float* __restrict__ states, long stride,
+                                                               float* __restrict__ out) {
+  __shared__ rt_key_t buf[RT_MAX_CAP];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int rw = fold_row_words(C);
+  int Cp = 1;
+  while (Cp < C) Cp <<= 1;
+  for (int i = tid; i < Cp; i += RT_NT) buf[i] = 0ull;
+  __syncthreads();
+  int held = 0;                     // uniform: entries of buf[0, Cp) that are real
+  for (int s = 0; s < S; ++s) {
+    const float* st = states + (long)s * stride + (long)b * rw;
+    const int* sti = reinterpret_cast<const int*>(st);
+    int hs = sti[2 * C];
+    hs = hs < 0 ? 0 : hs > C ? C : hs;
+    if (hs == 0) continue;
+    if (held == C && !(rt_key(st[0], sti[C]) > buf[C - 1])) continue;
+    for (int i = tid; i < Cp; i += RT_NT) {
+      const int j = Cp - 1 - i;     // entry j of the shard's list lands at Cp + i
+      buf[Cp + i] = j < hs ? rt_key(st[j], sti[C + j]) : 0ull;
+    }
+    __syncthreads();
+    for (int j = Cp; j > 0; j >>= 1) {
+      for (int t = tid; t < Cp; t += RT_NT) {
+        const int i = 2 * t - (t & (j - 1)), l = i + j;
+        const rt_key_t x = buf[i], y = buf[l];
+        if (x < y) { buf[i] = y; buf[l] = x; }
+      }
+      __syncthreads();
+    }
+    held = held + hs < C ? held + hs : C;
+    for (int i = C + tid; i < Cp; i += RT_NT) buf[i] = 0ull;      // (keep the first C: the zero padding of the next step)
+    __syncthreads();
+  }
+  float* o = out + (long)b * rw;
+  int* oi = reinterpret_cast<int*>(o);
+  for (int i = tid; i < C; i += RT_NT) {
+    const bool in = i < held;
+    const rt_key_t k = in ? buf[i] : 0ull;
+    o[i] = in ? rt_score(k) : -INFINITY;
+    oi[C + i] = in ? rt_id(k) : -1;
+  }
+  if (tid == 0) {
+    const rt_key_t thr = held == C ? buf[C - 1] : 0ull;
+    oi[2 * C] = held;
+    oi[2 * C + 1] = (int)(unsigned)thr;
+    oi[2 * C + 2] = (int)(unsigned)(thr >> 32);
+    oi[2 * C + 3] = 0;
+  }
+}
+
 inline bool bad_bc(int B, int C) { return bad_fold_bm(B, C, RT_MAX_C); }
 
 }  // namespace
@@ -231,15 +296,21 @@ extern "C" int tcar_retrieve_reset(int B, int C, void* state, void* stream) {
   return tcar_fold_reset(B, C, RT_MAX_C, FoldTail{}, state, stream);
 }
 
-extern "C" int tcar_retrieve_panel(int B, int n0, int n, const float* panel, int64_t ld, int C, const int32_t* excl, int X,
-                                   const int32_t* key, const int32_t* lo, const int32_t* hi, void* state, void* stream) {
+extern "C" int tcar_retrieve_panel_live(int B, int n0, int n, const float* panel, int64_t ld, int C, const int32_t* excl, int X,
+                                        const int32_t* key, const int32_t* lo, const int32_t* hi, void* state, const int32_t* live,
+                                        void* stream) {
   bool empty;
   if (const int rc = check_fold_args(B, C, RT_MAX_C, n0, n, panel, ld, excl, X, key, lo, hi, state, &empty); rc != TCAR_OK || empty)
     return rc;
   TCAR_LAUNCH((key ? retrieve_panel_kernel<true> : retrieve_panel_kernel<false>), dim3(B), dim3(RT_NT), 0, (hipStream_t)stream, n0, n,
-              panel, (long)ld, C, excl, X, (float*)state, key, lo, hi);
+              panel, (long)ld, C, excl, X, (float*)state, key, lo, hi, live);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
+}
+
+extern "C" int tcar_retrieve_panel(int B, int n0, int n, const float* panel, int64_t ld, int C, const int32_t* excl, int X,
+                                   const int32_t* key, const int32_t* lo, const int32_t* hi, void* state, void* stream) {
+  return tcar_retrieve_panel_live(B, n0, n, panel, ld, C, excl, X, key, lo, hi, state, nullptr, stream);
 }
 
 extern "C" int tcar_retrieve_finish(int B, int C, const void* state, int32_t* ids, float* scores, void* stream) {
@@ -251,8 +322,25 @@ extern "C" int tcar_retrieve_finish(int B, int C, const void* state, int32_t* id
   return TCAR_OK;
 }
 
-// the closing launch of tcar_retrieve_rerank_step (step.hip): arguments are the driver's, checked there
-int tcar_rerank_take(int B, int C, int k, const int32_t* ids, const float* cand_score, const int32_t* order, int32_t* topk, float* score,
+extern "C" int tcar_retrieve_shard_abi_version(void) { return TCAR_RETRIEVE_SHARD_ABI_VERSION; }
+
+extern "C" int tcar_retrieve_merge(int B, int C, int S, const void* states, int64_t stride_words, void* out, void* stream) {
+  if (bad_bc(B, C) || S < 1 || S > 64) return TCAR_E_ARG;
+  const int64_t rows = (int64_t)B * fold_row_words(C);
+  if (S > 1 && stride_words < rows) return TCAR_E_ARG;
+  if (B == 0) return TCAR_OK;
+  if (!states || !out || ((uintptr_t)states & 3) || ((uintptr_t)out & 3)) return TCAR_E_ARG;
+  const uintptr_t in0 = (uintptr_t)states, in1 = in0 + (uintptr_t)(((int64_t)(S - 1) * stride_words + rows) * 4);
+  const uintptr_t o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)(rows * 4);
+  if (o0 < in1 && in0 < o1) return TCAR_E_ARG;            // out overlaps the inputs
+  TCAR_LAUNCH(retrieve_merge_kernel, dim3(B), dim3(RT_NT), 0, (hipStream_t)stream, C, S, (const float*)states, (long)stride_words,
+              (float*)out);
+  TCAR_CHECK_LAUNCH();
+  return TCAR_OK;
+}
+
+// the closing launch of tcar_retrieve_rerank_step (step.hip) and of the sharded two-stage call (include/tcar_retrieve_shard.h)
+extern "C" int tcar_rerank_take(int B, int C, int k, const int32_t* ids, const float* cand_score, const int32_t* order, int32_t* topk, float* score,
                      void* stream) {
   if (B <= 0) return TCAR_OK;
   if (k < 1 || k > SEL_MAX_K || k > C || !ids || !cand_score || !order || !topk) return TCAR_E_ARG;

@@ -5,7 +5,7 @@
 #include "tcar_common.h"
 #include "../../include/tcar_serve_shard.h"
 #include "../../include/tcar_cand.h"
-#include "../../include/tcar_retrieve.h"
+#include "../../include/tcar_retrieve_shard.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1657,6 +1657,32 @@ extern "C" int tcar_shard_serve_fold(const tcar_ctx_t* sc, const tcar_shard_t* s
   const int Bq = sh->world * sh->cap;
   if (s->state_bytes < tcar_select_state_bytes(Bq, s->k)) return TCAR_E_ARG;
   return serve_fold(sc, Bq, sh->a16h, sh->a16l, sh->n0, label, lab_score, s, w, q, stream);
+}
+
+// ---- retrieve-then-rank on a catalog shard (include/tcar_retrieve_shard.h; sharded.py: ShardExchange.retrieve / .candidates)
+extern "C" int tcar_shard_retrieve_fold(const tcar_ctx_t* sc, const tcar_shard_t* sh, const tcar_retrieve_t* d, const int32_t* live,
+                                        void* stream) {
+  if (!d) return TCAR_E_ARG;
+  RET(check_panel_desc(d->panel, d->panel_buf, d->excl, d->X, d->window));
+  if (d->C < 1 || d->C > CAND_MAX_C || !d->state) return TCAR_E_ARG;
+  RET(check_shard_serve(sc, sh));
+  const int Bq = sh->world * sh->cap, C = d->C;
+  if (d->state_bytes < tcar_retrieve_state_bytes(Bq, C)) return TCAR_E_ARG;
+  const tcar_window_t* w = d->window;
+  RET(tcar_retrieve_reset(Bq, C, d->state, stream));
+  return for_panels(sc, Bq, sh->a16h, nullptr, 1, d->panel, d->panel_buf, stream, [&](int n0, int n) {
+    return tcar_retrieve_panel_live(Bq, sh->n0 + n0, n, d->panel_buf, d->panel, C, d->excl, d->X, w ? w->key : nullptr,
+                                    w ? w->lo : nullptr, w ? w->hi : nullptr, d->state, live, stream);
+  });
+}
+
+extern "C" int tcar_shard_cand_scores(const tcar_ctx_t* sc, const tcar_shard_t* sh, int C, const int32_t* cand, int64_t ld_cand,
+                                      float* part, int64_t ld_part, void* stream) {
+  if (C < 1 || C > CAND_MAX_C || ld_cand < C || ld_part < C || !cand || !part) return TCAR_E_ARG;
+  RET(check_shard_serve(sc, sh));
+  const Geo g(sc->d);
+  return tcar_cand_scores_owned(sh->world * sh->cap, C, sh->n_loc, g.ek, nullptr, 0, nullptr, 0, sh->a16h, sh->a16l, g.ek, sc->e16h,
+                                sc->e16l, g.ek, sc->scoring, cand, ld_cand, part, ld_part, sh->n0, stream);
 }
 
 extern "C" int tcar_shard_backward(const tcar_ctx_t* c, const tcar_shard_t* s, const float* stats_all, void* stream) {

@@ -265,10 +265,6 @@ int tcar_label_scores(int B, int N, int K, const float* att, int64_t ld_att, con
 int tcar_label_scores_owned(int B, int N, int K, const float* att, int64_t ld_att, const float* E, int64_t ldE, const void* a_hi,
                             const void* a_lo, int64_t a_inner, const void* e_hi, const void* e_lo, int64_t e_inner, int nsplit,
                             const int32_t* label, float* out, int lab0, int owned_only, void* stream);
-// retrieve.hip: topk[b, j] = ids[b, order[b, j]] and score[b, j] = cand_score[b, order[b, j]] for the first k ranks of every list
-// (order: tcar_cand_rank's, [B, C]); -1 / untouched behind a list's end
-int tcar_rerank_take(int B, int C, int k, const int32_t* ids, const float* cand_score, const int32_t* order, int32_t* topk, float* score,
-                     void* stream);
 
 // 16-byte write-through store (sc1): the bytes bypass the write-back state of this XCD's L2, so a consumer behind a completion
 // flag needs no release fence / L2 write-back from the producer (cdna_hip_programming.md Guideline 16, R1).  The compiler does not

@@ -58,6 +58,9 @@ class _GroupOps:
     def all_reduce(self, t: torch.Tensor):
         dist.all_reduce(t, group=self.group)
 
+    def all_to_all(self, send: torch.Tensor, recv: torch.Tensor):
+        dist.all_to_all_single(recv.view(-1), send.reshape(-1), group=self.group)
+
 
 class Collectives:
     """The collectives of both exchanges (`GradExchange` below, `sharded.ShardExchange`: each is this layer plus its schedule),
@@ -71,12 +74,16 @@ class Collectives:
                    per-rank compute of a large job on one GPU, results meaningless beyond their shapes)
       direct       None: RCCL directly on the nccl backend unless TCAR_RCCL_DIRECT=0; False: the process group; True: required
       reduce_scatter   None: where the backend has one (nccl); otherwise all-reduce + slice
+      all_to_all   None: tried where collectives are live — the direct communicator says at its self-test whether it has one
+                   (rccl.make_direct), a process group whose backend raises at the first call is remembered as having none;
+                   without one all_to_all_rows is an all-gather + slice.  `all_to_all_path` names the path taken
     Collectives issued with a key are counted for bench.py and the tests: `order`, `bytes_moved`, and with `timing` on (never in a
     headline pass: an event pair costs its stream a few us) a span per call — CUDA events on the issuing stream, host seconds on
     CPU — averaged by collective_ms()."""
 
     def __init__(self, group=None, world: Optional[int] = None, rank: Optional[int] = None, sim: Optional[bool] = False,
-                 reduce_scatter: Optional[bool] = None, force: Optional[bool] = None, direct: Optional[bool] = None):
+                 reduce_scatter: Optional[bool] = None, force: Optional[bool] = None, direct: Optional[bool] = None,
+                 all_to_all: Optional[bool] = None):
         live = dist.is_available() and dist.is_initialized()
         if sim is None:
             w = int(os.environ.get("TCAR_SIM_WORLD", "0")) if not live and world is None else 0
@@ -105,6 +112,8 @@ class Collectives:
             if direct is True and self.direct is None:
                 raise RuntimeError("the direct RCCL path was required and could not be built")
         self.ops = self.direct if self.direct is not None else _GroupOps(group)
+        self.use_all_to_all = (getattr(self.ops, "has_all_to_all", True) if all_to_all is None else bool(all_to_all)) and self.collective
+        self.all_to_all_path = "none"
         self.bytes_moved: Dict[str, int] = {}
         self.order = []
         self.timing = False
@@ -174,6 +183,32 @@ class Collectives:
             return out
         self._timed(key, full, self.ops.all_reduce, full)     # gloo (CPU tests, single-GPU dry runs): all-reduce + slice
         return full[self.rank * cap:(self.rank + 1) * cap]
+
+    def all_to_all_rows(self, t: torch.Tensor, cap: int, key: Optional[str] = None) -> torch.Tensor:
+        """t [W*cap, x] -> [W, cap, x]: the rows [rank cap, (rank + 1) cap) of EVERY rank's t, rank-major — what this rank needs of a
+        result every rank holds for the sessions of all ranks, a W-th of what an all-gather would move.  No collective: a view of
+        this rank's rows (sim: W copies of them); a backend without an all-to-all: all-gather + slice, the same bytes out"""
+        mine = t[self.rank * cap:(self.rank + 1) * cap]
+        if self.sim:
+            return mine.unsqueeze(0).expand((self.world,) + tuple(mine.shape)).contiguous()
+        if not self.collective:
+            return mine.unsqueeze(0)
+        self._note(key, t)
+        t = t.contiguous()
+        if self.use_all_to_all:
+            out = torch.empty((self.world, cap) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            try:
+                self._timed(key, t, self.ops.all_to_all, t, out)
+                self.all_to_all_path = "all-to-all (%s)" % ("RCCL C API" if self.direct is not None else self.backend)
+                return out
+            except (RuntimeError, NotImplementedError, AttributeError) as e:
+                # a backend without the collective refuses on every rank alike, before anything is sent: remembered, not fatal
+                self.use_all_to_all = False
+                self.all_to_all_error = "%s: %s" % (type(e).__name__, str(e).splitlines()[0][:120] if str(e) else "")
+        full = torch.empty((self.world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+        self._timed(key, t, self.ops.all_gather, t, full)
+        self.all_to_all_path = "all-gather + slice (%s)" % self.backend
+        return full[:, self.rank * cap:(self.rank + 1) * cap].contiguous()
 
     def all_reduce(self, t: torch.Tensor, key: Optional[str] = None) -> torch.Tensor:
         """in-place sum over the ranks (direct: asserts contiguity — an in-place collective on a copy would be lost)"""
@@ -247,11 +282,14 @@ class GradExchange(Collectives):
         self.finish(all_ids, all_rows, sqnorm_item, cand_time_bwd, scatter_rows, sqnorm_dense)
 
 
-def known_answers(ops, world: int, rank: int, dev) -> Optional[str]:
-    """ONE tiny in-place all-reduce, all-gather and reduce-scatter (the three collectives the exchanges use) through `ops` — the
-    process group (`preflight`) or a direct communicator (rccl.make_direct) — on `dev`, then the results of those issued against
+def known_answers(ops, world: int, rank: int, dev, caps: Optional[dict] = None) -> Optional[str]:
+    """ONE tiny in-place all-reduce, all-gather and reduce-scatter (the three collectives the training exchanges use) through `ops` —
+    the process group (`preflight`) or a direct communicator (rccl.make_direct) — on `dev`, then the results of those issued against
     their known answers (every rank issues all three first: a wrong answer stops no rank short of its peers' collectives).  Returns
-    None, or "<collective>: <what went wrong>" for the first that answered wrongly, else for the one that raised."""
+    None, or "<collective>: <what went wrong>" for the first that answered wrongly, else for the one that raised.
+    The all-to-all of the sharded retrieval (Collectives.all_to_all_rows) is OPTIONAL: it is issued last; where `ops` has none (it
+    raises, on every rank alike) caps["all_to_all"] is False and nothing is reported — the layer falls back to all-gather + slice —,
+    where it answers, the answer is checked like the others."""
     t = torch.full((4,), float(rank + 1), device=dev)
     mine, out = torch.full((3,), float(rank), device=dev), torch.empty(world * 3, device=dev)
     full, part = torch.arange(world * 2, dtype=torch.float32, device=dev) + rank, torch.empty(2, device=dev)
@@ -267,6 +305,19 @@ def known_answers(ops, world: int, rank: int, dev) -> Optional[str]:
             torch.cuda.synchronize(dev)
     except Exception as e:
         err = "%s: %s: %s" % (step, type(e).__name__, e)
+    a2a_send = torch.arange(world * 2, dtype=torch.float32, device=dev) + 100 * rank
+    a2a_recv, has_a2a = torch.empty(world * 2, device=dev), False
+    if err is None or step == "reduce_scatter":
+        try:
+            ops.all_to_all(a2a_send, a2a_recv)
+            if dev.type == "cuda":
+                torch.cuda.synchronize(dev)
+            has_a2a = True
+        except Exception as e:
+            if caps is not None:
+                caps["all_to_all_error"] = ("%s: %s" % (type(e).__name__, e)).splitlines()[0][:120]
+    if caps is not None:
+        caps["all_to_all"] = has_a2a
     for name, got, want in (("all_reduce", t, [world * (world + 1) / 2.0] * 4),
                             ("all_gather", out.view(world, 3)[:, 0], [float(r) for r in range(world)]),
                             ("reduce_scatter", part, [world * (2 * rank + j) + world * (world - 1) / 2.0 for j in range(2)])):
@@ -274,6 +325,8 @@ def known_answers(ops, world: int, rank: int, dev) -> Optional[str]:
             break
         if got.tolist() != want:
             return "%s: returned %r, expected %r" % (name, got.tolist(), want)
+    if has_a2a and a2a_recv.tolist() != [100.0 * r + 2 * rank + j for r in range(world) for j in range(2)]:
+        return "all_to_all: returned %r" % (a2a_recv.tolist(),)
     return err
 
 
@@ -294,7 +347,7 @@ def preflight(group=None, device=None, verbose: bool = True) -> Dict[str, object
             info["rccl"] = ".".join(str(x) for x in torch.cuda.nccl.version())
     except Exception as e:                                   # version query only: never fatal
         info["rccl"] = "unknown (%s)" % type(e).__name__
-    bad = known_answers(_GroupOps(group), world, rank, dev)
+    bad = known_answers(_GroupOps(group), world, rank, dev, info)
     if bad is not None and (backend == "nccl" or not bad.startswith("reduce_scatter:")):
         raise RuntimeError("collective preflight failed at %s (%s)" % (bad, info))
     info["reduce_scatter"] = bad is None

@@ -89,6 +89,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
                          "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  "
                          "0: the materialised evaluation of the catalog-sharded engine")
+    ap.add_argument("--shard_eval_shortlist", default=0, type=int,
+                    help="C > 0 (only with --dp_mode sharded and --shard_eval_panel P): evaluation additionally runs the two-stage "
+                         "recommendation over the shards on every batch (include/tcar_retrieve_shard.h: every shard's shortlist of C items "
+                         "from coarse scores merged exactly, re-scored by the rows' owners, cut to 20) and prints the line of "
+                         "--eval_shortlist; 65 <= C <= " + str(MAX_SHORTLIST) + ".  0: off")
     ap.add_argument("--eval_candidates", default=0, type=int,
                     help="C > 0: evaluation additionally ranks every label among C - 1 other items drawn uniformly from the catalog "
                          "(include/tcar_cand.h: only those C rows are scored) and prints their AUC / MRR / nDCG@5 / nDCG@10; "
@@ -180,6 +185,20 @@ def check_eval_shortlist(eval_shortlist, eval_panel, dp_mode, cat_cap=0):
         raise ValueError("--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap")
 
 
+def check_shard_eval_shortlist(shard_eval_shortlist, shard_eval_panel, dp_mode):
+    """--shard_eval_shortlist runs the two-stage recommendation of the catalog-sharded engine (include/tcar_retrieve_shard.h) beside
+    its streamed evaluation and compares their lists: it needs --dp_mode sharded and --shard_eval_panel"""
+    if not shard_eval_shortlist:
+        return
+    if shard_eval_shortlist < 65 or shard_eval_shortlist > MAX_SHORTLIST:
+        raise ValueError("--shard_eval_shortlist must be in [65, %d] (0: off)" % MAX_SHORTLIST)
+    if dp_mode != "sharded":
+        raise ValueError("--shard_eval_shortlist merges the shortlists of the catalog-sharded engine: it needs --dp_mode sharded "
+                         "(one engine with the whole catalog: --eval_shortlist)")
+    if not shard_eval_panel:
+        raise ValueError("--shard_eval_shortlist needs --shard_eval_panel P: its lists are compared with those of the streamed evaluation")
+
+
 def check_eval_mixed(eval_mixed, eval_panel, dp_mode, gpus=1, eval_candidates=0, eval_shortlist=0):
     """--eval_mixed packs the batches of the streamed evaluation of ONE engine into ragged batches (include/tcar_ragged.h): it needs
     --eval_panel and one process; the candidate and two-stage passes keep their rectangular batches"""
@@ -260,6 +279,7 @@ def main(argv=None):
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
     check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
+    check_shard_eval_shortlist(args.shard_eval_shortlist, args.shard_eval_panel, args.dp_mode)
     check_eval_mixed(args.eval_mixed, args.eval_panel, args.dp_mode, args.gpus, args.eval_candidates, args.eval_shortlist)
     dp_group = None
     if args.gpus > 1:

@@ -143,6 +143,7 @@ class Seq2SeqAttNN():
         self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
         self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
         self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
+        self.shard_eval_shortlist = self._shard_eval_shortlist(args)   # C > 0: test() also runs the SHARDED two-stage recommendation
         self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
@@ -205,6 +206,12 @@ class Seq2SeqAttNN():
         """eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
         panel, cap, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'cat_cap', 'eval_shortlist'))
         cli.check_eval_shortlist(short, panel, args.get('dp_mode', 'replica'), cap)
+        return short
+
+    def _shard_eval_shortlist(self, args) -> int:
+        """shard_eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        spanel, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('shard_eval_panel', 'shard_eval_shortlist'))
+        cli.check_shard_eval_shortlist(short, spanel, args.get('dp_mode', 'replica'))
         return short
 
     def _eval_mixed(self, args) -> int:
@@ -434,7 +441,8 @@ class Seq2SeqAttNN():
             raise ValueError("eval_candidates ranks the label among OTHER items: the catalog holds fewer than two")
         cand_rng = np.random.RandomState(self.seed) if ncand else None       # a stream of its own: no other random stream of the run moves
         cand_pending = []
-        short = self._eval_shortlist(args)
+        sshort = self._shard_eval_shortlist(args)                # the sharded two-stage call: the same line, the same metrics
+        short = self._eval_shortlist(args) or sshort
         short_pending = []
         if spanel and not hasattr(eng, "xch"):
             raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
@@ -485,6 +493,8 @@ class Seq2SeqAttNN():
             if feed is None:
                 if spanel:       # a COLLECTIVE: a rank without sessions still joins every exchange (sharded.ShardExchange.serve)
                     eng.eval_step_streamed(None, k=20, panel=spanel, cap=_cap, T=T)
+                if sshort:       # ... and those of the two-stage call (sharded.ShardExchange.retrieve)
+                    eng.shard_recommend_two_stage(None, k=20, shortlist=sshort, exclude_seen=False, panel=spanel, cap=_cap, T=T)
                 continue
             bt = eng.upload(feed)
             if panel or spanel:  # streamed: no [B, N] score matrix; inside the sessions' pools (fresh), capped per category (cap)
@@ -504,7 +514,12 @@ class Seq2SeqAttNN():
             if ncand:            # the label among ncand - 1 sampled items: only those rows are scored (include/tcar_cand.h)
                 res = eng.score_candidates(None, *self._label_among_sampled(feed["label"], ncand, cand_rng), bt=bt)
                 cand_pending.append((res.counts.clone(), res.metrics.clone()))
-            if short:            # the two-stage lists of the same sessions (include/tcar_retrieve.h), beside the streamed ones
+            if sshort:           # the two-stage lists over the shards (include/tcar_retrieve_shard.h), beside the streamed ones
+                topk = topk.clone()          # (the sharded calls share the gathered-row workspace: keep the streamed lists)
+                two, _ = eng.shard_recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20,
+                                                       shortlist=sshort, exclude_seen=False, panel=spanel, window=window, cap=_cap)
+                short_pending.append((feed["label"], topk, two.clone()))
+            elif short:          # the two-stage lists of the same sessions (include/tcar_retrieve.h), beside the streamed ones
                 two, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
                                                  exclude_seen=False, panel=panel, window=window)
                 short_pending.append((feed["label"], topk.clone(), two.clone()))       # (topk: the streamed step's own buffer, untouched)
@@ -579,7 +594,8 @@ class Seq2SeqAttNN():
         With the catalog-sharded engine (dp_mode sharded) this is a COLLECTIVE: every rank calls it with its own sessions — None
         where it has none, with cap= and T= (sharded.ShardedEngine.recommend).
         shortlist = C (k <= C <= 1024): the two-stage form — C items retrieved from coarse scores, re-scored exactly, the k best of
-        them returned (engine.TcarEngine.recommend_two_stage); None: the streamed selection over exact scores, as ever."""
+        them returned (engine.TcarEngine.recommend_two_stage; the catalog-sharded engine: shard_recommend_two_stage, a collective
+        like its recommend); None: the streamed selection over exact scores, as ever."""
         if shortlist is not None and max_per_category is not None:
             raise ValueError("the two-stage recommendation takes no per-category cap (shortlist and max_per_category exclude each other)")
         sessions = self._feed(sessions)
@@ -588,25 +604,32 @@ class Seq2SeqAttNN():
         if max_per_category is not None:
             self._install_categories()
         if shortlist is not None:
-            return self.engine.recommend_two_stage(sessions, k=k, shortlist=shortlist, window=window, **kw)
+            two_stage = self.engine.shard_recommend_two_stage if self._sharded() else self.engine.recommend_two_stage
+            return two_stage(sessions, k=k, shortlist=shortlist, window=window, **kw)
         return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)
 
     def retrieve(self, sessions, C, window=None, **kw):      # noqa: N803
         """A shortlist of the C best next items (1 <= C <= 1024) of every session of `sessions` — a feed dict as `recommend` takes
         it — from coarse scores: (ids [B, C] int32, coarse_scores [B, C] f32) on the device, -1 / -inf where fewer than C items are
         eligible; a valid `candidates` of score_candidates (engine.TcarEngine.retrieve has the options).  window as in `recommend`.
-        Not with the catalog-sharded engine."""
+        With the catalog-sharded engine a COLLECTIVE, as `recommend` (sharded.ShardedEngine.shard_retrieve: cap= and T=)."""
         if window is not None:
             self._item_keys()
-        return self.engine.retrieve(self._feed(sessions), C, window=window, **kw)
+        call = self.engine.shard_retrieve if self._sharded() else self.engine.retrieve
+        return call(self._feed(sessions), C, window=window, **kw)
 
-    def score_candidates(self, sessions, candidates, clicked=None):
+    def _sharded(self) -> bool:
+        """is the engine the catalog-sharded one (its serving calls are collectives under names of their own)?"""
+        return hasattr(self.engine, "shard_retrieve")
+
+    def score_candidates(self, sessions, candidates, clicked=None, **kw):
         """Score and rank the items every session of `sessions` names — a feed dict as `recommend` takes it; candidates int [B, C],
         0-based ids, -1 = an empty slot — without touching the rest of the catalog: engine.CandResult(scores, rank_of, order, counts,
         metrics) on the device (engine.TcarEngine.score_candidates).  With clicked [B, C] (0 / 1) the counts and metrics of each
-        list are those of an impression: host.metrics.impression_metrics turns them into AUC / MRR / nDCG@5 / nDCG@10.  Not with
-        the catalog-sharded engine."""
-        return self.engine.score_candidates(self._feed(sessions), candidates, clicked)
+        list are those of an impression: host.metrics.impression_metrics turns them into AUC / MRR / nDCG@5 / nDCG@10.  With the
+        catalog-sharded engine a COLLECTIVE (sharded.ShardedEngine.shard_score_candidates: cap=, T= and, without sessions, C=)."""
+        call = self.engine.shard_score_candidates if self._sharded() else self.engine.score_candidates
+        return call(self._feed(sessions), candidates, clicked, **kw)
 
     @staticmethod
     def _feed(sessions):

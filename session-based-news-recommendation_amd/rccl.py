@@ -51,6 +51,9 @@ def _lib() -> C.CDLL:
         lib.ncclAllGather.argtypes = [vp, vp, sz, i32, vp, vp]
         lib.ncclReduceScatter.argtypes = [vp, vp, sz, i32, i32, vp, vp]
         lib.ncclAllReduce.argtypes = [vp, vp, sz, i32, i32, vp, vp]
+        if hasattr(lib, "ncclAllToAll"):          # (RCCL's own: the sharded retrieval falls back to all-gather + slice without it)
+            lib.ncclAllToAll.argtypes = [vp, vp, sz, i32, vp, vp]
+            lib.ncclAllToAll.restype = i32
         lib.ncclGetErrorString.argtypes = [i32]
         lib.ncclGetErrorString.restype = C.c_char_p
         for f in ("ncclGetUniqueId", "ncclCommInitRank", "ncclCommDestroy", "ncclAllGather", "ncclReduceScatter", "ncclAllReduce"):
@@ -113,6 +116,13 @@ class RcclComm:
         _ck(self._lib.ncclAllReduce(C.c_void_p(t.data_ptr()), C.c_void_p(t.data_ptr()), t.numel(), _DT[t.dtype], op, self.comm,
                                     self._st(stream)), "ncclAllReduce")
 
+    def all_to_all(self, send: torch.Tensor, recv: torch.Tensor, stream: Optional[int] = None):
+        """recv block r <- block `rank` of rank r's send; blocks of send.numel() / world elements; never in place"""
+        assert send.is_contiguous() and recv.is_contiguous() and send.numel() == recv.numel() and send.numel() % self.world == 0
+        assert send.dtype == recv.dtype and send.data_ptr() != recv.data_ptr()
+        _ck(self._lib.ncclAllToAll(C.c_void_p(send.data_ptr()), C.c_void_p(recv.data_ptr()), send.numel() // self.world, _DT[send.dtype],
+                                   self.comm, self._st(stream)), "ncclAllToAll")
+
     def destroy(self):
         if getattr(self, "comm", None) is not None and self.comm.value:
             self._lib.ncclCommDestroy(self.comm)
@@ -151,7 +161,9 @@ def make_direct(group=None, device=None, want: bool = True, verbose: bool = True
     if _agree(err is None, group, dev):
         try:
             comm = RcclComm(group, dev)
-            err = known_answers(comm, comm.world, comm.rank, dev)
+            caps = {}
+            err = known_answers(comm, comm.world, comm.rank, dev, caps)
+            comm.has_all_to_all = bool(caps.get("all_to_all"))
         except Exception as e:
             err = "%s: %s" % (type(e).__name__, e)
         if _agree(err is None, group, dev):

@@ -41,6 +41,21 @@ Evaluation: `eval_step` scores the local sessions against the whole catalog on t
 
 The merge is exact: top-k, scores and rank are the bits of the unsharded streamed call, the cross entropy differs by the rounding of a
 sum whose order is fixed.  No [., Npad] buffer exists on any rank.
+
+Retrieve-then-rank over the shards: `shard_retrieve` / `shard_recommend_two_stage` / `shard_score_candidates` (ShardExchange.retrieve /
+.candidates, include/tcar_retrieve_shard.h).  Collectives under names of their own — the single-engine names keep refusing:
+
+  all-gather   the packed session rows of the streamed selection; the label slot is the live marker (-1: a padding session)
+  fold         the shard's HI planes alone in column panels, global item ids -> one top-C state per gathered LIVE session
+  all-to-all   the states [W*cap, 2C + 4]: rank r receives rows [r cap, (r + 1) cap) of every shard's; tcar_retrieve_merge, finish
+  all-gather   the shortlists [cap, C]                                              (two-stage only)
+  gather       the exact score of every slot whose row this shard owns, -inf elsewhere
+  all-to-all   the parts [W*cap, C]; every slot takes its OWNER's bits (tcar_cand_combine), list order, the first k
+
+Both joins are exact: no float sum in the merge, a copy of the owner's word in the combine.  The all-to-all moves a W-th of what an
+all-gather would (W = 8, cap = 512, C = 1,024: 8.4 MB into every rank instead of 67 MB).  Which path it took — RCCL's ncclAllToAll on the
+step's stream, all_to_all_single of a process group, or all-gather + slice where a backend has neither (the documented fallback, not a
+failure) — is `exchange_info()["all_to_all"]`.
 """
 from __future__ import annotations
 
@@ -52,7 +67,7 @@ import torch
 
 from . import _lib, dp
 from ._lib import Batch, Dims, check
-from .engine import Switches, TcarEngine, _ru
+from .engine import CandResult, Switches, TcarEngine, _ru
 from .workspace import BF16, F32, I32, ScoreForm, Spec, scoring_specs
 
 
@@ -126,6 +141,52 @@ class ShardExchange(dp.Collectives):
             pieces.label_scores(self.all_gather(parts, "serve_label_scores"))
         state = pieces.fold()
         return pieces.finish(self.all_gather(state, "serve_states"))
+
+    def retrieve(self, pieces, cap: int, rerank: bool):
+        """one retrieval (a shortlist of C items from coarse scores) or, with `rerank`, one two-stage recommendation
+        (include/tcar_retrieve_shard.h): every rank folds ITS shard into a top-C state per session of EVERY rank, the states merge
+        exactly; then every rank scores the shortlist slots whose rows it owns and the owners' bits combine.  A rank needs only its
+        own sessions' slice of every shard's result, so results travel by all-to-all (Collectives.all_to_all_rows), a W-th of an
+        all-gather.  Every rank, also one without sessions, issues the same collectives in the same order with buffers of the same shape:
+
+          1 all-gather  serve_rows: the packed session rows of `serve` [cap, ld]; the label slot carries the live marker (-1: padding)
+          2 all-to-all  retrieve_states [W * cap, 2C + 4] -> [W, cap, 2C + 4]; tcar_retrieve_merge, tcar_retrieve_finish
+          3 all-gather  retrieve_shortlists int32 [cap, C]                            (rerank only)
+          4 all-to-all  cand_parts fp32 [W * cap, C] -> [W, cap, C]; tcar_cand_combine, tcar_cand_rank, tcar_rerank_take   (rerank only)
+
+        `pieces` supplies the local compute:
+             begin() -> rows [cap, ld]          prepare(rows_all [W*cap, ld])          fold() -> state [W*cap, 2C+4]
+             merge(states [W, cap, 2C+4]) -> shortlist ids [cap, C]                   shortlist() -> the result of a retrieval
+             scores(lists [W*cap, C]) -> parts [W*cap, C]                             rerank(parts [W, cap, C]) -> the two-stage result"""
+        self.order = []
+        self.wait_rows()
+        head = pieces.begin()
+        head_all = self.all_gather(head, "serve_rows").view(self.world * cap, -1)
+        pieces.prepare(head_all)
+        state = pieces.fold()
+        ids = pieces.merge(self.all_to_all_rows(state, cap, "retrieve_states"))
+        if not rerank:
+            return pieces.shortlist()
+        lists = self.all_gather(ids, "retrieve_shortlists").view(self.world * cap, -1)
+        part = pieces.scores(lists)
+        return pieces.rerank(self.all_to_all_rows(part, cap, "cand_parts"))
+
+    def candidates(self, pieces, cap: int):
+        """one candidate-scoring step: every session names C items, every rank scores the slots whose rows it owns for the sessions of
+        EVERY rank, and each session's list takes every slot from its owner.  The same collectives on every rank:
+
+          1 all-gather  serve_rows (no exclusions, no window)
+          2 all-gather  cand_lists int32 [cap, C]
+          3 all-to-all  cand_parts fp32 [W * cap, C] -> [W, cap, C]; tcar_cand_combine, tcar_cand_rank (with `clicked`)
+
+        `pieces`: begin(), prepare(rows_all), lists() -> [cap, C], scores(lists [W*cap, C]) -> parts, rank(parts [W, cap, C]) -> result"""
+        self.order = []
+        self.wait_rows()
+        head = pieces.begin()
+        pieces.prepare(self.all_gather(head, "serve_rows").view(self.world * cap, -1))
+        lists = self.all_gather(pieces.lists(), "cand_lists").view(self.world * cap, -1)
+        part = pieces.scores(lists)
+        return pieces.rank(self.all_to_all_rows(part, cap, "cand_parts"))
 
 
 class _Pieces:
@@ -307,6 +368,102 @@ class _ServePieces:
         return e.sel_rank[:B], e.sel_topk[:B], e.sel_ce[:B], e.sel_score[:B]
 
 
+class _OwnedScores(_ServePieces):
+    """What the pieces of ShardExchange.retrieve and .candidates share on top of begin / prepare of `_ServePieces` (unlabelled: the
+    label slot of a packed row is the live marker): the shard's exact scores of the slots it owns, and the combine of the parts."""
+
+    # lists [W*cap, C] GLOBAL ids of the sessions of every rank -> parts [W*cap, C]: the owner's exact score, -inf elsewhere
+    def scores(self, lists):
+        e, C_ = self.eng, self.C
+        if not lists.is_contiguous():
+            lists = lists.contiguous()
+        self._lists = lists
+        check(e.lib.tcar_shard_cand_scores(C.byref(self.sctx), C.byref(self.sh), C_, e._p(lists), C_, e._p(e.rs_part), C_, self.st),
+              "tcar_shard_cand_scores")
+        return e.rs_part[:self.Bq]
+
+    # parts [W, cap, C] of the local sessions' lists `cand` [cap, C] -> out [cap, C]: every slot takes its owner's bits
+    def _combine(self, parts, cand, out):
+        e, cap, C_ = self.eng, self.cap, self.C
+        if not parts.is_contiguous():
+            parts = parts.contiguous()
+        self._parts = parts
+        check(e.lib.tcar_cand_combine(cap, C_, parts.shape[0], e.S, e.geo.N, e._p(cand), C_, e._p(parts), cap * C_, e._p(out), C_,
+                                      self.st), "tcar_cand_combine")
+
+
+class _RetrievePieces(_OwnedScores):
+    """The local compute between the exchanges of ShardExchange.retrieve, bound to the C entry points of
+    include/tcar_retrieve_shard.h.  ONE object per engine, re-armed per call; each piece can be called on its own."""
+
+    def arm(self, bt, cap, C_, k, panel, meta, X, windowed):
+        super().arm(bt, cap, k or 1, panel, False, meta, X, windowed, None)
+        self.C, self.k, self.rw = C_, k, 2 * C_ + 4
+
+    # the shard's rows, panel by panel in the coarse precision, into one top-C state per session of every rank; padding sessions
+    # (label slot -1) cost nothing
+    def fold(self):
+        e, Bq = self.eng, self.Bq
+        d = _lib.Retrieve()
+        d.C, d.panel, d.panel_buf = self.C, self.panel, e.sv_panel.data_ptr()
+        d.state, d.state_bytes = e.rs_state.data_ptr(), e.rs_state.numel() * 4
+        if self.X:
+            d.excl, d.X = e.sv_excl.data_ptr(), self.X
+        w = e._window_desc(e._item_keys, e.sv_lohi) if self.windowed else None
+        if w is not None:
+            d.window = C.addressof(w)                # (w stays alive until the call has returned)
+        check(e.lib.tcar_shard_retrieve_fold(C.byref(self.sctx), C.byref(self.sh), C.byref(d), e._p(e.sv_lab), self.st),
+              "tcar_shard_retrieve_fold")
+        return e.rs_state[:Bq]
+
+    # the W states of the local sessions' rows -> one (tcar_retrieve_merge), finished: the shortlist [cap, C]
+    def merge(self, states):
+        e, cap, C_ = self.eng, self.cap, self.C
+        if not states.is_contiguous():
+            states = states.contiguous()
+        self._states = states
+        check(e.lib.tcar_retrieve_merge(cap, C_, states.shape[0], e._p(states), cap * self.rw, e._p(e.rs_merged), self.st),
+              "tcar_retrieve_merge")
+        check(e.lib.tcar_retrieve_finish(cap, C_, e._p(e.rs_merged), e._p(e.rs_ids), e._p(e.rs_scores), self.st), "tcar_retrieve_finish")
+        return e.rs_ids[:cap]
+
+    def shortlist(self):
+        e = self.eng
+        return e.rs_ids[:self.B], e.rs_scores[:self.B]
+
+    # the exact scores of the shortlist from their owners, its list order, the first k of it
+    def rerank(self, parts):
+        e, cap, C_, k = self.eng, self.cap, self.C, self.k
+        self._combine(parts, e.rs_ids, e.rs_exact)
+        check(e.lib.tcar_cand_rank(cap, C_, e._p(e.rs_exact), C_, e._p(e.rs_ids), C_, None, 0, e._p(e.rs_rank[0]), e._p(e.rs_rank[1]),
+                                   None, None, self.st), "tcar_cand_rank")
+        check(e.lib.tcar_rerank_take(cap, C_, k, e._p(e.rs_ids), e._p(e.rs_exact), e._p(e.rs_rank[1]), e._p(e.rs_topk),
+                                     e._p(e.rs_topscore), self.st), "tcar_rerank_take")
+        return e.rs_topk[:self.B], e.rs_topscore[:self.B]
+
+
+class _CandPieces(_OwnedScores):
+    """The local compute between the exchanges of ShardExchange.candidates.  ONE object per engine, re-armed per call."""
+
+    def arm(self, bt, cap, C_, meta, clicked):
+        super().arm(bt, cap, 1, 128, False, meta, 0, False, None)
+        self.C, self.clicked = C_, clicked
+
+    # the local sessions' lists [cap, C]: -1 (empty slots) in the rows past the local batch
+    def lists(self):
+        return self.eng.cs_in[0, :self.cap]
+
+    def rank(self, parts):
+        e, cap, C_, B, clk = self.eng, self.cap, self.C, self.B, self.clicked
+        cand = e.cs_in[0]
+        self._combine(parts, cand, e.cs_score)
+        check(e.lib.tcar_cand_rank(cap, C_, e._p(e.cs_score), C_, e._p(cand), C_, e._p(e.cs_in[1]) if clk else None, C_ if clk else 0,
+                                   e._p(e.cs_rank[0]), e._p(e.cs_rank[1]), e._p(e.cs_counts) if clk else None,
+                                   e._p(e.cs_metrics) if clk else None, self.st), "tcar_cand_rank")
+        return CandResult(e.cs_score[:B], e.cs_rank[0, :B], e.cs_rank[1, :B], e.cs_counts[:B] if clk else None,
+                          e.cs_metrics[:B] if clk else None)
+
+
 class ShardedEngine(TcarEngine):
     def __init__(self, params, content_emb, mwdhm, lr=1e-3, max_grad=150.0, neg_weight=0.01, device="cuda:0", group=None,
                  scoring="bf16x3", world: Optional[int] = None, rank: Optional[int] = None,
@@ -352,6 +509,8 @@ class ShardedEngine(TcarEngine):
 
     # ------------------------------------------------------------------------------------------ collectives
     close = dp.DPEngine.close          # synchronise, then destroy the direct RCCL communicator (idempotent)
+    RETRIEVE_COLLECTIVES = ("serve_rows", "retrieve_states", "retrieve_shortlists", "cand_parts")
+    CAND_COLLECTIVES = ("serve_rows", "cand_lists", "cand_parts")
 
     def exchange_info(self) -> Dict[str, object]:
         g = self.geo
@@ -366,6 +525,13 @@ class ShardedEngine(TcarEngine):
                 "collectives_per_step": 6,
                 "serve_collectives": ("serve_rows", "serve_label_scores", "serve_states"),        # ShardExchange.serve (labelled: all three)
                 "serve_bytes": {n: self.bytes_moved.get(n, 0) for n in ("serve_rows", "serve_label_scores", "serve_states")},
+                # ShardExchange.retrieve (a retrieval alone: the first two) and .candidates; bytes per rank SENT of an all-to-all
+                "retrieve_collectives": self.RETRIEVE_COLLECTIVES, "cand_collectives": self.CAND_COLLECTIVES,
+                "retrieve_bytes": {n: self.bytes_moved.get(n, 0) for n in self.RETRIEVE_COLLECTIVES},
+                "cand_bytes": {n: self.bytes_moved.get(n, 0) for n in self.CAND_COLLECTIVES},
+                # how all_to_all_rows ran: "all-to-all (RCCL C API)", "all-to-all (<backend>)", or, on a backend without one (the
+                # documented fallback, not a failure), "all-gather + slice (<backend>)"; "none" until the first exchange
+                "all_to_all": self.xch.all_to_all_path,
                 "note": "all-gather [attout | label | negatives | coefficient] rows, all-gather softmax stats, reduce-scatter dX, "
                         "all-gather [row | id] item-row gradients, all-reduce arena, all-gather updated item rows; the dense item "
                         "gradient and the candidate-time block stay local"}
@@ -641,11 +807,29 @@ class ShardedEngine(TcarEngine):
         cap are needed): eval_step_streamed (labelled) and recommend hand them to the exchange; a caller that moves the buffers
         itself calls begin / prepare / label_scores / fold / finish in that order.  No buffer of the catalog's width is touched:
         every rank scores its shard's rows only."""
-        g = self.geo
+        self._refuse_ragged_shard(batch, bt)
+        k, panel, quota = self._serve_request(k, panel, window, max_per_category, _ru(self.nl, 128))
+        bt, cap, X, meta = self._gathered_inputs(batch, bt, labelled, exclude_seen, exclude, window, cap, T, panel)
+        self.ws.ensure([Spec("sv_state", (self.world * cap, 2 * k + 4), I32), Spec("sv_merged", (cap, 2 * k + 4), I32),
+                        Spec("sel_score", (cap, k), F32), Spec("sel_topk", (cap, k), I32), Spec("sel_rank", (cap,), I32),
+                        Spec("sel_ce", (cap,), F32)])
+        pc = getattr(self, "_serve_pc", None)
+        if pc is None:
+            pc = self._serve_pc = _ServePieces(self)
+        pc.arm(bt, cap, k, panel, labelled, meta, X, window is not None, quota)
+        return pc
+
+    def _refuse_ragged_shard(self, batch, bt=None) -> None:
         if self.is_ragged(batch) or getattr(bt, "_rg", None) is not None:      # (the sharded session forward is rectangular)
             raise ValueError("the catalog-sharded engine takes rectangular feeds: ragged batches (sessions of mixed lengths) are for "
                              "the single-engine serving calls")
-        k, panel, quota = self._serve_request(k, panel, window, max_per_category, _ru(self.nl, 128))
+
+    def _gathered_inputs(self, batch, bt, labelled: bool, exclude_seen: bool, exclude, window, cap, T, panel: int):
+        """What every serving collective of this engine prepares behind its request checks: the uploaded local sessions (`batch` /
+        `bt`; both None: none — then T and cap are needed), the rows every rank contributes, the width X of the exclusion lists every
+        rank packs, the workspace of begin / prepare (`_ServePieces`) and the ints that ride behind attout, one row per local
+        session -> (bt, cap, X, meta)."""
+        g = self.geo
         self.flush()
         excl = None
         if labelled:
@@ -668,16 +852,13 @@ class ShardedEngine(TcarEngine):
         cap = max(cap or 0, B, 1)
         self._ensure_work(max(B, 1), T)
         X = int(excl.shape[1]) if excl is not None else 0
-        Bq, K, rw = self.world * cap, 2 + X, 2 * k + 4
+        Bq, K = self.world * cap, 2 + X
         ld = _ru(g.ek + 2 + K, 4)
         rp = _ru(Bq, 128)
         self.ws.ensure([Spec("sv_head", (cap, ld), F32, 0), Spec("sv_lab", (Bq,), I32, -1), Spec("sv_coef", (Bq,), F32, 0),
                         Spec("sv_meta", (Bq, K), I32, -1), Spec("sv_lohi", (2, Bq), I32, 0), Spec("sv_excl", (Bq, max(X, 1)), I32, -1),
                         Spec("sv_a16h", (rp, g.ek), BF16, 0), Spec("sv_a16l", (rp, g.ek), BF16, 0),
-                        Spec("sv_lab_part", (Bq,), F32, 0), Spec("sv_lab_score", (Bq,), F32, 0),
-                        Spec("sv_panel", (Bq, panel), F32), Spec("sv_state", (Bq, rw), I32), Spec("sv_merged", (cap, rw), I32),
-                        Spec("sel_score", (cap, k), F32), Spec("sel_topk", (cap, k), I32), Spec("sel_rank", (cap,), I32),
-                        Spec("sel_ce", (cap,), F32)])
+                        Spec("sv_lab_part", (Bq,), F32, 0), Spec("sv_lab_score", (Bq,), F32, 0), Spec("sv_panel", (Bq, panel), F32)])
         meta = None
         if B:
             # the ints that ride behind attout: [lo | hi | exclusion ids], one row per local session
@@ -687,11 +868,7 @@ class ShardedEngine(TcarEngine):
             else:
                 lohi = torch.zeros(B, 2, dtype=torch.int32, device=self.dev)
             meta = torch.cat([lohi, excl], dim=1).contiguous() if X else lohi
-        pc = getattr(self, "_serve_pc", None)
-        if pc is None:
-            pc = self._serve_pc = _ServePieces(self)
-        pc.arm(bt, cap, k, panel, labelled, meta, X, window is not None, quota)
-        return pc
+        return bt, cap, X, meta
 
     def _exchange(self, pc: _ServePieces):
         out = self.xch.serve(pc, pc.cap, pc.labelled)
@@ -736,6 +913,91 @@ class ShardedEngine(TcarEngine):
         """not on the catalog-sharded engine: its first stage is retrieve(), its second score_candidates()"""
         raise _lib.TcarError("recommend_two_stage() needs the whole catalog on one engine (no shard): the catalog-sharded engine "
                              "has neither retrieve() nor score_candidates()")
+
+    # ---- retrieval, candidate scoring and the two-stage call over the shards (include/tcar_retrieve_shard.h; the collectives:
+    # ShardExchange.retrieve / .candidates).  New names: they are COLLECTIVES with cap / T arguments, which the single-engine calls of
+    # the same purpose (refused above) do not have.
+    def retrieve_pieces(self, batch, C, k: Optional[int] = None, exclude_seen: bool = True, exclude=None,      # noqa: N803
+                        panel: Optional[int] = None, window=None, cap: Optional[int] = None, T: Optional[int] = None) -> _RetrievePieces:
+        """The armed local pieces of ONE ShardExchange.retrieve for this rank's sessions (`batch` None: none — then T and cap are
+        needed); k None: a retrieval, else the two-stage call.  A caller that moves the buffers itself calls begin / prepare / fold /
+        merge (/ scores / rerank) in that order.  The request is validated before any upload (TcarEngine._retrieve_request, the
+        shard's padded rows as the panel bound).  No buffer of the catalog's width is touched."""
+        self._refuse_ragged_shard(batch)
+        panel = self._retrieve_request(C, k, panel, window, _ru(self.nl, 128))
+        C_, k = int(C), (int(k) if k is not None else None)
+        bt, cap, X, meta = self._gathered_inputs(batch, None, False, exclude_seen, exclude, window, cap, T, panel)
+        Bq, rw = self.world * cap, 2 * C_ + 4
+        self.ws.ensure([Spec("rs_state", (Bq, rw), I32), Spec("rs_merged", (cap, rw), I32), Spec("rs_ids", (cap, C_), I32),
+                        Spec("rs_scores", (cap, C_), F32)])
+        if k is not None:
+            self.ws.ensure([Spec("rs_part", (Bq, C_), F32), Spec("rs_exact", (cap, C_), F32), Spec("rs_rank", (2, cap, C_), I32),
+                            Spec("rs_topk", (cap, k), I32), Spec("rs_topscore", (cap, k), F32)])
+        pc = getattr(self, "_retrieve_pc", None)
+        if pc is None:
+            pc = self._retrieve_pc = _RetrievePieces(self)
+        pc.arm(bt, cap, C_, k, panel, meta, X, window is not None)
+        return pc
+
+    def cand_pieces(self, batch, candidates, clicked=None, cap: Optional[int] = None, T: Optional[int] = None,
+                    C: Optional[int] = None) -> _CandPieces:      # noqa: N803
+        """The armed local pieces of ONE ShardExchange.candidates (`batch` None: a rank without sessions — then T, cap and the list
+        length C are needed).  The request is validated before any upload (TcarEngine._cand_request)."""
+        self._refuse_ragged_shard(batch)
+        if batch is not None:
+            cand, clk = self._cand_request(self._sessions(batch), candidates, clicked)
+            C_ = cand.shape[1]
+        else:
+            if isinstance(C, bool) or not isinstance(C, (int, np.integer)) or not 1 <= C <= self.CAND_MAX_C:
+                raise ValueError("a rank without sessions needs the step's list length: C must be in [1, %d]" % self.CAND_MAX_C)
+            cand, clk, C_ = None, None, int(C)
+        bt, cap, _, meta = self._gathered_inputs(batch, None, False, False, None, None, cap, T, 128)
+        self.ws.ensure([Spec("cs_in", (2, cap, C_), I32), Spec("rs_part", (self.world * cap, C_), F32), Spec("cs_score", (cap, C_), F32),
+                        Spec("cs_rank", (2, cap, C_), I32), Spec("cs_counts", (cap, 3), I32), Spec("cs_metrics", (cap, 3), F32)])
+        # cand and clicked are the two planes of ONE workspace entry: they go up in one copy; rows past the local batch: empty slots
+        self.cs_in[0].fill_(-1)
+        if cand is not None:
+            if clk is None:
+                self.cs_in[0, :cand.shape[0]].copy_(torch.from_numpy(cand))
+            else:
+                self.cs_in[:, :cand.shape[0]].copy_(torch.from_numpy(np.stack([cand, clk])))
+        pc = getattr(self, "_cand_pc", None)
+        if pc is None:
+            pc = self._cand_pc = _CandPieces(self)
+        pc.arm(bt, cap, C_, meta, clk is not None)
+        return pc
+
+    def shard_retrieve(self, batch, C, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None, window=None,      # noqa: N803
+                       cap: Optional[int] = None, T: Optional[int] = None):
+        """TcarEngine.retrieve over the shards: (ids [B, C] int32, coarse_scores [B, C] f32) of this rank's sessions against the
+        whole catalog — every shard's top-C state of the hi-plane scores, merged exactly (tcar_retrieve_merge).  A COLLECTIVE, as
+        eval_step_streamed: `batch` = None on a rank without sessions, with T and cap; every rank passes exclusion lists of the same
+        width.  Views of the workspace, valid until the next call."""
+        pc = self.retrieve_pieces(batch, C, None, exclude_seen, exclude, panel, window, cap, T)
+        out = self.xch.retrieve(pc, pc.cap, False)
+        self.poll_fork_errors()
+        return out
+
+    def shard_recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
+                                  panel: Optional[int] = None, window=None, cap: Optional[int] = None, T: Optional[int] = None):
+        """TcarEngine.recommend_two_stage over the shards: (topk [B, k] int32, scores [B, k] f32), the k best of the shortlist's exact
+        scores, each slot scored by the shard that owns its row (the bits a whole-catalog engine computes from the same operands).
+        A COLLECTIVE, as shard_retrieve.  `last_shortlist` / `last_exact` hold the shortlist [B, shortlist] and its exact scores."""
+        pc = self.retrieve_pieces(batch, shortlist, k, exclude_seen, exclude, panel, window, cap, T)
+        out = self.xch.retrieve(pc, pc.cap, True)
+        self.poll_fork_errors()
+        self.last_shortlist, self.last_exact = self.rs_ids[:pc.B], self.rs_exact[:pc.B]
+        return out
+
+    def shard_score_candidates(self, batch, candidates, clicked=None, cap: Optional[int] = None, T: Optional[int] = None,
+                               C: Optional[int] = None) -> CandResult:      # noqa: N803
+        """TcarEngine.score_candidates over the shards: CandResult of this rank's sessions; every slot is scored by the shard that
+        owns its row.  A COLLECTIVE: `batch` = None on a rank without sessions, with T, cap and the list length C; every rank passes
+        lists of the same length."""
+        pc = self.cand_pieces(batch, candidates, clicked, cap, T, C)
+        out = self.xch.candidates(pc, pc.cap)
+        self.poll_fork_errors()
+        return out
 
     # ------------------------------------------------------------------------------ inspection (tests, export)
     def _item_rows_full(self, local: torch.Tensor) -> np.ndarray:

@@ -36,6 +36,16 @@ streamed list found in the two-stage list, and the share of sessions whose lists
 events around one fold of the panel the last step left in the panel buffer into a fresh state, tcar_select_panel at K beside
 tcar_retrieve_panel at C.
 
+       python tools/eval_bench.py [iters] [--n_items N] --retrieve C[,C...] --sharded W [--k K] [--panel P] [--rounds R]
+
+--retrieve C --sharded W: the catalog-sharded engine at the shapes of rank 0 of a W-rank job (the sim world of --streamed --sharded W:
+the collectives' own time is not in the numbers, and the W "shards" a rank merges are copies of its own).  Per rank and round, on the
+same host batches: ShardedEngine.recommend (the streamed selection over the shard's exact scores, merged) beside shard_retrieve and
+shard_recommend_two_stage at every C, and their ratios.  Then the pieces of the two-stage call alone, device events around each on
+the buffers the last call left: the shard's fold, tcar_retrieve_merge, the owners' gather (tcar_shard_cand_scores), tcar_cand_combine,
+and ONE tcar_retrieve_panel launch over the engine's panel buffer for B sessions; and the fold with 300 of cap = 512 rows live beside
+512 live (a padding session must cost nothing: include/tcar_retrieve_shard.h, tcar_retrieve_panel_live).
+
        python tools/eval_bench.py [iters] [--n_items N] --ragged LMAX [--k K] [--panel P] [--rounds R]
 
 --ragged LMAX: B = 512 sessions whose lengths are drawn uniformly from 1 .. LMAX (fixed seed).  TcarEngine.recommend once per length
@@ -74,8 +84,9 @@ N, B, iters = a.n_items, 512, a.iters
 fold = SynthFold(n_items=N, dim=250, n_train=60000, n_test=1000, seed=2020, **(dict(lean=True) if N > 200000 else {}))
 np.random.seed(2020)
 if a.sharded:
-    if not a.streamed:
-        sys.exit("--sharded W compares the two evaluation steps of the catalog-sharded engine: it needs --streamed")
+    if not a.streamed and not a.retrieve:
+        sys.exit("--sharded W compares the two evaluation steps of the catalog-sharded engine (--streamed) or its two recommendation "
+                 "calls (--retrieve C): it needs one of them")
     if a.sharded > 1:
         os.environ["TCAR_SIM_WORLD"] = str(a.sharded)
     from tcar_amd.sharded import ShardedEngine
@@ -142,10 +153,80 @@ if cands:
         sys.stdout.flush()
     sys.exit(0)
 shorts = [int(c) for c in a.retrieve.split(",") if c]
+if shorts and a.sharded:
+    import ctypes as C_
+    P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
+    K, W, g = a.k, eng.world, eng.geo
+    feeds = [{n: v for n, v in b.items() if n not in ("label", "neg")} for b in batches]
+    vp = lambda t, off=0: C_.c_void_p(t.data_ptr() + 4 * off)
+
+    def timed_host(step):
+        for i in range(5):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    def events(fn):
+        """ms per call of fn on the step's stream: device events around `iters` calls behind 5 warm ones"""
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters
+
+    def pieces_alone(c):
+        """the pieces of ONE shard_recommend_two_stage on the buffers the call left on the engine"""
+        eng.shard_recommend_two_stage(feeds[0], k=K, shortlist=c, panel=P)
+        pc, lib, st = eng._retrieve_pc, eng.lib, eng._stream()
+        cap, rw = pc.cap, 2 * c + 4
+        states, parts, lists = pc._states, pc._parts, pc._lists
+        fold = events(pc.fold)
+        merge = events(lambda: lib.tcar_retrieve_merge(cap, c, W, vp(states), cap * rw, vp(eng.rs_merged), st))
+        gather = events(lambda: pc.scores(lists))
+        comb = events(lambda: lib.tcar_cand_combine(cap, c, W, eng.S, g.N, vp(eng.rs_ids), c, vp(parts), cap * c, vp(eng.rs_exact), c, st))
+        width = eng.sv_panel.shape[1]
+        n = min(width, eng.nl)
+
+        def one_panel():
+            lib.tcar_retrieve_reset(cap, c, vp(eng.rs_state), st)
+            lib.tcar_retrieve_panel(cap, 0, n, vp(eng.sv_panel), width, c, None, 0, None, None, None, vp(eng.rs_state), st)
+        panel = events(one_panel)
+        return fold, merge, gather, comb, panel, n
+
+    def fold_live(c, live):
+        """ms of the shard's fold alone with `live` of cap = B rows of every rank live (the others padding sessions)"""
+        f = {n_: v[:live] for n_, v in feeds[0].items()}
+        pc = eng.retrieve_pieces(f, c, K, panel=P, cap=B)
+        pc.prepare(eng.xch.all_gather(pc.begin()).view(W * B, -1))
+        return events(pc.fold)
+
+    print("N=%d sharded W=%d: shard of %d rows, %d gathered sessions per step, k=%d" % (N, W, eng.nl, W * B, K))
+    for rnd in range(a.rounds):
+        dt = timed_host(lambda f: eng.recommend(f, k=K, panel=P))
+        print("N=%d W=%d round %d sharded recommend k=%d: %.3f ms = %.0f sessions/s" % (N, W, rnd, K, dt * 1e3, B / dt))
+        for c in shorts:
+            dr = timed_host(lambda f: eng.shard_retrieve(f, c, panel=P))
+            d2 = timed_host(lambda f: eng.shard_recommend_two_stage(f, k=K, shortlist=c, panel=P))
+            print("N=%d W=%d round %d C=%d: shard_retrieve %.3f ms (%.3f of recommend), shard_recommend_two_stage %.3f ms (%.3f of recommend)"
+                  % (N, W, rnd, c, dr * 1e3, dr / dt, d2 * 1e3, d2 / dt))
+        sys.stdout.flush()
+    for c in shorts:
+        fold, merge, gather, comb, panel, n = pieces_alone(c)
+        print("N=%d W=%d C=%d pieces alone: fold of the shard %.3f ms, merge of %d states x %d sessions %.4f ms, owners' gather %.4f ms, "
+              "combine %.4f ms; one tcar_retrieve_panel of %d columns x %d sessions %.4f ms" % (N, W, c, fold, W, B, merge, gather, comb, n, B, panel))
+        f512, f300 = fold_live(c, B), fold_live(c, 300)
+        print("N=%d W=%d C=%d fold with cap=%d: %d live %.3f ms, 300 live %.3f ms (%.3f)" % (N, W, c, B, B, f512, f300, f300 / f512))
+        sys.stdout.flush()
+    sys.exit(0)
 if shorts:
     import ctypes as C_
-    if a.sharded:
-        sys.exit("--retrieve needs the whole catalog on one engine: not with --sharded")
     P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
     K = a.k
     feeds = [{n: v for n, v in b.items() if n not in ("label", "neg")} for b in batches]
