@@ -38,20 +38,8 @@ __device__ __forceinline__ const EmbRagged& emb_ragged(const EmbRagged& r) { ret
 __device__ __forceinline__ EmbRagged emb_ragged() { return EmbRagged{0, nullptr}; }
 
 
-__device__ __forceinline__ int time_vocab(int k) {
-  return k == 0 ? 13 : k == 1 ? 32 : k == 2 ? 8 : k == 3 ? 25 : k == 4 ? 61 : TCAR_DUR_VOCAB;
-}
-// row offset of table k inside the contiguous [month|day|week|hour|minute|dur] block
-__device__ __forceinline__ int time_rowoff(int k) {
-  return k == 0 ? 0 : k == 1 ? 13 : k == 2 ? 45 : k == 3 ? 53 : k == 4 ? 78 : 139;
-}
+// (time_vocab, time_rowoff, pick5 and clip_time_piece: tcar_common.h — catalog.hip clips the rows a catalog row names with them)
 constexpr int SMALL_ROWS = 150;  // 13+32+8+25+61+11
-
-// select one of five kernel-argument pointers without a runtime-indexed (scratch) copy of the argument struct
-template <typename P>
-__device__ __forceinline__ P pick5(P const (&arr)[5], int k) {
-  return k == 0 ? arr[0] : k == 1 ? arr[1] : k == 2 ? arr[2] : k == 3 ? arr[3] : arr[4];
-}
 
 // ------------------------------------------------------------------------------------------------ forward
 // RAGGED: the rows of sessions of mixed lengths, R in all — the position row of a row is rpos[row] (clamped into the 40-row table) in
@@ -506,8 +494,8 @@ __global__ __launch_bounds__(256) void cand_time_fwd_kernel(const CandArgs a) {
     const int k = rr < 13 ? 0 : rr < 45 ? 1 : rr < 53 ? 2 : rr < 78 ? 3 : 4;
     const int id = rr - time_rowoff(k);
     float4 x = valid ? ld4(pick5(a.tab, k) + (long)id * ldt + lin * 4) : zero4();
-    const float s = clip_scale(group_sum(dot4(x, x), sub));
-    if (valid) st4(lds + rr * ldt + lin * 4, scale4(x, s));
+    const float4 y = clip_time_piece(x, sub);
+    if (valid) st4(lds + rr * ldt + lin * 4, y);
   }
   __syncthreads();
   // One 128-row block of E per workgroup pass; thread = (row, 16-column half of a 32-wide k-block).  In the KB32 planes

@@ -352,3 +352,24 @@ __device__ __forceinline__ void clip_bwd_coef(float ss, float d, float& a, float
   }
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- the five publish-time tables (month | day | week | hour | minute, then the dwell table) as every kernel addresses them
+__device__ __forceinline__ int time_vocab(int k) {
+  return k == 0 ? 13 : k == 1 ? 32 : k == 2 ? 8 : k == 3 ? 25 : k == 4 ? 61 : TCAR_DUR_VOCAB;
+}
+// row offset of table k inside the contiguous [month|day|week|hour|minute|dur] block
+__device__ __forceinline__ int time_rowoff(int k) {
+  return k == 0 ? 0 : k == 1 ? 13 : k == 2 ? 45 : k == 3 ? 53 : k == 4 ? 78 : 139;
+}
+// select one of five kernel-argument pointers without a runtime-indexed (scratch) copy of the argument struct
+template <typename P>
+__device__ __forceinline__ P pick5(P const (&arr)[5], int k) {
+  return k == 0 ? arr[0] : k == 1 ? arr[1] : k == 2 ? arr[2] : k == 3 ? arr[3] : arr[4];
+}
+// The clipped form of a time-table row as the CANDIDATE side holds it: an aligned group of `sub` = ldt / 4 lanes owns the row, lane
+// `lin` of the group its columns [4 lin, 4 lin + 4).  ONE reduction order — dot4, then the xor butterfly of group_sum over the group,
+// then clip_scale — for the whole-catalog refresh (embed.hip: cand_time_fwd_kernel) and the row update (catalog.hip), whose time
+// blocks must agree bit for bit.  Every lane of the group calls it (lanes of a group without a row pass zeros).
+__device__ __forceinline__ float4 clip_time_piece(const float4 x, int sub) {
+  return scale4(x, clip_scale(group_sum(dot4(x, x), sub)));
+}

@@ -395,6 +395,10 @@ class DPEngine(TcarEngine):
         torch.cuda.synchronize(self.dev)
         self.xch.close()
 
+    def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
+        """not on a replica: every rank holds the whole catalog, and nothing makes the ranks agree on an update"""
+        raise _lib.TcarError("update_items() is not for the data-parallel replicas: the ranks would have to agree on the update")
+
     def _ensure_rows(self, rows: int):
         if rows > self.rows_cap:
             self.rows_buf = torch.zeros(rows, self.geo.ldh, dtype=torch.float32, device=self.dev)

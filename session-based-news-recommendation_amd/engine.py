@@ -248,23 +248,12 @@ class TcarEngine(OpLevelStep):
         for n in TABLE_VARS:
             use[SLOT[n]] = 0
         self.use_dense = torch.tensor(use, device=self.dev)
-        self.mwdhm = torch.tensor(np.ascontiguousarray(np.asarray(mwdhm)[n0:n0 + nl], dtype=np.int32), device=self.dev)
+        # (a host copy of its own: update_items writes it, and the index below is rebuilt from it)
+        self._mwdhm_host = np.array(np.asarray(mwdhm)[n0:n0 + nl], dtype=np.int32, order="C")
+        self.mwdhm = torch.tensor(self._mwdhm_host, device=self.dev)
         self.dims = Dims(g.N, g.H, g.Ht, g.ldh, g.ldt)
         self.dims_cand = Dims(nl, g.H, g.Ht, g.ldh, g.ldt)        # the candidate-side kernels see the shard as a catalog
-        # static inverted index of publish_time_MWDHM: candidates listed per time-table row (cand_time_bwd_indexed)
-        mw = np.ascontiguousarray(np.asarray(mwdhm)[n0:n0 + nl], dtype=np.int64)
-        rowoff = np.array([0, 13, 45, 53, 78])
-        key = (np.clip(mw, 0, np.array(TIME_VOCAB) - 1) + rowoff[None, :]).T.reshape(-1)          # [5N], k-major
-        order = np.argsort(key, kind="stable")
-        inv_off = np.zeros(140, dtype=np.int32)
-        inv_off[1:] = np.cumsum(np.bincount(key, minlength=139))
-        self.inv_n = torch.tensor((order % nl).astype(np.int32), device=self.dev)
-        self.inv_off = torch.tensor(inv_off, device=self.dev)
-        # inverse of the index: position of (k, n) in list order.  In the bf16 scoring modes the dE GEMM writes the time
-        # block of dE in THAT order (tcar_gemm_bf16_perm), so the candidate-time backward streams contiguous lists
-        et_perm = np.empty(5 * nl, dtype=np.int32)
-        et_perm[order] = np.arange(5 * nl, dtype=np.int32)
-        self.et_perm = torch.tensor(et_perm, device=self.dev)
+        self._build_time_index()
         self.adam_bitmap = torch.zeros(((nl + 31) // 32 + 15) // 16 * 16, dtype=torch.int32, device=self.dev)   # split update marks, whole 64-byte units
         self.ct_ws = torch.zeros(self.lib.tcar_cand_time_ws_floats(C.byref(self.dims_cand)), **f32)
         # segment tables for the optimizer kernels
@@ -284,6 +273,30 @@ class TcarEngine(OpLevelStep):
             s.off[i], s.len[i], s.slot[i] = sg["off"], sg["n"], sg["slot"]
         return s
 
+    _index_stale = False      # update_items changed publish times: the index below is rebuilt in front of the next training step
+
+    def _build_time_index(self):
+        """The static inverted index of publish_time_MWDHM (the host copy `_mwdhm_host` of the rows this engine owns): candidates
+        listed per time-table row (cand_time_bwd_indexed).  Built when the engine is; rebuilt INTO the same device buffers — the
+        pointers a context carries stay valid — in front of the first training step after update_items changed a publish time."""
+        nl = self.shard[1]
+        mw = self._mwdhm_host.astype(np.int64)
+        rowoff = np.array([0, 13, 45, 53, 78])
+        key = (np.clip(mw, 0, np.array(TIME_VOCAB) - 1) + rowoff[None, :]).T.reshape(-1)          # [5N], k-major
+        order = np.argsort(key, kind="stable")
+        inv_off = np.zeros(140, dtype=np.int32)
+        inv_off[1:] = np.cumsum(np.bincount(key, minlength=139))
+        # inverse of the index: position of (k, n) in list order.  In the bf16 scoring modes the dE GEMM writes the time
+        # block of dE in THAT order (tcar_gemm_bf16_perm), so the candidate-time backward streams contiguous lists
+        et_perm = np.empty(5 * nl, dtype=np.int32)
+        et_perm[order] = np.arange(5 * nl, dtype=np.int32)
+        for name, host in (("inv_n", (order % nl).astype(np.int32)), ("inv_off", inv_off), ("et_perm", et_perm)):
+            if getattr(self, name, None) is None:
+                setattr(self, name, torch.tensor(host, device=self.dev))
+            else:
+                getattr(self, name).copy_(torch.from_numpy(host))
+        self._index_stale = False
+
     # --------------------------------------------------------------------------------- parameter (un)packing
     def load_params(self, params: Dict[str, np.ndarray], content_emb: Optional[np.ndarray] = None):
         if getattr(self, "_pending_lr", None) is not None:
@@ -292,6 +305,7 @@ class TcarEngine(OpLevelStep):
         self.W.copy_(torch.from_numpy(self._pack_arena(params)))
         if content_emb is not None:
             self._content = np.asarray(content_emb, dtype=np.float32)
+            self._content_own = False         # (may be the caller's array: update_items copies it before its first write)
         item = np.asarray(params["item_emb"], dtype=np.float32)
         # the candidate matrix is assembled on the device in row chunks: no [Npad, ek] host image (33 GB at 10 M items)
         self.E.zero_()
@@ -837,6 +851,8 @@ class TcarEngine(OpLevelStep):
         (tcar_train_step_deferred) — or by flush(); results are identical, the HBM-bound pass over the item table leaves
         the critical path."""
         self._refuse_ragged(batch, bt, "train_step")
+        if self._index_stale:
+            self._build_time_index()
         bt = bt or self.upload(batch)
         if self.native:
             self._ensure_work(bt.B, bt.T)
@@ -859,6 +875,8 @@ class TcarEngine(OpLevelStep):
     def loss_and_grads(self, batch, bt: Optional[Batch] = None) -> torch.Tensor:
         self._refuse_ragged(batch, bt, "loss_and_grads")
         self.flush()
+        if self._index_stale:
+            self._build_time_index()
         bt = bt or self.upload(batch)
         if self.native:
             self._ensure_work(bt.B, bt.T)
@@ -1148,8 +1166,122 @@ class TcarEngine(OpLevelStep):
         _, topk, _, scores = self._serve(bt, k, panel, excl, False, window, max_per_category)
         return topk, scores
 
+    # ---- in-place catalog updates (include/tcar_catalog.h): publish, correct and retire articles in a live engine
+    def _update_request(self, ids, content, item_rows, mwdhm, keys, categories):
+        """The request of an update_items call, validated before anything is uploaded or launched -> (ids int32 [U], then content /
+        item_rows float32 [U, H], mwdhm int32 [U, 5], keys / categories int32 [U], each None where the call brings none)."""
+        g = self.geo
+        ids = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if ids.ndim != 1 or ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("ids must be an integer array [U] of at least one catalog row")
+        U = int(ids.size)
+        if int(ids.min()) < 0 or int(ids.max()) >= g.N:
+            raise ValueError("ids must lie in [0, N = %d)" % g.N)
+        if np.unique(ids).size != U:
+            raise ValueError("ids must be pairwise distinct")
+        if all(x is None for x in (content, item_rows, mwdhm, keys, categories)):
+            raise ValueError("update_items needs at least one of content, item_rows, mwdhm, keys, categories")
+
+        def table(x, what, shape, integer):
+            if x is None:
+                return None
+            x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+            ok = np.issubdtype(x.dtype, np.integer) if integer else (np.issubdtype(x.dtype, np.floating) or np.issubdtype(x.dtype, np.integer))
+            if not ok or x.shape != shape:
+                raise ValueError("%s must be %s array [%s]" % (what, "an integer" if integer else "a float", ", ".join(str(n) for n in shape)))
+            return x
+        content, item_rows = table(content, "content", (U, g.H), False), table(item_rows, "item_rows", (U, g.H), False)
+        mwdhm, keys = table(mwdhm, "mwdhm", (U, 5), True), table(keys, "keys", (U,), True)
+        categories = table(categories, "categories", (U,), True)
+        if keys is not None and getattr(self, "_item_keys", None) is None:
+            raise ValueError("keys update the item keys: call set_item_keys(keys) first")
+        if categories is not None and getattr(self, "_cat", None) is None:
+            raise ValueError("categories update the category table: call set_categories(cat_of_item) first")
+        for x, what in ((keys, "item keys"), (categories, "categories"), (mwdhm, "mwdhm")):
+            if x is not None and (int(x.min()) < -2 ** 31 or int(x.max()) >= 2 ** 31):
+                raise ValueError("%s must fit int32" % what)
+        f32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.float32)
+        i32 = lambda x: None if x is None else np.ascontiguousarray(x, dtype=np.int32)
+        return i32(ids), f32(content), f32(item_rows), i32(mwdhm), i32(keys), i32(categories)
+
+    def _catalog_ctx(self) -> "_lib.Ctx":
+        """the context of a catalog update: the catalog side alone (tables, planes, publish times, item moments, the arena for the
+        five time tables) — no workspace, so a fresh engine can be updated before its first batch"""
+        c = _lib.Ctx()
+        c.d, c.arena_n, c.scoring = self.dims, self.arena_n, self.scoring_code
+        for i, sg in enumerate(self.seg.values()):
+            c.off[i] = sg["off"]
+        for n in ["E", "W", "Mi", "Vi", "mwdhm"] + (["e16h", "e16l"] if self.scoring_code else []):
+            setattr(c, n, getattr(self, n).data_ptr())
+        return c
+
+    def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None) -> None:
+        """Replace rows of the catalog IN PLACE, between two calls of a live engine: ids int [U], 0-based as in `candidates` /
+        `exclude`, each in [0, N), pairwise distinct; then any of content / item_rows float [U, H], mwdhm int [U, 5]
+        (publish_time_MWDHM rows), keys int [U] (after set_item_keys), categories int [U] (after set_categories).  One staged copy
+        and one tcar_catalog_update on the engine's stream, ordered behind every earlier call and in front of every later one; no
+        device synchronisation (the pinned staging words are reused: a call waits for the COPY of the update before it, no more).  Every buffer the engine derives from a row — the fp32 image, the bf16 planes, the clipped time
+        block, the one-hot row — then holds the bytes of an engine built from the final tables (include/tcar_catalog.h), and no
+        whole-catalog refresh follows: where the time block was clean it stays clean.  item_rows zeroes the Adam moments of those
+        rows (a replaced row has no optimizer history).  A changed publish time marks the inverted index of the training step stale;
+        it is rebuilt once, in front of the next train_step / loss_and_grads.
+        Publishing without growing N: build the engine with spare rows whose key lies above every window's `hi` — they are in no
+        pool —, publish an article into one (content, mwdhm, keys = its minute, categories) and retire it by moving the key back."""
+        ids, content, item_rows, mwdhm, keys, categories = self._update_request(ids, content, item_rows, mwdhm, keys, categories)
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("update_items needs the whole catalog on this engine (no shard)")
+        self.flush()
+        U, ldr = int(ids.size), _ru(g.H, 4)
+        # the payload in ONE buffer of 4-byte words, every section on a 16-byte boundary: ids | mwdhm | keys | categories | item | content
+        parts, off, words = [("ids", ids), ("mwdhm", mwdhm), ("key", keys), ("cat", categories), ("item", item_rows), ("content", content)], {}, 0
+        for name, x in parts:
+            if x is not None:
+                off[name] = words
+                words += _ru(U * ldr if x.dtype == np.float32 else x.size, 4)
+        if getattr(self, "_upd_pin", None) is None or self._upd_pin.numel() < words:
+            self._upd_pin = torch.empty(max(words, 1 << 12), dtype=torch.int32).pin_memory()
+            self._upd_evt = None
+        if self._upd_evt is not None:
+            self._upd_evt.synchronize()          # the copy that last read the pinned words has finished
+        host = self._upd_pin.numpy()
+        for name, x in parts:
+            if x is None:
+                continue
+            if x.dtype == np.float32:
+                rows = host[off[name]:off[name] + U * ldr].view(np.float32).reshape(U, ldr)
+                rows[:, :g.H], rows[:, g.H:] = x, 0.0
+            else:
+                host[off[name]:off[name] + x.size] = x.reshape(-1)
+        self.ws.ensure([Spec("upd_stage", (max(words, 1 << 12),), I32)])
+        self.upd_stage[:words].copy_(self._upd_pin[:words], non_blocking=True)
+        self._upd_evt = torch.cuda.Event()
+        self._upd_evt.record(torch.cuda.current_stream(self.dev))
+        at = lambda name: self.upd_stage.data_ptr() + 4 * off[name] if name in off else None
+        d = _lib.CatalogUpdate()
+        d.U, d.ids = U, at("ids")
+        d.item, d.ld_item, d.content, d.ld_content, d.mwdhm = at("item"), ldr, at("content"), ldr, at("mwdhm")
+        # a dirty time block is rebuilt whole, from the updated table, by the next call anyway; a clean one stays clean
+        d.refresh_time = int(mwdhm is not None and not self._time_dirty)
+        if keys is not None:
+            d.key, d.key_table = at("key"), self._item_keys.data_ptr()
+        if categories is not None:
+            d.cat, d.cat_table = at("cat"), self._cat.data_ptr()
+        d.zero_moments = int(item_rows is not None)
+        if mwdhm is not None and getattr(self, "_oh16", None) is not None:
+            d.onehot, d.onehot_inner = self._oh16.data_ptr(), 160
+        check(self.lib.tcar_catalog_update(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_catalog_update")
+        # the host copies follow: load_params / export read the content, the index is rebuilt from the publish times
+        if content is not None:
+            if not self._content_own:
+                self._content, self._content_own = np.array(self._content, dtype=np.float32), True
+            self._content[1 + ids] = content
+        if mwdhm is not None:
+            self._mwdhm_host[ids] = mwdhm
+            self._index_stale = True
+
     # ---- candidate-list scoring (include/tcar_cand.h): only the rows a session names are read
-    CAND_MAX_C = 1024              # slots of one list (CAND_MAX_C of csrc/tcar_common.h)
+    CAND_MAX_C = 1024             # slots of one list (CAND_MAX_C of csrc/tcar_common.h)
 
     @staticmethod
     def _cand_request(B: int, candidates, clicked):

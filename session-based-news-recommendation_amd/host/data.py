@@ -36,6 +36,12 @@ def _dt_fields(dt) -> tuple:
     return (dt.month, dt.day, dt.isoweekday(), dt.hour, dt.minute)
 
 
+def publish_fields(dt) -> tuple:
+    """a publish datetime -> its publish_time_MWDHM row: month, day, isoweekday, hour + 1, minute + 1 (sampler.py:81-85)"""
+    pm, pd_, pw, ph, pmi = _dt_fields(dt)
+    return (pm, pd_, pw, ph + 1, pmi + 1)
+
+
 class SessionStore:
     """Flat, integer-only view of (len_dict, session_dict, session_time_dict).
 
@@ -85,8 +91,7 @@ class SessionStore:
                 prev = None
                 for j, t in enumerate(times):
                     p, cdt = t["publish_t"], t["click_t"]
-                    pm, pd_, pw, ph, pmi = _dt_fields(p)
-                    pub[o + j] = (pm, pd_, pw, ph + 1, pmi + 1)
+                    pub[o + j] = publish_fields(p)
                     cm, cd, cw, ch, cmi = _dt_fields(cdt)
                     clk[o + j] = (cm - 1, cd - 1, cw - 1, ch, cmi)
                     if "active_t" in t:

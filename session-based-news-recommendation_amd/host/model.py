@@ -25,7 +25,7 @@ import torch
 
 from ..engine import TIME_NAMES, TIME_VOCAB, TcarEngine, VAR_ORDER
 from . import cli, metrics as M
-from .data import pack_sessions
+from .data import pack_sessions, publish_fields
 from .sampler import Sampler
 
 
@@ -118,7 +118,7 @@ class Seq2SeqAttNN():
     """The memory network with context/temporal attention, MI355X edition."""
 
     def __init__(self, args):
-        self.publish_time_MWDHM = np.asarray(args['publish_time_MWDHM'], dtype=np.int32)
+        self.publish_time_MWDHM = np.array(args['publish_time_MWDHM'], dtype=np.int32)      # (a copy: update_articles writes it)
         self.itemnum = args['itemnum']
         self.category_id = args['category_id']
         self.item_freq_dict_norm = args.get('item_freq_dict_norm')
@@ -617,6 +617,42 @@ class Seq2SeqAttNN():
             self._item_keys()
         call = self.engine.shard_retrieve if self._sharded() else self.engine.retrieve
         return call(self._feed(sessions), C, window=window, **kw)
+
+    # ---------------------------------------------------------------------------------- catalog updates
+    def update_articles(self, ids, content=None, publish_time=None, category=None, item_rows=None):
+        """Publish, correct or retire articles in the live engine (engine.TcarEngine.update_items; one call of it): ids int [U] in
+        the id convention of the lists `recommend` returns (0-based), then any of content float [U, H], publish_time (U datetimes),
+        category int [U] (codes of the fold's category table) and item_rows float [U, H] (new item-table rows; their Adam moments
+        start from zero).  From publish_time come the publish_time_MWDHM rows — the fold loader's fields, host.data.publish_fields —
+        and, once the item keys are installed (a window has been used), the minute keys since the earliest publish time the keys
+        were built from; a time before it is refused.  The model's own tables (publish_time_MWDHM, publish_time, the keys, the
+        category table) follow the engine's.
+        The neighbour-negative lists of the sampler are NOT rebuilt: training after an update draws negatives from the lists the
+        fold was loaded with."""
+        ids = np.asarray(ids)
+        mw = keys = None
+        if publish_time is not None:
+            when = list(publish_time)
+            mw = np.asarray([publish_fields(t) for t in when], dtype=np.int32).reshape(len(when), 5)
+            if self._keys is not None:
+                keys = self.minute_of(when)
+                if keys.size and int(keys.min()) < 0:
+                    raise ValueError("publish_time before the earliest publish time of the item keys (%s): the keys count minutes since it"
+                                     % self._key_t0)
+        if category is not None:
+            self._install_categories()
+        self.engine.update_items(ids, content=content, item_rows=item_rows, mwdhm=mw, keys=keys, categories=category)
+        if publish_time is not None:
+            self.publish_time_MWDHM[ids] = mw
+            if self.publish_time is not None:
+                if not isinstance(self.publish_time, (list, np.ndarray)):
+                    self.publish_time = list(self.publish_time)
+                for i, t in zip(ids.tolist(), when):
+                    self.publish_time[i] = t
+            if keys is not None:
+                self._keys[ids] = keys.astype(np.int32)
+        if category is not None:
+            self._cat[ids] = np.asarray(category)          # in place: the table on the engine stays THIS table (_cat_on_engine)
 
     def _sharded(self) -> bool:
         """is the engine the catalog-sharded one (its serving calls are collectives under names of their own)?"""

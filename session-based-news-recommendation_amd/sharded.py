@@ -914,6 +914,12 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("recommend_two_stage() needs the whole catalog on one engine (no shard): the catalog-sharded engine "
                              "has neither retrieve() nor score_candidates()")
 
+    def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
+        """not on the catalog-sharded engine: a row would have to be routed to the rank that owns it, and the ranks would have to
+        agree on the update (include/tcar_catalog.h takes the whole catalog)"""
+        raise _lib.TcarError("update_items() needs the whole catalog on one engine (no shard): the catalog-sharded engine does not "
+                             "route rows to their owners")
+
     # ---- retrieval, candidate scoring and the two-stage call over the shards (include/tcar_retrieve_shard.h; the collectives:
     # ShardExchange.retrieve / .candidates).  New names: they are COLLECTIVES with cap / T arguments, which the single-engine calls of
     # the same purpose (refused above) do not have.

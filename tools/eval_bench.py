@@ -52,7 +52,16 @@ and ONE tcar_retrieve_panel launch over the engine's panel buffer for B sessions
 bucket — what a caller of the rectangular entry points has to do, one stream of the catalog per bucket — beside ONE recommend on the
 ragged feed of the same sessions (include/tcar_ragged.h), alternating for `rounds` rounds; ms per request batch, uploads included in
 both.  Then the head alone, device events around tcar_ragged_forward on resident batches: one ragged head of all 512 sessions beside
-the heads of the buckets (each a ragged call of uniform lengths, which runs exactly the launches of the rectangular head)."""
+the heads of the buckets (each a ragged call of uniform lengths, which runs exactly the launches of the rectangular head).
+
+       python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --update U[,U...] [--rounds R]
+
+--update U: TcarEngine.update_items (include/tcar_catalog.h) of U random distinct rows on an engine whose time block is clean (so the
+row refresh runs), for two payloads — content + mwdhm + key, and the item row alone —, beside what an engine without it has to do for
+ONE changed row: load_params(params, content) followed by the first recommend(), and beside the whole-catalog time refresh alone
+(device events around tcar_cand_time_fwd_bf16 as the steps call it).  An update is timed two ways, the host clock around work that ends
+in a device synchronise both times: `iters` calls back to back (ms per call at full rate, staging included) and single calls, each
+synchronised (the median: what one publisher waits).  Everything alternates for `rounds` rounds."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -76,6 +85,8 @@ ap.add_argument("--candidates", type=str, default="", help="comma-separated list
 ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve)")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
+ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
+ap.add_argument("--scoring", type=str, default="bf16x3-mixed", help="scoring mode of the engine (f32 | bf16x3 | bf16x3-mixed | bf16)")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 if not torch.cuda.is_available():
@@ -93,7 +104,8 @@ if a.sharded:
     eng = ShardedEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
     assert eng.world == a.sharded
 else:
-    eng = TcarEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
+    params0 = initial_variables(N, 250, 64, 0.002, 0.05, **(dict(lean=True) if N > 200000 and a.update else {}))
+    eng = TcarEngine(params0, fold.content, fold.mwdhm, device="cuda:0", scoring=a.scoring)
 batches = build_batches(fold, 16, B, 0, np.random.RandomState(1), CONFIGS["globo"])
 res = [eng.make_resident(b) for b in batches]
 
@@ -110,6 +122,84 @@ def timed(step):
 
 
 plain = lambda bt: eng.eval_step(None, bt=bt)
+ups = [int(u) for u in a.update.split(",") if u]
+if ups:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--update needs the whole catalog on one engine: not with --sharded")
+    g, rng = eng.geo, np.random.RandomState(9)
+    feed = {n: v for n, v in batches[0].items() if n not in ("label", "neg")}
+    eng.set_item_keys(np.arange(N, dtype=np.int32))
+    pay = {}
+    for U in ups:
+        ids = rng.choice(N, U, replace=False)
+        pay[U] = dict(ids=ids, content=(rng.standard_normal((U, g.H)) * 0.5).astype(np.float32),
+                      item=(rng.standard_normal((U, g.H)) * 0.002).astype(np.float32),
+                      mw=np.stack([rng.randint(1, v, U) for v in (13, 32, 8, 25, 61)], -1).astype(np.int32), keys=ids.astype(np.int32))
+    forms = (("content + mwdhm + key", lambda q: eng.update_items(q["ids"], content=q["content"], mwdhm=q["mw"], keys=q["keys"])),
+             ("item row", lambda q: eng.update_items(q["ids"], item_rows=q["item"])))
+
+    def update_times(call, q):
+        """(ms per call of `iters` calls back to back, median ms of single synchronised calls)"""
+        for _ in range(5):
+            call(q)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            call(q)
+        torch.cuda.synchronize()
+        rate = (time.perf_counter() - t0) / iters
+        one = []
+        for _ in range(min(iters, 50)):
+            t0 = time.perf_counter()
+            call(q)
+            torch.cuda.synchronize()
+            one.append(time.perf_counter() - t0)
+        return rate * 1e3, float(np.median(one)) * 1e3
+
+    def refresh_alone():
+        lib, p, st = eng.lib, eng._p, eng._stream()
+        planes = bool(eng.scoring_code)
+        args = (C_.byref(eng.dims), C_.byref(eng._time_ptrs()), p(eng.mwdhm), None if planes else p(eng.E), p(eng.e16h) if planes else None,
+                p(eng.e16l) if planes else None, st)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            assert lib.tcar_cand_time_fwd_bf16(*args) == 0
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters
+
+    def rebuild():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.load_params(params0, fold.content)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        eng.recommend(feed)
+        torch.cuda.synchronize()
+        return (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
+
+    eng.recommend(feed)                       # the workspace exists and the time block is clean: every update refreshes its rows
+    torch.cuda.synchronize()
+    row_bytes = 4 * 2 * g.ldh + (4 * g.ek if eng.scoring_code else 4 * g.pt)      # item | content in E, then the row of both planes or the fp32 time block
+    print("N=%d scoring=%s: ek=%d, %.1f KB written per row that takes content, item row and publish time (+ %.1f KB of moments)"
+          % (N, a.scoring, g.ek, row_bytes / 1e3, 8 * g.ldh / 1e3))
+    for rnd in range(a.rounds):
+        lp, first = rebuild()
+        print("N=%d %s round %d rebuild: load_params %.2f ms + first recommend %.3f ms = %.2f ms" % (N, a.scoring, rnd, lp, first, lp + first))
+        assert not eng._time_dirty
+        print("N=%d %s round %d whole-catalog time refresh alone: %.4f ms" % (N, a.scoring, rnd, refresh_alone()))
+        for U in ups:
+            for name, call in forms:
+                rate, one = update_times(call, pay[U])
+                assert not eng._time_dirty
+                print("N=%d %s round %d update_items U=%d (%s): %.4f ms per call back to back, %.4f ms one synchronised call = 1 / %.0f of the rebuild"
+                      % (N, a.scoring, rnd, U, name, rate, one, (lp + first) / one))
+        sys.stdout.flush()
+    eng.check_forks()
+    sys.exit(0)
 cands = [int(c) for c in a.candidates.split(",") if c]
 if cands:
     import ctypes as C_
