@@ -34,13 +34,14 @@ def _hipcc() -> str:
 
 # The C ABI, one row per layer: (prefix of the layer's names in this module, its header under include/).  Every header is compiled
 # into the library AND read by _bind(), and each builds on the rows above it: the core; in-place updates of catalog rows in a live
-# context (on the core alone, so it sits next to it); streamed score-and-select; its publish-time
+# context (on the core alone, so it sits next to it) and their ownership-aware form for a rank that holds a shard of the candidate
+# side; streamed score-and-select; its publish-time
 # windows; its per-category caps; the state merge and the shard's fold of the catalog-sharded serving path; candidate-list scoring;
 # the streamed top-C shortlist and the two-stage step; the shortlist merge, the owner-aware candidate gather and the shard's side
 # of both on the catalog-sharded engine; ragged batches (sessions of mixed lengths) under every serving step.
-ABI_LAYERS = [("", "tcar_hip.h"), ("CATALOG", "tcar_catalog.h"), ("SERVE", "tcar_serve.h"), ("WINDOW", "tcar_window.h"),
-              ("QUOTA", "tcar_quota.h"), ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"), ("RETRIEVE", "tcar_retrieve.h"),
-              ("RETRIEVE_SHARD", "tcar_retrieve_shard.h"), ("RAGGED", "tcar_ragged.h")]
+ABI_LAYERS = [("", "tcar_hip.h"), ("CATALOG", "tcar_catalog.h"), ("CATALOG_SHARD", "tcar_catalog_shard.h"), ("SERVE", "tcar_serve.h"),
+              ("WINDOW", "tcar_window.h"), ("QUOTA", "tcar_quota.h"), ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"),
+              ("RETRIEVE", "tcar_retrieve.h"), ("RETRIEVE_SHARD", "tcar_retrieve_shard.h"), ("RAGGED", "tcar_ragged.h")]
 
 
 def _name(prefix: str, name: str) -> str:

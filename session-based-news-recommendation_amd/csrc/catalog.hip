@@ -11,9 +11,14 @@
 // cand_time_fwd_kernel — and pass through 5 ldt floats of LDS per wave to change owner from 4 columns per lane to 8.  Staging all
 // 139 rows per workgroup, as the whole-catalog refresh does, would read and clip 139 rows for four catalog rows: 28 times the five a
 // wave needs, at every U (the grid follows U, so the share per workgroup never grows).
+//
+// Ownership (include/tcar_catalog_shard.h): the kernel takes the rows [n0, n0 + nl) a context OWNS.  E, the key and category tables and
+// the optional whole publish-time table are indexed by the catalog row n and written for every named row; the planes, the context's
+// publish times, the one-hot plane and the moments are the owner's, indexed by n - n0 and written only where n is owned.
+// tcar_catalog_update is the owned form with (0, N): ONE kernel body, so both give the bytes of a rebuild by the same code.
 #include "tcar_common.h"
 #include "tcar_bf16_layout.h"
-#include "../../include/tcar_catalog.h"
+#include "../../include/tcar_catalog_shard.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_c;
 
@@ -21,10 +26,12 @@ namespace {
 
 struct CatArgs {
   int U, N, H, ldh, ldt, planes, refresh;
+  int n0, nl;                          // the rows this context owns: [n0, n0 + nl) of [0, N)
   const int32_t* ids;
   const float* item; long ld_item;
   const float* content; long ld_content;
-  const int32_t* mw_new; int32_t* mw_tab;
+  const int32_t* mw_new; int32_t* mw_tab;   // mw_tab: the owner's table, [nl, 5]
+  int32_t* mw_all;                     // the whole [N, 5] table a rank may keep beside it, or null
   const float* tab[5];
   float* E; __bf16* eh; __bf16* el;
   const int32_t* key; int32_t* key_table;
@@ -63,6 +70,8 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const CatArgs a) {
   const long u = (long)blockIdx.x * 4 + wave;
   const int n = u < a.U ? a.ids[u] : -1;
   const bool live = n >= 0 && n < a.N;            // (an id outside the catalog names no row: nothing is read or written for it)
+  const bool own = live && n >= a.n0 && n - a.n0 < a.nl;      // (per wave: the planes, publish times, one-hot row and moments are the owner's)
+  const int r = own ? n - a.n0 : 0;               // the row in the owner's buffers
   float* const Erow = a.E + (long)(live ? n : 0) * ek;
 
   // item | content rows -> E and the planes
@@ -76,7 +85,7 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const CatArgs a) {
       const float4 t0 = ld4_live(row, w, a.H), t1 = ld4_live(row, w + 4, a.H);
       st4(Erow + c, t0);
       st4(Erow + c + 4, t1);
-      if (a.planes) store_planes8(a.eh, a.el, kb32_off(n, c, in32), t0, t1);
+      if (a.planes && own) store_planes8(a.eh, a.el, kb32_off(r, c, in32), t0, t1);
     }
   }
 
@@ -84,30 +93,34 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const CatArgs a) {
   int id[5];
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
-    const int raw = !live ? 0 : a.mw_new ? a.mw_new[u * 5 + k] : a.mw_tab ? a.mw_tab[(long)n * 5 + k] : 0;
+    const int raw = !own ? 0 : a.mw_new ? a.mw_new[u * 5 + k] : a.mw_tab ? a.mw_tab[(long)r * 5 + k] : 0;
     id[k] = clampi(raw, 0, time_vocab(k) - 1);
   }
-  if (live && a.mw_new && lane < 5) a.mw_tab[(long)n * 5 + lane] = a.mw_new[u * 5 + lane];
+  if (live && a.mw_new && lane < 5) {
+    const int32_t v = a.mw_new[u * 5 + lane];
+    if (own) a.mw_tab[(long)r * 5 + lane] = v;
+    if (a.mw_all) a.mw_all[(long)n * 5 + lane] = v;
+  }
 
   // clipped time block: clip the five table rows in groups of ldt / 4 lanes, hand them over through LDS, store 8 columns per lane —
   // into E on an fp32 context, into the planes alone on a plane context (the destinations of tcar_cand_time_fwd_bf16 in step.hip)
-  if (a.refresh) {                                // (uniform over the grid: every thread reaches the barrier)
+  if (a.refresh) {                                // (uniform over the grid: every thread reaches the barrier, a wave that owns nothing too)
     float* const my = lds + wave * pt;
     const int sub = ldt >> 2, gpw = 64 / sub;
     const int grp = lane / sub, lin = lane - grp * sub;
     for (int k0 = 0; k0 < 5; k0 += gpw) {
       const int k = k0 + grp;
-      const bool valid = live && k < 5;
+      const bool valid = own && k < 5;
       const int kk = k < 5 ? k : 0;
       const float4 x = valid ? ld4(pick5(a.tab, kk) + (long)pick5(id, kk) * ldt + lin * 4) : zero4();
       const float4 y = clip_time_piece(x, sub);
       if (valid) st4(my + kk * ldt + lin * 4, y);
     }
     __syncthreads();
-    if (live) {
+    if (own) {                                    // (an fp32 context owns the whole catalog: r == n, Erow is row n)
       for (int c = lane * 8; c < pt; c += 512) {
         const float4 t0 = ld4(my + c), t1 = ld4(my + c + 4);
-        if (a.planes) store_planes8(a.eh, a.el, kb32_off(n, ic + c, in32), t0, t1);
+        if (a.planes) store_planes8(a.eh, a.el, kb32_off(r, ic + c, in32), t0, t1);
         else {
           st4(Erow + ic + c, t0);
           st4(Erow + ic + c + 4, t1);
@@ -116,6 +129,11 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const CatArgs a) {
     }
   }
   if (!live) return;
+  if (lane == 0) {                                // the whole tables every rank keeps
+    if (a.key) a.key_table[n] = a.key[u];
+    if (a.cat) a.cat_table[n] = a.cat[u];
+  }
+  if (!own) return;
 
   // the one-hot row of tcar_time_onehot: ones at the five time rows and at the anchor columns 139 .. 146, zeros elsewhere
   if (a.oh && a.mw_new) {
@@ -129,19 +147,15 @@ __global__ __launch_bounds__(256) void catalog_update_kernel(const CatArgs a) {
         for (int k = 0; k < 5; ++k) one = one || col == time_rowoff(k) + id[k];
         o[j] = (__bf16)(one ? 1.0f : 0.0f);
       }
-      *reinterpret_cast<bf16x8_c*>(a.oh + kb32_off(n, c, a.oh_in32)) = o;
+      *reinterpret_cast<bf16x8_c*>(a.oh + kb32_off(r, c, a.oh_in32)) = o;
     }
   }
   // a replaced row has no optimizer history
   if (a.Mi) {
     for (int c = lane * 4; c < ldh; c += 256) {
-      st4(a.Mi + (long)n * ldh + c, zero4());
-      st4(a.Vi + (long)n * ldh + c, zero4());
+      st4(a.Mi + (long)r * ldh + c, zero4());
+      st4(a.Vi + (long)r * ldh + c, zero4());
     }
-  }
-  if (lane == 0) {
-    if (a.key) a.key_table[n] = a.key[u];
-    if (a.cat) a.cat_table[n] = a.cat[u];
   }
 }
 
@@ -152,11 +166,10 @@ bool bad_dims(const tcar_dims_t& d) {
 }
 bool bad_table(const float* p, int64_t ld, int H) { return p && (!tcar_aligned16(p) || ld < H || (ld & 3)); }
 
-}  // namespace
-
-extern "C" int tcar_catalog_abi_version(void) { return TCAR_CATALOG_ABI_VERSION; }
-
-extern "C" int tcar_catalog_update(const tcar_ctx_t* c, const tcar_catalog_update_t* u, void* stream) {
+// both entry points: the rows [n0, n0 + n_loc) of the context's catalog are owned (sharded: the shard-local layout of
+// tcar_catalog_shard.h; whole: (0, N), where it is the layout of tcar_catalog.h)
+int update_rows(const tcar_ctx_t* c, const tcar_catalog_update_t* u, bool sharded, int32_t n0, int32_t n_loc, int32_t* mwdhm_all,
+                void* stream) {
   if (!c || !u || u->U < 0) return TCAR_E_ARG;
   if (u->U == 0) return TCAR_OK;
   // the descriptor
@@ -172,8 +185,12 @@ extern "C" int tcar_catalog_update(const tcar_ctx_t* c, const tcar_catalog_updat
   if (u->mwdhm && !c->mwdhm) return TCAR_E_ARG;
   if (u->zero_moments && (!c->Mi || !c->Vi || !tcar_aligned16(c->Mi) || !tcar_aligned16(c->Vi))) return TCAR_E_ARG;
   if (u->refresh_time && (!c->W || !tcar_aligned16(c->W))) return TCAR_E_ARG;
+  // the shard
+  if (sharded && (!c->scoring || n0 < 0 || n_loc <= 0 || (long)n0 + n_loc > c->d.n_items)) return TCAR_E_ARG;
+  if (!sharded) { n0 = 0; n_loc = c->d.n_items; }
 
   CatArgs a{};
+  a.n0 = n0; a.nl = n_loc; a.mw_all = mwdhm_all;
   a.U = u->U; a.N = c->d.n_items; a.H = c->d.H; a.ldh = c->d.ldh; a.ldt = c->d.ldt;
   a.planes = c->scoring != 0; a.refresh = u->refresh_time != 0;
   a.ids = u->ids;
@@ -193,4 +210,18 @@ extern "C" int tcar_catalog_update(const tcar_ctx_t* c, const tcar_catalog_updat
   TCAR_LAUNCH(catalog_update_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
   TCAR_CHECK_LAUNCH();
   return TCAR_OK;
+}
+
+}  // namespace
+
+extern "C" int tcar_catalog_abi_version(void) { return TCAR_CATALOG_ABI_VERSION; }
+extern "C" int tcar_catalog_shard_abi_version(void) { return TCAR_CATALOG_SHARD_ABI_VERSION; }
+
+extern "C" int tcar_catalog_update(const tcar_ctx_t* c, const tcar_catalog_update_t* u, void* stream) {
+  return update_rows(c, u, false, 0, 0, nullptr, stream);
+}
+
+extern "C" int tcar_catalog_update_owned(const tcar_ctx_t* c, const tcar_catalog_update_t* u, int32_t n0, int32_t n_loc,
+                                         int32_t* mwdhm_all, void* stream) {
+  return update_rows(c, u, true, n0, n_loc, mwdhm_all, stream);
 }

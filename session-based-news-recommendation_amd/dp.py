@@ -217,6 +217,26 @@ class Collectives:
             self._note(key, t)
         return t
 
+    def agree(self, digest: bytes, key: Optional[str] = "update_digest", device=None) -> None:
+        """Every rank holds the same 16 bytes, or TcarError: ONE all-gather of the digest as four int32 words (on the CPU for a gloo
+        group, on `device` — default: the current one — for nccl and the direct RCCL communicator), then every rank looks at the
+        same [W, 4] table, so a disagreement raises on EVERY rank, naming the ranks whose digest differs from rank 0's.  The host
+        reads the gathered table: this is the one synchronisation of a catalog update (shard_update_items / replica_update_items
+        with verify=True); nothing else of an update waits for the device.  Without live collectives (one rank, a sim world): a
+        no-op, nothing is gathered and nothing is waited for."""
+        if not self.collective:
+            return
+        if len(digest) != 16:
+            raise ValueError("agree() takes a digest of 16 bytes")
+        words = torch.from_numpy(np.frombuffer(digest, dtype=np.int32).copy())
+        if self.backend != "gloo":
+            words = words.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        table = self.all_gather(words, key).cpu()
+        differ = [r for r in range(self.world) if not torch.equal(table[r], table[0])]
+        if differ:
+            raise _lib.TcarError("the ranks do not agree on the update: the request of rank%s %s differs from rank 0's (seen on rank %d); "
+                                 "nothing was written" % ("s" if len(differ) > 1 else "", ", ".join(str(r) for r in differ), self.rank))
+
     def share_rows(self, stage: torch.Tensor, install) -> None:
         """the item-row all-gather: `stage` [W, S, ldh] holds this rank's updated rows in slot `rank`; issued asynchronously —
         wait_rows() calls `install(stage)` to copy the gathered table into place once it has landed"""
@@ -242,6 +262,21 @@ class Collectives:
             if work is not None:
                 work.wait()                   # NCCL: orders the current stream behind the collective, no host block
             install(stage)
+
+
+def update_digest(ids, content, item_rows, mwdhm, keys, categories) -> bytes:
+    """16 bytes that name the request of a catalog update — what the ranks compare in Collectives.agree.  Takes the VALIDATED arrays
+    of TcarEngine._update_request (int32 / float32, None where the call brings none): blake2b over U, the mask of the fields that
+    are present and the bytes of each, contiguous, in request order.  Requests that validate to the same arrays (a list, an int64
+    array, a tensor of the same values) hash equal; any changed element, field or order does not."""
+    import hashlib
+    fields = (ids, content, item_rows, mwdhm, keys, categories)
+    h = hashlib.blake2b(digest_size=16)
+    h.update(np.asarray([int(ids.size), sum(1 << i for i, x in enumerate(fields) if x is not None)], dtype=np.int64).tobytes())
+    for x, dt in zip(fields, (np.int32, np.float32, np.float32, np.int32, np.int32, np.int32)):
+        if x is not None:
+            h.update(np.ascontiguousarray(x, dtype=dt).tobytes())
+    return h.digest()
 
 
 class GradExchange(Collectives):
@@ -396,8 +431,20 @@ class DPEngine(TcarEngine):
         self.xch.close()
 
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
-        """not on a replica: every rank holds the whole catalog, and nothing makes the ranks agree on an update"""
+        """not under this name on a replica: every rank holds the whole catalog and the ranks have to agree on an update — that is
+        replica_update_items(), a collective"""
         raise _lib.TcarError("update_items() is not for the data-parallel replicas: the ranks would have to agree on the update")
+
+    def replica_update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None, verify: bool = True) -> None:
+        """TcarEngine.update_items on every replica.  A COLLECTIVE when `verify` is set and collectives are live: every rank passes
+        the same request; it is validated (the same ValueErrors, before anything else), the ranks compare its digest
+        (Collectives.agree: one all-gather of 16 bytes, the one host synchronisation of the call — a disagreement raises TcarError
+        on every rank and nothing is written), then every replica, which holds the whole catalog, applies it with the whole-catalog
+        kernel.  verify=False skips the comparison and its synchronisation: the caller vouches for the request."""
+        req = self._update_request(ids, content, item_rows, mwdhm, keys, categories)
+        if verify:
+            self.xch.agree(update_digest(*req), device=getattr(self, "dev", None))
+        TcarEngine.update_items(self, *req)
 
     def _ensure_rows(self, rows: int):
         if rows > self.rows_cap:
@@ -525,6 +572,8 @@ class DPEngine(TcarEngine):
     def _local(self, bt):
         """forward + rank-local backward, driven from C++ (tcar_step_forward / tcar_step_backward_local)."""
         self.flush()
+        if self._index_stale:                      # (replica_update_items changed a publish time)
+            self._build_time_index()
         if self.native:
             self._ensure_work(bt.B, bt.T)
             ctx, st = self._ctx(), self._stream()

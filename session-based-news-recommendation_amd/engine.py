@@ -1215,23 +1215,12 @@ class TcarEngine(OpLevelStep):
             setattr(c, n, getattr(self, n).data_ptr())
         return c
 
-    def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None) -> None:
-        """Replace rows of the catalog IN PLACE, between two calls of a live engine: ids int [U], 0-based as in `candidates` /
-        `exclude`, each in [0, N), pairwise distinct; then any of content / item_rows float [U, H], mwdhm int [U, 5]
-        (publish_time_MWDHM rows), keys int [U] (after set_item_keys), categories int [U] (after set_categories).  One staged copy
-        and one tcar_catalog_update on the engine's stream, ordered behind every earlier call and in front of every later one; no
-        device synchronisation (the pinned staging words are reused: a call waits for the COPY of the update before it, no more).  Every buffer the engine derives from a row — the fp32 image, the bf16 planes, the clipped time
-        block, the one-hot row — then holds the bytes of an engine built from the final tables (include/tcar_catalog.h), and no
-        whole-catalog refresh follows: where the time block was clean it stays clean.  item_rows zeroes the Adam moments of those
-        rows (a replaced row has no optimizer history).  A changed publish time marks the inverted index of the training step stale;
-        it is rebuilt once, in front of the next train_step / loss_and_grads.
-        Publishing without growing N: build the engine with spare rows whose key lies above every window's `hi` — they are in no
-        pool —, publish an article into one (content, mwdhm, keys = its minute, categories) and retire it by moving the key back."""
-        ids, content, item_rows, mwdhm, keys, categories = self._update_request(ids, content, item_rows, mwdhm, keys, categories)
+    def _stage_update(self, ids, content, item_rows, mwdhm, keys, categories) -> "_lib.CatalogUpdate":
+        """The validated request of a catalog update on the device -> its descriptor (tcar_catalog_update_t), all but the one-hot
+        plane: the payload in ONE pinned buffer and ONE copy on the engine's stream; the pinned words are reused, so a call waits for
+        the COPY of the update before it, no more.  refresh_time as every engine wants it: publish times given and the time block
+        clean — a dirty one is rebuilt whole, from the updated table, by the next call anyway; a clean one stays clean."""
         g = self.geo
-        if self.shard != (0, g.N):
-            raise _lib.TcarError("update_items needs the whole catalog on this engine (no shard)")
-        self.flush()
         U, ldr = int(ids.size), _ru(g.H, 4)
         # the payload in ONE buffer of 4-byte words, every section on a 16-byte boundary: ids | mwdhm | keys | categories | item | content
         parts, off, words = [("ids", ids), ("mwdhm", mwdhm), ("key", keys), ("cat", categories), ("item", item_rows), ("content", content)], {}, 0
@@ -1261,13 +1250,32 @@ class TcarEngine(OpLevelStep):
         d = _lib.CatalogUpdate()
         d.U, d.ids = U, at("ids")
         d.item, d.ld_item, d.content, d.ld_content, d.mwdhm = at("item"), ldr, at("content"), ldr, at("mwdhm")
-        # a dirty time block is rebuilt whole, from the updated table, by the next call anyway; a clean one stays clean
         d.refresh_time = int(mwdhm is not None and not self._time_dirty)
         if keys is not None:
             d.key, d.key_table = at("key"), self._item_keys.data_ptr()
         if categories is not None:
             d.cat, d.cat_table = at("cat"), self._cat.data_ptr()
         d.zero_moments = int(item_rows is not None)
+        return d
+
+    def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None) -> None:
+        """Replace rows of the catalog IN PLACE, between two calls of a live engine: ids int [U], 0-based as in `candidates` /
+        `exclude`, each in [0, N), pairwise distinct; then any of content / item_rows float [U, H], mwdhm int [U, 5]
+        (publish_time_MWDHM rows), keys int [U] (after set_item_keys), categories int [U] (after set_categories).  One staged copy
+        and one tcar_catalog_update on the engine's stream, ordered behind every earlier call and in front of every later one; no
+        device synchronisation (the pinned staging words are reused: a call waits for the COPY of the update before it, no more).  Every buffer the engine derives from a row — the fp32 image, the bf16 planes, the clipped time
+        block, the one-hot row — then holds the bytes of an engine built from the final tables (include/tcar_catalog.h), and no
+        whole-catalog refresh follows: where the time block was clean it stays clean.  item_rows zeroes the Adam moments of those
+        rows (a replaced row has no optimizer history).  A changed publish time marks the inverted index of the training step stale;
+        it is rebuilt once, in front of the next train_step / loss_and_grads.
+        Publishing without growing N: build the engine with spare rows whose key lies above every window's `hi` — they are in no
+        pool —, publish an article into one (content, mwdhm, keys = its minute, categories) and retire it by moving the key back."""
+        ids, content, item_rows, mwdhm, keys, categories = self._update_request(ids, content, item_rows, mwdhm, keys, categories)
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("update_items needs the whole catalog on this engine (no shard)")
+        self.flush()
+        d = self._stage_update(ids, content, item_rows, mwdhm, keys, categories)
         if mwdhm is not None and getattr(self, "_oh16", None) is not None:
             d.onehot, d.onehot_inner = self._oh16.data_ptr(), 160
         check(self.lib.tcar_catalog_update(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_catalog_update")

@@ -628,7 +628,10 @@ class Seq2SeqAttNN():
         were built from; a time before it is refused.  The model's own tables (publish_time_MWDHM, publish_time, the keys, the
         category table) follow the engine's.
         The neighbour-negative lists of the sampler are NOT rebuilt: training after an update draws negatives from the lists the
-        fold was loaded with."""
+        fold was loaded with.
+        Routed by engine, as score_candidates: the catalog-sharded engine takes it as shard_update_items, the data-parallel replicas
+        as replica_update_items, any other engine as update_items.  On the first two EVERY rank calls update_articles with the same
+        arguments — as every rank already builds the same batches — and the ranks check that they did (dp.Collectives.agree)."""
         ids = np.asarray(ids)
         mw = keys = None
         if publish_time is not None:
@@ -641,7 +644,9 @@ class Seq2SeqAttNN():
                                      % self._key_t0)
         if category is not None:
             self._install_categories()
-        self.engine.update_items(ids, content=content, item_rows=item_rows, mwdhm=mw, keys=keys, categories=category)
+        call = (self.engine.shard_update_items if self._sharded() else
+                self.engine.replica_update_items if hasattr(self.engine, "replica_update_items") else self.engine.update_items)
+        call(ids, content=content, item_rows=item_rows, mwdhm=mw, keys=keys, categories=category)
         if publish_time is not None:
             self.publish_time_MWDHM[ids] = mw
             if self.publish_time is not None:

@@ -602,6 +602,8 @@ class ShardedEngine(TcarEngine):
         g = self.geo
         B = bt.B if bt is not None else 0
         cap = max(cap, B, 1)
+        if self._index_stale:                      # (shard_update_items changed a publish time of an owned row)
+            self._build_time_index()
         self.xch.wait_rows()                       # the previous update's rows, before anything reads the item table
         self._ensure_work(max(B, 1), T)
         self._ensure_score(cap, K)
@@ -915,10 +917,53 @@ class ShardedEngine(TcarEngine):
                              "has neither retrieve() nor score_candidates()")
 
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
-        """not on the catalog-sharded engine: a row would have to be routed to the rank that owns it, and the ranks would have to
-        agree on the update (include/tcar_catalog.h takes the whole catalog)"""
+        """not under this name on the catalog-sharded engine (include/tcar_catalog.h takes the whole catalog): a row's derived state
+        lives on the rank that owns it and the ranks have to agree on the update — that is shard_update_items(), a collective"""
         raise _lib.TcarError("update_items() needs the whole catalog on one engine (no shard): the catalog-sharded engine does not "
                              "route rows to their owners")
+
+    # ---- in-place catalog updates over the shards (include/tcar_catalog_shard.h).  A name of its own, as the calls below: it is a
+    # COLLECTIVE, which the single-engine call (refused above) is not.
+    _mwdhm_full_own = False       # (`_mwdhm_full` may be the caller's array: shard_update_items copies it before its first write)
+
+    def shard_update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None, verify: bool = True) -> None:
+        """TcarEngine.update_items over the shards: the arguments, the ValueErrors and the guarantee are its own — after the call
+        every buffer of every rank holds the bytes of an engine built from the final tables.  A COLLECTIVE when `verify` is set and
+        collectives are live: EVERY rank passes the SAME request (the whole update, not its own rows).  In this order: the request is
+        validated; flush() installs the pending item-row all-gather of the last training update (its install() would otherwise
+        overwrite freshly written rows of E); the ranks compare the digest of the request (dp.Collectives.agree: one all-gather of
+        16 bytes and the ONE host synchronisation of the call — a disagreement raises TcarError on every rank, nothing written);
+        one staged copy and ONE tcar_catalog_update_owned on the engine's stream: E, the key and category tables and the whole
+        publish-time table of eval_step on every rank, the planes, the clipped time block (where it was clean: it stays clean), the
+        one-hot row, the moments and the shard's publish times by the rank that owns the row; then the host copies.
+        verify=False skips the comparison and with it the synchronisation: the caller vouches for the request.
+        A changed publish time of an OWNED row marks this rank's inverted index stale (rebuilt in front of the next training step)."""
+        ids, content, item_rows, mwdhm, keys, categories = req = self._update_request(ids, content, item_rows, mwdhm, keys, categories)
+        self.flush()
+        if verify:
+            self.xch.agree(dp.update_digest(*req), device=self.dev)
+        d = self._stage_update(ids, content, item_rows, mwdhm, keys, categories)
+        oh = getattr(self, "s_oh16", None) if self.onehot else None          # the shard's one-hot plane, once its scoring family exists
+        if mwdhm is not None and oh is not None:
+            d.onehot, d.onehot_inner = oh.data_ptr(), 160
+        ev_mw = getattr(self, "_ev_mw", None) if mwdhm is not None else None
+        check(self.lib.tcar_catalog_update_owned(C.byref(self._catalog_ctx()), C.byref(d), self.n0, self.nl,
+                                                 None if ev_mw is None else C.c_void_p(ev_mw.data_ptr()), self._stream()),
+              "tcar_catalog_update_owned")
+        # the host copies follow: load_params / export read the content, the index is rebuilt from the owned publish times
+        if content is not None:
+            if not self._content_own:
+                self._content, self._content_own = np.array(self._content, dtype=np.float32), True
+            self._content[1 + ids] = content
+        if mwdhm is not None:
+            if not self._mwdhm_full_own:
+                self._mwdhm_full, self._mwdhm_full_own = np.array(self._mwdhm_full, dtype=np.int32), True
+            self._mwdhm_full[ids] = mwdhm
+            own = (ids >= self.n0) & (ids < self.n0 + self.nl)
+            loc = ids[own] - self.n0
+            if own.any() and (self._mwdhm_host[loc] != mwdhm[own]).any():
+                self._mwdhm_host[loc] = mwdhm[own]
+                self._index_stale = True
 
     # ---- retrieval, candidate scoring and the two-stage call over the shards (include/tcar_retrieve_shard.h; the collectives:
     # ShardExchange.retrieve / .candidates).  New names: they are COLLECTIVES with cap / T arguments, which the single-engine calls of

@@ -54,14 +54,17 @@ ragged feed of the same sessions (include/tcar_ragged.h), alternating for `round
 both.  Then the head alone, device events around tcar_ragged_forward on resident batches: one ragged head of all 512 sessions beside
 the heads of the buckets (each a ragged call of uniform lengths, which runs exactly the launches of the rectangular head).
 
-       python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --update U[,U...] [--rounds R]
+       python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --update U[,U...] [--sharded W] [--rounds R]
 
 --update U: TcarEngine.update_items (include/tcar_catalog.h) of U random distinct rows on an engine whose time block is clean (so the
 row refresh runs), for two payloads — content + mwdhm + key, and the item row alone —, beside what an engine without it has to do for
 ONE changed row: load_params(params, content) followed by the first recommend(), and beside the whole-catalog time refresh alone
 (device events around tcar_cand_time_fwd_bf16 as the steps call it).  An update is timed two ways, the host clock around work that ends
 in a device synchronise both times: `iters` calls back to back (ms per call at full rate, staging included) and single calls, each
-synchronised (the median: what one publisher waits).  Everything alternates for `rounds` rounds."""
+synchronised (the median: what one publisher waits).  Everything alternates for `rounds` rounds.
+With --sharded W: ShardedEngine.shard_update_items(verify=False) (include/tcar_catalog_shard.h) at the shapes of rank 0 of W ranks —
+the sim world, so no collective and no agreement — beside load_params() + the first sharded recommend() on the same engine; the
+time refresh alone is the shard's."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -80,7 +83,7 @@ ap.add_argument("--window", type=str, default="", help="comma-separated fraction
 ap.add_argument("--cap", type=str, default="", help="comma-separated caps: at most M items of one category in a list")
 ap.add_argument("--cats", type=int, default=300, help="number of category codes when the synthetic fold carries no category table")
 ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog whose items all share one category")
-ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (needs --streamed)")
+ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (with --streamed, --retrieve or --update)")
 ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
 ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve)")
@@ -94,17 +97,17 @@ if not torch.cuda.is_available():
 N, B, iters = a.n_items, 512, a.iters
 fold = SynthFold(n_items=N, dim=250, n_train=60000, n_test=1000, seed=2020, **(dict(lean=True) if N > 200000 else {}))
 np.random.seed(2020)
+params0 = initial_variables(N, 250, 64, 0.002, 0.05, **(dict(lean=True) if N > 200000 and a.update else {}))
 if a.sharded:
-    if not a.streamed and not a.retrieve:
-        sys.exit("--sharded W compares the two evaluation steps of the catalog-sharded engine (--streamed) or its two recommendation "
-                 "calls (--retrieve C): it needs one of them")
+    if not a.streamed and not a.retrieve and not a.update:
+        sys.exit("--sharded W compares the two evaluation steps of the catalog-sharded engine (--streamed), its two recommendation "
+                 "calls (--retrieve C) or a catalog update with a rebuild (--update U): it needs one of them")
     if a.sharded > 1:
         os.environ["TCAR_SIM_WORLD"] = str(a.sharded)
     from tcar_amd.sharded import ShardedEngine
-    eng = ShardedEngine(initial_variables(N, 250, 64, 0.002, 0.05), fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
+    eng = ShardedEngine(params0, fold.content, fold.mwdhm, device="cuda:0", scoring="bf16x3-mixed")
     assert eng.world == a.sharded
 else:
-    params0 = initial_variables(N, 250, 64, 0.002, 0.05, **(dict(lean=True) if N > 200000 and a.update else {}))
     eng = TcarEngine(params0, fold.content, fold.mwdhm, device="cuda:0", scoring=a.scoring)
 batches = build_batches(fold, 16, B, 0, np.random.RandomState(1), CONFIGS["globo"])
 res = [eng.make_resident(b) for b in batches]
@@ -125,8 +128,12 @@ plain = lambda bt: eng.eval_step(None, bt=bt)
 ups = [int(u) for u in a.update.split(",") if u]
 if ups:
     import ctypes as C_
+    # --sharded W: ShardedEngine.shard_update_items(verify=False) at the shapes of rank 0 of W ranks (the sim world: no collective, so
+    # no agreement either), beside load_params() + the first sharded recommend() of the same engine
+    update = (lambda ids, **kw: eng.shard_update_items(ids, verify=False, **kw)) if a.sharded else eng.update_items
+    uname = "shard_update_items W=%d" % a.sharded if a.sharded else "update_items"
     if a.sharded:
-        sys.exit("--update needs the whole catalog on one engine: not with --sharded")
+        a.scoring = "bf16x3-mixed, rank 0 of %d (%d rows)" % (a.sharded, eng.nl)
     g, rng = eng.geo, np.random.RandomState(9)
     feed = {n: v for n, v in batches[0].items() if n not in ("label", "neg")}
     eng.set_item_keys(np.arange(N, dtype=np.int32))
@@ -136,8 +143,8 @@ if ups:
         pay[U] = dict(ids=ids, content=(rng.standard_normal((U, g.H)) * 0.5).astype(np.float32),
                       item=(rng.standard_normal((U, g.H)) * 0.002).astype(np.float32),
                       mw=np.stack([rng.randint(1, v, U) for v in (13, 32, 8, 25, 61)], -1).astype(np.int32), keys=ids.astype(np.int32))
-    forms = (("content + mwdhm + key", lambda q: eng.update_items(q["ids"], content=q["content"], mwdhm=q["mw"], keys=q["keys"])),
-             ("item row", lambda q: eng.update_items(q["ids"], item_rows=q["item"])))
+    forms = (("content + mwdhm + key", lambda q: update(q["ids"], content=q["content"], mwdhm=q["mw"], keys=q["keys"])),
+             ("item row", lambda q: update(q["ids"], item_rows=q["item"])))
 
     def update_times(call, q):
         """(ms per call of `iters` calls back to back, median ms of single synchronised calls)"""
@@ -160,7 +167,7 @@ if ups:
     def refresh_alone():
         lib, p, st = eng.lib, eng._p, eng._stream()
         planes = bool(eng.scoring_code)
-        args = (C_.byref(eng.dims), C_.byref(eng._time_ptrs()), p(eng.mwdhm), None if planes else p(eng.E), p(eng.e16h) if planes else None,
+        args = (C_.byref(eng.dims_cand), C_.byref(eng._time_ptrs()), p(eng.mwdhm), None if planes else p(eng.E), p(eng.e16h) if planes else None,
                 p(eng.e16l) if planes else None, st)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         for it in range(5 + iters):
@@ -195,8 +202,8 @@ if ups:
             for name, call in forms:
                 rate, one = update_times(call, pay[U])
                 assert not eng._time_dirty
-                print("N=%d %s round %d update_items U=%d (%s): %.4f ms per call back to back, %.4f ms one synchronised call = 1 / %.0f of the rebuild"
-                      % (N, a.scoring, rnd, U, name, rate, one, (lp + first) / one))
+                print("N=%d %s round %d %s U=%d (%s): %.4f ms per call back to back, %.4f ms one synchronised call = 1 / %.0f of the rebuild"
+                      % (N, a.scoring, rnd, uname, U, name, rate, one, (lp + first) / one))
         sys.stdout.flush()
     eng.check_forks()
     sys.exit(0)
