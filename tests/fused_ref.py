@@ -6,7 +6,7 @@ in-launch slab folds) leaves its own gradients; `loss_and_grads` takes another p
 and TWO batches: the first step starts at the initial parameters (its oracle run is cached and shared by the three precisions), the
 second is teacher-forced from the parameters the engine exported behind its own update.
 
-The gates are those the suite already holds on gradients (test_gpu_parity.check_grads: rtol 1e-3 + 5e-5 of the variable's largest,
+The gates are those the suite already holds on gradients (step_cases.check_grads: rtol 1e-3 + 5e-5 of the variable's largest,
 clip norms 2e-3; bf16x3-mixed 1e-2 norm-wise, large elements within 10 %, clip norms 2e-2) restated as ratios error / bound so that a
 test can print them, plus two things defined from the same constants:
   * a ROW-WISE check of item_emb (`item_row_ratio`): every row whose oracle norm is >= MIXED_BIG_FRAC of the largest holds the
@@ -26,9 +26,11 @@ from collections import OrderedDict
 
 import numpy as np
 
+from step_cases import CASES, MIXED_BIG_FRAC, MIXED_BIG_RTOL, MIXED_GRAD_RTOL, MIXED_SQNORM_RTOL, _case, check_grads
+
 SCORINGS = ("f32", "bf16x3", "bf16x3-mixed")
 MAX_GRAD = 2.0
-GRAD_RTOL, GRAD_ATOL = 1e-3, 5e-5            # test_gpu_parity.close as check_grads calls it
+GRAD_RTOL, GRAD_ATOL = 1e-3, 5e-5            # gpu_util.close as step_cases.check_grads calls it
 SQN_RTOL = 2e-3
 # the five weights used as x @ W in the attention layers: name -> (x, dy) keys of the oracle's forward
 XW = OrderedDict([
@@ -54,11 +56,10 @@ def _mk(N, H, Ht, pseed, steps, tweaks=(), tuning=None, both=False, floor=None, 
 
 
 def _cases():
-    from test_gpu_parity import CASES as P
     c = OrderedDict()
     # A. the eight shapes of test_step_matches_oracle (same seeds), then the next shape's batch at the same model
-    for i, (N, H, Ht, B, T, K) in enumerate(P):
-        _, _, _, B2, T2, K2 = P[(i + 1) % len(P)]
+    for i, (N, H, Ht, B, T, K) in enumerate(CASES):
+        _, _, _, B2, T2, K2 = CASES[(i + 1) % len(CASES)]
         s = N + H + B + T
         c["parity%d" % i] = _mk(N, H, Ht, s, [(B, T, K, s), (B2, T2, K2, s + 1)], tweaks=("tail_label",))
     small = (300, 40, 16)
@@ -184,7 +185,6 @@ def build(name):
     """-> dict(spec, params, content, mw, batches [2])"""
     if name in _BUILT:
         return _BUILT[name]
-    from test_gpu_parity import _case
     spec = cases()[name]
     N, H, Ht = spec["N"], spec["H"], spec["Ht"]
     (B, T, K, seed), (B2, T2, K2, seed2) = spec["steps"]
@@ -263,7 +263,6 @@ def _r(err, bound):
 
 def item_row_ratio(got, want, scoring):
     """worst row-wise rel_norm over the rows of item_emb that carry signal, over the precision's gradient gate"""
-    from test_gpu_parity import MIXED_BIG_FRAC, MIXED_GRAD_RTOL
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
     rn = np.linalg.norm(want, axis=1)
     if not rn.max() > 0:
@@ -276,7 +275,7 @@ def item_row_ratio(got, want, scoring):
 def below_fp32(want, got, gmax):
     """A variable whose every oracle element is below 2^-24 of the step's largest gradient while the implementation holds exact zeros:
     the gradient through the exp-normaliser of a length-1 session is proportional to 1 - alpha = 1e-9 / (e + 1e-9), which fp32 rounds to
-    0 (test_gpu_parity.close has a floor of 1e-9 for it; at H = 250 the oracle's value is 3e-9).  Zero IS the fp32 answer there."""
+    0 (gpu_util.close has a floor of 1e-9 for it; at H = 250 the oracle's value is 3e-9).  Zero IS the fp32 answer there."""
     return float(np.abs(want).max()) < 2.0 ** -24 * gmax and not np.asarray(got).any()
 
 
@@ -287,7 +286,6 @@ def gate_ratios(g_e, sq_e, ref, scoring, floors=None):
     large element and, for an array A, the norm the relative term is stated on, max(||want||, ||A||).  The clip norm of a dense weight
     with a floor (||g||^2) is allowed what that gate allows its gradient: 2 ||g|| E + E^2, E the norm of the allowed error."""
     from oracle.tcar_oracle import TABLES
-    from test_gpu_parity import MIXED_BIG_FRAC, MIXED_BIG_RTOL, MIXED_GRAD_RTOL, MIXED_SQNORM_RTOL
     g_o, sq_o = ref["grads"], ref["sqn"]
     floors = floors or {}
     gmax = max(float(np.abs(v).max()) for v in g_o.values())
@@ -327,7 +325,6 @@ def worst(r):
 def check(g_e, sq_e, ref, scoring, floors=None):
     """the assertion of both tests: check_grads itself on every variable without a floor (and not below fp32's resolution: below_fp32),
     the ratios on all of them"""
-    from test_gpu_parity import check_grads
     gmax = max(float(np.abs(v).max()) for v in ref["grads"].values())
     keep = [k for k in ref["grads"] if not (floors and k in floors)
             and not (scoring != "bf16x3-mixed" and below_fp32(ref["grads"][k], g_e[k], gmax))]

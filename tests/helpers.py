@@ -1,9 +1,18 @@
-"""Shared helpers for tests: fixture loading (JSON -> the reference's dict/datetime form)."""
+"""Shared helpers for tests: fixture loading (the golden step; JSON -> the reference's dict/datetime form)."""
 import datetime
 import json
 import os
 
+import numpy as np
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def load_fixture():
+    z = np.load(os.path.join(GOLD, "oracle_step_small.npz"))
+    params = {k[2:]: z[k] for k in z.files if k.startswith("p/")}
+    batch = {k[2:]: z[k] for k in z.files if k.startswith("b/")}
+    return z, params, batch
 
 
 def load_sampler_fixture():

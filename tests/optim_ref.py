@@ -11,6 +11,8 @@ from collections import OrderedDict
 
 import numpy as np
 
+from step_cases import _case
+
 NSLOT = 32
 B1, B2, EPS, LR = 0.9, 0.999, 1e-8, 1e-3
 F = np.float32
@@ -218,7 +220,7 @@ def a_inputs(shape, seed=11):
 # name -> (N, H, Ht, K, parameter seed, max_grad, [(B, T, batch seed, tweak)]).  The clip census (clip_census) holds in every step:
 #  * A single session clips the item table at max_grad 2 only when it is short: norm 3.1 at T = 2 with this seed, 1.9 at T = 5, 1.2 at
 #    T = 12.  So the B = 1 step has T = 2.
-#  * T = 1 is left out: the gradients through the exp-normaliser of a length-1 session are below fp32 resolution.  test_gpu_parity.close
+#  * T = 1 is left out: the gradients through the exp-normaliser of a length-1 session are below fp32 resolution.  gpu_util.close
 #    has an absolute floor of 1e-9 for them; the gates here have none.
 #  * The lone session clicks two DIFFERENT items (tweak "distinct"; _case would repeat the first).  With one item clicked twice the two
 #    positions differ by dec_pos only, and the attention weights' gradients are differences of nearly equal terms: the split-bf16 modes'
@@ -239,7 +241,6 @@ def b_sequence(name):
     if name in _SEQ:
         return _SEQ[name]
     from oracle.tcar_oracle import TABLES, TcarOracle
-    from test_gpu_parity import _case
     N, H, Ht, K, pseed, max_grad, plan = B_CASES[name]
     params, content, mw, _ = _case(N, H, Ht, plan[0][0], plan[0][1], K, seed=pseed)
     ora = TcarOracle(params, content, mw, max_grad=max_grad)

@@ -1,9 +1,9 @@
 """What the tests of ragged batches (include/tcar_ragged.h) share: the two length mixes, a mixed batch at the shape of
-test_gpu_serve.reference() as a ragged feed, and the fp64 oracle's scores of it — eval_batch per length group, the rows put back in
+serve_case.reference() as a ragged feed, and the fp64 oracle's scores of it — eval_batch per length group, the rows put back in
 session order.  Computed once, shared, never written."""
 import numpy as np
 
-from test_gpu_serve import B, N, reference
+from serve_case import B, N, reference
 
 SET = (1, 2, 3, 4, 5, 7, 8, 40)
 # 41 sessions: T = 1; below, at and above the four register-cached positions; odd lengths against the 2- and 4-position trips; the

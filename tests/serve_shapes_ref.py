@@ -19,7 +19,7 @@ import numpy as np
 from cand_ref import rank_model
 from retrieve_ref import shortlist
 from select_ref import finish, fold_state
-from select_util import close
+from gpu_util import close
 
 U = 2.0 ** -8
 TOPK = 20
@@ -57,7 +57,7 @@ _IN, _REF, _RAGGED, _TRAIN = {}, {}, {}, {}
 
 
 def inputs(name):
-    """(params, content, mw, batch) of a case: the content of `_case` of tests/test_gpu_parity.py.  Computed once, never written."""
+    """(params, content, mw, batch) of a case: the content of `_case` of tests/step_cases.py.  Computed once, never written."""
     if name not in _IN:
         from oracle.tcar_oracle import init_params_numpy
         c = CASES[name]

@@ -5,7 +5,6 @@ on engines that were never built, and the routing of Seq2SeqAttNN.update_article
 import ctypes as C
 import datetime
 import os
-import socket
 import sys
 import types
 
@@ -18,6 +17,8 @@ from tcar_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+from dist_util import launch  # noqa: E402
 
 
 def test_the_layer_is_bound_and_every_pinned_count_and_position_is_unchanged():
@@ -149,14 +150,6 @@ def test_requests_that_validate_to_the_same_arrays_hash_equal_and_nothing_else_d
 
 
 # ---------------------------------------------------------------------------------------- agreement over gloo
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _agree_worker(rank, world, port, ret):
     import torch.distributed as dist
     for k in ("TCAR_FORCE_COLLECTIVES", "TCAR_RCCL_DIRECT", "TCAR_SIM_WORLD"):
@@ -212,10 +205,8 @@ def _agree_worker(rank, world, port, ret):
 
 
 def test_agree_over_gloo_returns_on_equal_digests_and_raises_on_both_ranks_otherwise():
-    import torch.multiprocessing as mp
     world = 2
-    ret = mp.Manager().dict()
-    mp.spawn(_agree_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    ret = launch(_agree_worker, world)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 
@@ -288,6 +279,8 @@ class _Recorder:
 @pytest.mark.parametrize("names, want", [(("update_items",), "update_items"),
                                          (("update_items", "replica_update_items"), "replica_update_items"),
                                          (("update_items", "shard_update_items", "shard_retrieve"), "shard_update_items")])
+
+
 def test_update_articles_routes_by_engine(names, want):
     from tcar_amd.host.data import publish_fields
     from tcar_amd.host.model import Seq2SeqAttNN

@@ -5,25 +5,17 @@ a stand-in communicator that answers wrongly) and close()."""
 import ctypes as C
 import datetime
 import os
-import socket
 import sys
 
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from dist_util import launch  # noqa: E402
+
 ENV = ("TCAR_FORCE_COLLECTIVES", "TCAR_RCCL_DIRECT", "TCAR_SIM_WORLD")
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, ret):
@@ -148,8 +140,6 @@ def _worker(rank, world, port, ret):
 
 def test_collectives_layer_world2_gloo():
     world = 2
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    ret = launch(_worker, world)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)

@@ -4,33 +4,25 @@ Each rank computes the gradients of ITS shard with the CPU oracle, the exchange 
 documented in dp.py, and the result must equal the single-process oracle on the concatenated global batch:
 summed gradients, the IndexedSlices clip norms (S5) and the variables after clip + Adam."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from dist_util import launch  # noqa: E402
+from helpers import load_fixture  # noqa: E402
+
 TIME = ["month_embedding", "day_embedding", "week_embedding", "hour_embedding", "minute_embedding"]
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _global_case():
     import tcar_amd  # noqa: F401
-    from test_oracle_model import load_fixture
     z, params, batch = load_fixture()
     return z, params, batch
 
@@ -155,9 +147,7 @@ def _worker(rank, world, port, ret, split_big=False):
 @pytest.mark.parametrize("split_big", [False, True])
 def test_gradient_exchange_world2_matches_single_process(split_big):
     world = 2
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, split_big), nprocs=world, join=True)
+    ret = launch(_worker, world, split_big)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 

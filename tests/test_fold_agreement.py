@@ -2,7 +2,7 @@
 lo <= key < hi, the unaligned key slice), so on the same matrix, the same `excl` and the same window the first k entries of the
 shortlist (tcar_retrieve_*) ARE the unlabelled select list (tcar_select_*): ids and scores, byte for byte.
 
-Inputs: those of test_gpu_retrieve_select.reference() — B = 5, N = 5,000, ld = 5,120, X = 24 — with the NaN entries of row 3 made
+Inputs: those of retrieve_select_case.reference() — B = 5, N = 5,000, ld = 5,120, X = 24 — with the NaN entries of row 3 made
 finite (the select fold reserves NaN for dead candidates; its +inf, -inf, -0.0 and +0.0 entries stay).  Row 4 with the filters keeps
 its pool of 180 items, so every list of k <= 64 is full.  The host half compares the two numpy models and runs without a GPU; the GPU
 half compares the two kernels with each other and with the model, over "panels of 128" and "1001 + 3999, copied" (a key slice that is
@@ -13,10 +13,10 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+import retrieve_select_case as rs
 import select_ref
-import test_gpu_retrieve_select as rs
+from gpu_util import lib, ptr  # noqa: F401  (lib: the fixture)
 from retrieve_ref import eligible_mask, shortlist
-from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 B, N, LD, X = rs.B, rs.N, rs.LD, rs.X
 KS = (1, 20, 64)

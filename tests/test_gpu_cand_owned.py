@@ -9,7 +9,7 @@ import torch
 import tcar_amd  # noqa: F401
 
 from cand_ref import bf16_values, kb32_plane
-from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -8,7 +8,7 @@ import torch
 import tcar_amd  # noqa: F401
 
 from cand_ref import rank_model
-from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

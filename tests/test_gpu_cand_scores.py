@@ -7,7 +7,7 @@ import torch
 import tcar_amd  # noqa: F401
 
 from cand_ref import bf16_values, kb32_plane
-from select_util import _need_gpu, lib, ptr  # noqa: F401  (lib: fixture)
+from gpu_util import _need_gpu, lib, ptr  # noqa: F401  (lib: fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """Candidate-list scoring at the engine level (TcarEngine.score_candidates, tcar_cand_step) against the fp64 oracle, on the reference
-setup of tests/test_gpu_serve.py.  The engine's scores differ from the oracle's by rounding, so ranks and pair counts are checked in
+setup of tests/serve_case.py.  The engine's scores differ from the oracle's by rounding, so ranks and pair counts are checked in
 BANDS of delta_b = 1e-3 * max_n |s[b, n]| — the project's logits gate — in which no session and no slot is left out."""
 import io
 from contextlib import redirect_stdout
@@ -10,28 +10,10 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from select_util import _need_gpu, close
-from test_gpu_serve import B, N, TOPK, reference
+from gpu_util import _need_gpu, close
+from serve_case import B, C_, N, TOPK, _lists, reference
 
 pytestmark = pytest.mark.gpu
-
-C_ = 37
-
-
-def _lists():
-    """the label in slot 0, 30 random ids, 3 repeats of earlier slots and 3 empty slots (-1, N, -7); clicked: the label and a few more"""
-    lab = reference()["batch"]["label"]
-    rng = np.random.RandomState(23)
-    cand = np.empty((B, C_), np.int32)
-    cand[:, 0] = lab
-    cand[:, 1:31] = rng.randint(0, N, (B, 30))
-    cand[:, 31:34] = np.take_along_axis(cand, rng.randint(0, 31, (B, 3)), 1)
-    cand[:, 34:] = [-1, N, -7]
-    for b in range(B):                                  # the empty slots and the repeats sit somewhere else in every row
-        cand[b, 1:] = cand[b, 1:][rng.permutation(C_ - 1)]
-    clicked = (rng.rand(B, C_) < 0.15).astype(np.int32)
-    clicked[:, 0] = 1
-    return cand, clicked
 
 
 @pytest.mark.parametrize("scoring", ["f32", "bf16x3-mixed"])

@@ -3,7 +3,7 @@ ShardedEngine.shard_update_items, DPEngine.replica_update_items).  The contract 
 BITS as buffers, or engines, built from scratch from the final tables — so every comparison but one is torch.equal / tobytes; the one
 tolerance (test 3) is the project's gate for scores against the fp64 oracle (tests/serve_shapes_ref.py).
 
-Shapes and tables: those of test_gpu_catalog_update (N = 700, H = 250 / ldh = 256, Ht = 64, B = 8, T = 5).  Shards: W = 2 holds rows
+Shapes and tables: those of catalog_case (N = 700, H = 250 / ldh = 256, Ht = 64, B = 8, T = 5).  Shards: W = 2 holds rows
 384 / 316 — rank 0's buffers END at its last owned row, the canary directly behind; rank 1 has 68 padding rows that must stay zero —,
 W = 3 holds 256 / 256 / 188.  Id sets: [0], [N - 1], the seams [383, 384] and [255, 256, 511, 512], rows 256 .. 383 (ONE shard at
 either W: the other ranks own nothing), 37 scattered ids in random order, all N rows reversed.
@@ -19,6 +19,7 @@ either W: the other ranks own nothing), 37 scattered ids in random order, all N 
   6  two ranks over gloo on one device: agreement, then the bits of the in-process engines; a request that differs in one element on
      rank 1 raises on both ranks and leaves every catalog buffer as it was."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -29,12 +30,12 @@ import tcar_amd  # noqa: F401
 from tcar_amd import _lib
 
 import serve_shapes_ref as R
-from select_util import _need_gpu
-from test_gpu_catalog_update import (B, CANARY, EK, FAR, H, HT, LDH, LDT, N, NPAD, SPARE, T, VOCAB, Raw, _bytes, _device_payload, _guarded,
-                                     _moments, final_tables, tables)
-from test_gpu_catalog_update import _update as _update_whole
-from test_gpu_shard_retrieve import play_candidates, play_retrieve
-from test_gpu_shard_serve import _free_port, play
+from catalog_case import (B, CANARY, EK, FAR, H, HT, LDH, LDT, N, NPAD, SPARE, T, VOCAB, Raw, _bytes, _device_payload, _guarded, _moments,
+                          final_tables, tables)
+from catalog_case import _update as _update_whole
+from dist_util import launch
+from gpu_util import _need_gpu, _np, lib  # noqa: F401  (lib: the module-scoped fixture)
+from shard_case import play, play_candidates, play_retrieve, split
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +49,7 @@ ENGINE_IDS = ID_SETS["scattered"] + [i for i in (0, 127, 128, 255, 256, 383, 384
 SPLITS = {1: ([8], 8), 2: ([5, 3], 6), 3: ([3, 0, 5], 5)}       # sessions per rank (uneven, one rank with none at W = 3) and cap
 TOPK, PANEL, SHORT = 20, 128, 64
 WINDOW = (1000, 600000)
+_split = functools.partial(split, splits=SPLITS)       # shard_case.split over the split sizes of THIS module
 
 
 # ----------------------------------------------------------------------------------- 1  the kernel, raw bytes
@@ -128,12 +130,6 @@ def _same_shard(got, want, what, skip=()):
         assert not bool(got.oh.view(got.nlpad // 128, 5, 128, 32)[-1, :, pad:, :].view(torch.int16).any()), (what, "padding rows of the one-hot plane")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    _need_gpu()
-    return _lib.load()
-
-
 @pytest.mark.parametrize("refresh", [0, 1])
 @pytest.mark.parametrize("name", list(ID_SETS))
 @pytest.mark.parametrize("W, rank", [(w, r) for w in (2, 3) for r in range(w)])
@@ -190,10 +186,6 @@ def test_ids_outside_the_catalog_and_rows_of_other_ranks_write_nothing_here(lib)
 
 
 # ------------------------------------------------------------------------ 2  updated engines against rebuilt ones
-def _np(*ts):
-    return [t.cpu().numpy().copy() for t in ts]
-
-
 _STATE = {}
 
 
@@ -223,12 +215,6 @@ def _engines(W, params, content, mw, keys, cat, scoring, state=None, max_grad=2.
         e.set_categories(cat)
         out.append(e)
     return out
-
-
-def _split(batch, W):
-    sizes, cap = SPLITS[W]
-    edges = np.r_[0, np.cumsum(sizes)]
-    return [({k: v[a:b] for k, v in batch.items()} if b > a else None) for a, b in zip(edges[:-1], edges[1:])], edges, cap
 
 
 def _recommend(engs, W, **kw):
@@ -595,11 +581,8 @@ def _worker(rank, world, port, ret, scoring):
 
 def test_two_ranks_over_gloo_agree_and_give_the_bits_of_the_two_engines_in_one_process():
     _need_gpu()
-    import torch.multiprocessing as mp
     scoring, world = "bf16x3-mixed", 2
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, scoring), nprocs=world, join=True)
+    ret = launch(_worker, world, scoring, spawned_manager=True)
     for rk in range(world):
         assert isinstance(ret.get(rk), dict), ret.get(rk)
     engs, _ = _prepared(scoring, world, "fresh")

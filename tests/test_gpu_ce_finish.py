@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _kb32_index, _planes, close, lib, ptr, ptr2  # noqa: F401  (lib: the module's fixture)
+from gpu_util import _kb32_index, _planes, close, lib, ptr, ptr2  # noqa: F401  (lib: the module's fixture)
 
 pytestmark = pytest.mark.gpu
 

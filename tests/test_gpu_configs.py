@@ -15,21 +15,10 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+from gpu_util import RTOL, _need_gpu
+from gpu_util import close_broadcast as close
+
 pytestmark = pytest.mark.gpu
-RTOL = 1e-3            # north-star tolerance (BASELINE.json): 1e-3 relative
-
-
-def close(got, want, rtol=RTOL, atol_scale=2e-5, name=""):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    atol = atol_scale * max(1e-30, float(np.abs(want).max()))
-    bad = np.abs(got - want) > atol + rtol * np.abs(want)
-    assert not bad.any(), "%s: %d / %d off, max abs err %.3e (max |want| %.3e)" % (
-        name, int(bad.sum()), bad.size, float(np.abs(got - want).max()), float(np.abs(want).max()))
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 CONFIGS = {

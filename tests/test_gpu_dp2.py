@@ -3,7 +3,6 @@ DPEngine path on the real kernels — rank-local forward/backward from the C++ d
 GradExchange collective schedule, scatter of the all-gathered rows, clip + Adam — against a single engine that sees the
 concatenated batch.  (RCCL itself needs >1 GPU; the driver's scaling run covers it.)"""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -14,18 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from dist_util import launch  # noqa: E402
+from step_cases import _case  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, scoring, ret):
+def _worker(rank, world, port, ret, scoring):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -33,7 +27,6 @@ def _worker(rank, world, port, scoring, ret):
         import tcar_amd  # noqa: F401
         from tcar_amd.dp import DPEngine, shard_bounds
         from tcar_amd.engine import TcarEngine
-        from test_gpu_parity import _case
         N, H, Ht, B, T, K = 1000, 250, 64, 37, 4, 6          # 37 sessions: uneven shards (19 + 18)
         params, content, mw, batch = _case(N, H, Ht, B, T, K, seed=5)
         lo, hi, cap = shard_bounds(B, world, rank)
@@ -70,16 +63,13 @@ def _worker(rank, world, port, scoring, ret):
 def test_two_ranks_match_single_engine(scoring):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    import torch.multiprocessing as mp
     world = 2
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), scoring, ret), nprocs=world, join=True)
+    ret = launch(_worker, world, scoring, spawned_manager=True)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 
 
-def _cli_worker(rank, world, port, argv, ret):
+def _cli_worker(rank, world, port, ret, argv):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), TCAR_DIST_BACKEND="gloo", TCAR_SAME_DEVICE="1")
     try:
@@ -104,12 +94,9 @@ def test_cli_two_ranks_shard_batches_and_agree_with_one_rank(extra):
         pytest.skip("no GPU")
     import io
     from contextlib import redirect_stdout
-    import torch.multiprocessing as mp
     argv = ["--synthetic", "700", "--synthetic_train", "3000", "--synthetic_test", "600", "--epoch", "2",
             "--hidden_size", "48", "--time_hidden_size", "16", "--batch_size", "128", "--gap_mode", "click_delta"]
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_cli_worker, args=(2, _free_port(), argv + extra, ret), nprocs=2, join=True)
+    ret = launch(_cli_worker, 2, argv + extra, spawned_manager=True)
     for r in range(2):
         assert isinstance(ret.get(r), dict), ret.get(r)
     assert ret[0] == ret[1]                                   # every rank reports the same all-reduced numbers

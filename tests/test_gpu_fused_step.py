@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import fused_ref as F
-from test_gpu_parity import close
+from gpu_util import close
 
 pytestmark = pytest.mark.gpu
 

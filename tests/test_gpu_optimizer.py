@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import optim_ref as R
-from test_gpu_parity import _kb32_index, close, lib, ptr, ptr2  # noqa: F401  (lib: the module-scoped fixture)
+from gpu_util import _kb32_index, close, lib, ptr, ptr2  # noqa: F401  (lib: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 

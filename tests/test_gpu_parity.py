@@ -10,47 +10,19 @@ import torch
 
 import tcar_amd  # noqa: F401
 from tcar_amd import _lib
+from gpu_util import RTOL, _kb32_index, _need_gpu, _planes, close, lib, ptr, ptr2  # noqa: F401  (lib: the module-scoped fixture)
 from helpers import GOLD
+from step_cases import CASES, _case, check_grads, rel_norm
 
 pytestmark = pytest.mark.gpu
-
-RTOL = 1e-3
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def close(got, want, rtol=RTOL, atol_scale=2e-5, name=""):
-    got = np.asarray(got, dtype=np.float64)
-    want = np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    scale = max(float(np.abs(want).max()), 1e-30)
-    err = np.abs(got - want)
-    # absolute floor 1e-9: quantities below fp32 resolution of their inputs (e.g. the gradient through the
-    # exp-normaliser of a length-1 session, ~1e-9 relative) are legitimately 0 in fp32 and ~1e-11 in fp64
-    tol = rtol * np.abs(want) + atol_scale * scale + 1e-9
-    bad = err > tol
-    assert not bad.any(), "%s: %d/%d off, max err %.3e (scale %.3e) at %s" % (
-        name, bad.sum(), bad.size, err.max(), scale, np.unravel_index(err.argmax(), err.shape))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    _need_gpu()
-    from tcar_amd import _lib
-    return _lib.load()
-
-
-def ptr(t, off=0):
-    return C.c_void_p(t.data_ptr() + 4 * off)
 
 
 # ------------------------------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("M,N,K", [(1, 1, 4), (5, 7, 8), (130, 129, 36), (128, 128, 32), (512, 300, 832),
                                    (257, 64, 1000), (64, 832, 2052)])
+
+
 def test_gemm_layouts(lib, layout, M, N, K):
     rng = np.random.RandomState(M * 7 + N * 3 + K + layout)
     ld = lambda x: (x + 3) // 4 * 4 + 4
@@ -180,72 +152,6 @@ def test_softmax_ce_and_rank_topk(lib):
 
 
 # --------------------------------------------------------------------------------------------- full model
-def _case(N, H, Ht, B, T, K, seed, emb_std=0.35, w_std=0.12):
-    from oracle.tcar_oracle import init_params_numpy
-    rng = np.random.RandomState(seed)
-    params = init_params_numpy(N, H, Ht, emb_std, w_std, rng)
-    content = (rng.standard_normal((N + 1, H)) * 0.5).astype(np.float32)
-    content[0] = 0
-    mw = np.stack([rng.randint(1, 13, N), rng.randint(1, 32, N), rng.randint(1, 8, N), rng.randint(1, 25, N),
-                   rng.randint(1, 61, N)], -1).astype(np.int32)
-    b = {"seq": rng.randint(1, N + 1, (B, T)), "label": rng.randint(0, N, B), "pm": rng.randint(1, 13, (B, T)),
-         "pd": rng.randint(1, 32, (B, T)), "pw": rng.randint(1, 8, (B, T)), "ph": rng.randint(1, 25, (B, T)),
-         "pmi": rng.randint(1, 61, (B, T)), "cw": rng.randint(0, 7, B), "ch": rng.randint(0, 24, B),
-         "gap": rng.randint(0, 12, (B, T)), "neg": rng.randint(0, N, (B, K))}
-    b = {k: v.astype(np.int32) for k, v in b.items()}
-    if T > 1:
-        b["seq"][0, 1] = b["seq"][0, 0]            # a repeated item inside one session
-    b["seq"][-1, 0] = b["seq"][0, 0]               # and across sessions (scatter collisions)
-    return params, content, mw, b
-
-
-CASES = [  # N, H, Ht, B, T, K
-    (50, 12, 8, 1, 1, 3),
-    (50, 12, 8, 3, 2, 4),
-    (1000, 250, 64, 64, 7, 20),
-    (1000, 40, 16, 3, 40, 5),
-    (1000, 256, 64, 5, 3, 2),
-    (129, 250, 64, 130, 3, 1),          # N just past one 128-row block, B past one 128-row plane block, a single negative
-    (1000, 250, 64, 513, 2, 33),        # B = 512 + 1: a second (one-row) M tile in every scoring GEMM; K > 32 negatives
-    (1000, 250, 64, 300, 8, 5),         # B * T = 2,400: a LONG bucket — un-split projections (> TCAR_PROJ_SPLIT_ROWS), small-table backward in chunks
-]
-
-
-def rel_norm(got, want):
-    """norm-wise relative error ||got - want|| / ||want||"""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    return float(np.linalg.norm(got - want) / max(np.linalg.norm(want), 1e-300))
-
-
-# bf16x3-mixed (the precision bench.py and main.py default to): logits / loss at the 1e-3 gate, the two scoring-gradient
-# GEMMs on plain bf16 operands -> EVERY gradient within 1e-2 norm-wise, every clip norm within 2e-2
-MIXED_GRAD_RTOL = 1e-2
-MIXED_SQNORM_RTOL = 2e-2
-MIXED_BIG_FRAC, MIXED_BIG_RTOL = 0.1, 0.1
-
-
-def check_grads(g_e, sq_e, g_o, sq_o, scoring, atol_scale=5e-5):
-    """all 23 gradients and their S5 clip norms against the oracle, at the gate of the scoring precision"""
-    gmax = max(float(np.abs(np.asarray(v)).max()) for v in g_o.values())
-    for k in g_o:
-        want = np.asarray(g_o[k], dtype=np.float64)
-        if scoring == "bf16x3-mixed":
-            # gradients that are rounding noise on both sides (zero in exact arithmetic) are compared on the step's scale
-            got = np.asarray(g_e[k], dtype=np.float64)
-            err = np.linalg.norm(got - want)
-            assert err <= MIXED_GRAD_RTOL * np.linalg.norm(want) + 1e-7 * gmax * np.sqrt(want.size), ("grad " + k, err, np.linalg.norm(want))
-            # ... and element-wise where an element carries signal (>= 10 % of the variable's largest): right sign, within 10 % —
-            # a norm-wise gate alone would let a wrong-sign coordinate of a large variable through (VERDICT r03, weak 1)
-            big = np.abs(want) >= MIXED_BIG_FRAC * np.abs(want).max()
-            if big.any() and np.abs(want).max() > 1e-6 * gmax:
-                rel = np.abs(got[big] - want[big]) / np.abs(want[big])
-                assert rel.max() <= MIXED_BIG_RTOL, ("grad (large elements) " + k, float(rel.max()), int(big.sum()))
-            assert abs(sq_e[k] - sq_o[k]) <= MIXED_SQNORM_RTOL * sq_o[k] + 1e-12, ("sqnorm", k, sq_e[k], sq_o[k])
-        else:
-            close(g_e[k], want, name="grad " + k, atol_scale=atol_scale)
-            assert abs(sq_e[k] - sq_o[k]) <= 2e-3 * sq_o[k] + 1e-12, ("sqnorm", k, sq_e[k], sq_o[k])
-
-
 @pytest.mark.parametrize("scoring", ["f32", "bf16x3", "bf16x3-mixed"])
 @pytest.mark.parametrize("N,H,Ht,B,T,K", CASES)
 def test_step_matches_oracle(N, H, Ht, B, T, K, scoring):
@@ -466,33 +372,10 @@ def test_dp_engine_single_rank_path_matches_oracle():
 
 
 # ----------------------------------------------------------------------------------------- split-bf16 GEMM
-def ptr2(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _kb32_index(rows, inner):
-    """numpy restatement of csrc/tcar_bf16_layout.h: flat element offset of every (row, k)."""
-    r = np.arange(rows)[:, None]
-    k = np.arange(inner)[None, :]
-    blk = (r >> 7) * (inner // 32) + (k >> 5)
-    rr, kk = r & 127, k & 31
-    return blk * 4096 + rr * 32 + ((((kk >> 3) ^ ((rr >> 2) & 3)) << 3) | (kk & 7))
-
-
-def _planes(lib, x):
-    """fp32 [rows, cols] -> KB32 hi / lo planes through the product's own tcar_split_bf16; returns (hi, lo, inner, rows)."""
-    rows, cols = x.shape
-    inner = (cols + 31) // 32 * 32
-    rp = (rows + 127) // 128 * 128
-    xd = torch.tensor(np.ascontiguousarray(x)).cuda()
-    hi = torch.full((rp * inner,), float("nan"), dtype=torch.bfloat16, device="cuda")
-    lo = torch.full((rp * inner,), float("nan"), dtype=torch.bfloat16, device="cuda")
-    assert lib.tcar_split_bf16(ptr(xd), cols, rows, cols, ptr2(hi), ptr2(lo), inner, None, None, 0, 0, 0, None) == 0
-    return hi, lo, inner, rows
-
-
 @pytest.mark.parametrize("M,N,K,nsplit,K2", [(300, 1000, 64, 3, 0), (77, 129, 96, 3, 0), (512, 46033, 832, 3, 0), (130, 5000, 832, 1, 0),
                                              (300, 1000, 64, 3, 139), (77, 129, 512, 3, 160), (512, 46033, 512, 3, 139)])
+
+
 def test_logits_gemm_softmax_epilogue(lib, M, N, K, nsplit, K2):
     """tcar_gemm_bf16_ce + tcar_ce_finish (model_combine.py:138,145 without materialised logits): per-group (max, sum) statistics,
     the label's score, the cross entropy, and the in-place rescaled plane softmax - onehot against fp64 — on every workgroup
@@ -1055,7 +938,6 @@ def test_schedule_switches_agree_bitwise_with_the_default_schedule():
             assert np.abs(base[0] - run[0]).max() <= tol * np.abs(base[0]).max(), (sw, np.abs(base[0] - run[0]).max())
 
 
-
 def test_anchored_softmax_form_in_the_step():
     """Round 6: the fused step at the benched size takes the ANCHORED softmax form (no rescale pass over the [B, N] plane).
       * the form is on for every batch (full ones and a 500-session tail batch) and off under TCAR_FUSED_CE = 1;
@@ -1242,6 +1124,8 @@ def test_split_bf16_planes_kb32_layout(lib):
 @pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("M,N,K", [(512, 300, 832), (130, 129, 64), (64, 832, 2080), (257, 576, 512), (5, 7, 32),
                                    (600, 260, 96)])
+
+
 def test_gemm_bf16_layouts(lib, layout, nsplit, M, N, K):
     """All three operand layouts (swizzled b128 fragments and ds_read_b64_tr_b16 transposed fragments, staged by
     direct-to-LDS DMA) against fp64; asymmetric random operands (a swapped row/col map cannot pass)."""
@@ -1758,6 +1642,8 @@ def test_gather_forward_throughput_form_equals_latency_form(lib, B, T, H, Ht):
 @pytest.mark.parametrize("B,T,K,N,ldh", [(512, 2, 20, 3000, 256), (64, 40, 7, 50, 256), (300, 5, 0, 100000, 256), (1, 1, 3, 10, 256),
                                          (2048, 40, 2, 500, 256), (512, 32, 33, 2, 256), (128, 3, 4, 1_000_000, 512),
                                          (4096, 4, 1, 70000, 320), (1024, 40, 20, 70000, 256), (1024, 20, 0, 5000, 256)])
+
+
 def test_sorted_segmented_item_scatter(lib, B, T, K, N, ldh):
     """tcar_segsum_*: the item-row gradients of the gathers (mode 0) and of the negatives (mode 1) added into the dense
     gradient by sort + segmented sum — head-heavy ids (runs of hundreds: multi-chunk runs), against np.add.at in fp64, the
@@ -1830,10 +1716,11 @@ def test_sorted_segmented_item_scatter(lib, B, T, K, N, ldh):
         assert np.array_equal(o[0], outs[0][0]) and np.array_equal(o[1], outs[0][1])        # bit for bit
 
 
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,T,k,N,ncat", [(64, 1, 20, 500, 7), (200, 7, 20, 46033, 40), (5, 40, 20, 30, 3), (33, 3, 20, 12, 2),
                                           (257, 2, 20, 1000, 1), (16, 5, 64, 3000, 500)])
+
+
 def test_eval_diversity_kernel_equals_the_reference_loops(lib, B, T, k, N, ncat):
     """tcar_eval_diversity (ILD / unexp pair counts + the coverage map, model_combine.py:174-194,301-313) against the oracle's
     literal double loops (oracle/metrics_oracle.py: getILD / getUnexp restated line by line) on random top-k lists: few
@@ -1883,6 +1770,8 @@ def _bf(x):
 #  of round 6 on 192- / 128-row tiles, 1922 / 2562 = the double-buffered 192- / 256-row tiles under their A/B codes)
 @pytest.mark.parametrize("N,B,tile", [(3000, 100, 0), (46033, 512, 0), (46033, 512, 256), (46033, 512, 128), (5754, 600, 64), (700, 33, 0),
                                       (46033, 512, 1923), (3000, 100, 1923), (5754, 600, 1283), (46033, 512, 2562), (700, 33, 1922)])
+
+
 def test_onehot_gradient_gemms_and_candidate_time_backward(lib, N, B, tile):
     """The one-hot form of the two scoring GRADIENT GEMMs (round 4) at op level, through the C-ABI, against fp64 numpy on the
     bf16-rounded operands AND against the materialised form it replaces:

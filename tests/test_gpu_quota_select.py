@@ -22,7 +22,7 @@ import torch
 import tcar_amd  # noqa: F401
 
 from select_ref import capped_walk
-from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

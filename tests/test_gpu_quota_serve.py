@@ -1,5 +1,5 @@
 """Per-category caps at the engine level (TcarEngine.eval_step_streamed / recommend with max_per_category=, tcar_serve_step_quota) and
-through Seq2SeqAttNN.test() with cat_cap, on the small engine and fold of test_gpu_window_serve.py.
+through Seq2SeqAttNN.test() with cat_cap, on the small engine and fold of tests/window_case.py.
 
 The engine check needs no tolerance: recommend(k=64) returns the 64 best items of a session and their score bits; every other item
 scores lower, so the capped walk over those 64 — as long as it yields k items — is the capped list of the whole catalog."""
@@ -8,32 +8,11 @@ import pytest
 
 import tcar_amd  # noqa: F401
 
-from select_ref import capped_walk
-from select_util import _need_gpu
-from test_gpu_window_serve import B, N, PANEL, reference, run_test, trained
+from gpu_util import _need_gpu
+from quota_case import CAT, K, M, walk_of_the_best_64
+from window_case import B, N, PANEL, reference, run_test, trained
 
 pytestmark = pytest.mark.gpu
-
-K, M = 10, 2
-CAT = (np.arange(N) % 8).astype(np.int32)
-CAT.setflags(write=False)
-
-
-def walk_of_the_best_64(tk64, sc64):
-    """the capped lists (ids, score bits) that follow from the uncapped 64 best of every session"""
-    ids_out, sc_out = [], []
-    for b in range(tk64.shape[0]):
-        ids = tk64[b][tk64[b] >= 0].astype(np.int64)
-        assert len(ids) == 64, b                                    # 64 items, so everything else scores lower
-        s = np.full(N, -np.inf, np.float32)
-        s[ids] = sc64[b, :len(ids)]
-        el = np.zeros(N, bool)
-        el[ids] = True
-        want = capped_walk(s, CAT, K, M, el)
-        assert len(want) == K, (b, want)                            # the precondition: the walk is over before the 64 are
-        ids_out.append(want)
-        sc_out.append(s[want])
-    return np.array(ids_out, np.int32), np.array(sc_out, np.float32)
 
 
 @pytest.mark.parametrize("scoring", ["f32", "bf16x3-mixed"])

@@ -1,6 +1,6 @@
 """The ragged gather and the ragged attention pools at the op level (include/tcar_ragged.h: tcar_gather_clip_fwd_ragged,
 tcar_attn_pool_fwd_ragged, tcar_attn_pool_fwd_slabs_ragged) against their rectangular twins, at the shape of
-test_gpu_serve.reference(): N = 700, H = 250, Ht = 64, B = 41.
+serve_case.reference(): N = 700, H = 250, Ht = 64, B = 41.
 
 One wave owns a session in both forms and runs the same operations on the same rows in the same order, and the gather is per row:
 every session of the mix must carry the BITS the rectangular launch gives the sub-batch of its length — no band."""
@@ -13,8 +13,8 @@ import torch
 import tcar_amd  # noqa: F401
 
 from ragged_util import MIX_SMALL, SET, group, offsets, random_ragged
-from select_util import _need_gpu, ptr
-from test_gpu_serve import B, reference
+from gpu_util import _need_gpu, ptr
+from serve_case import B, reference
 
 pytestmark = pytest.mark.gpu
 

@@ -1,6 +1,6 @@
 """Ragged batches at the engine level (include/tcar_ragged.h; TcarEngine.eval_step_streamed / recommend / retrieve /
 recommend_two_stage / score_candidates on a feed with "len"), through Seq2SeqAttNN and through test() with --eval_mixed, at the
-shape of test_gpu_serve.reference(): N = 700, H = 250, Ht = 64, B = 41, panel 256, k = 20.
+shape of serve_case.reference(): N = 700, H = 250, Ht = 64, B = 41, panel 256, k = 20.
 
 Uniform lengths and permutations are held bit for bit; mixed lengths against the fp64 oracle (eval_batch per length group, rows put
 back in session order) in exactly the bands the rectangular tests use — delta_b = 1e-3 * max_n |s[b, n]|, no session and no item
@@ -15,16 +15,16 @@ import torch
 import tcar_amd  # noqa: F401
 
 from ragged_util import mixed_reference, own_items, permuted, random_ragged
-from select_util import _need_gpu, close
-from test_gpu_cand_serve import C_, _lists
-from test_gpu_retrieve_serve import SHORT, U, _kb32_index
-from test_gpu_serve import B, N, PANEL, TOPK, check_band, reference
+from gpu_util import _need_gpu, _np, close
+from quota_case import CAT, K, M, walk_of_the_best_64
+from serve_case import B, C_, N, PANEL, SHORT, TOPK, _lists, reference
+from serve_case import beta_of_engine as _beta
+from serve_shapes_ref import check_band
+from window_case import check_band as check_pool
+from window_case import check_eval
+from window_case import reference as wref
 
 pytestmark = pytest.mark.gpu
-
-
-def _np(*ts):
-    return [t.cpu().numpy().copy() for t in ts]
 
 
 def _engine(scoring):
@@ -78,15 +78,6 @@ def test_uniform_lengths_give_the_bits_of_the_rectangular_calls(scoring):
         _same_bits(got, want, name)
         assert np.isfinite(want["attout"][0]).all() and (want["eval"][1] >= 0).all()
     eng.check_forks()
-
-
-def _beta(eng, delta):
-    """the band of a coarse score (test_gpu_retrieve_serve): u (|A| |E|^T) + delta_b from the operands the engine scored"""
-    g = eng.geo
-    A = eng.attout[:B].cpu().numpy().astype(np.float64)
-    idx = torch.tensor(_kb32_index(eng.e16h.shape[0], g.ek)[:N], device=eng.dev)
-    E = (eng.e16h.flatten()[idx].double() + eng.e16l.flatten()[idx].double()).cpu().numpy()
-    return U * (np.abs(A) @ np.abs(E).T) + delta[:, None]
 
 
 @pytest.mark.parametrize("mix", ["small", "long"])
@@ -211,8 +202,6 @@ def test_a_permutation_of_the_sessions_permutes_the_results_bit_for_bit(scoring)
 
 def test_window_cap_and_exclusions_carry_over_to_a_mixed_batch():
     _need_gpu()
-    from test_gpu_quota_serve import CAT, K, M, walk_of_the_best_64
-    from test_gpu_window_serve import check_band as check_pool, check_eval, reference as wref
     m = mixed_reference("small")
     feed, s, delta, lab = m["feed"], m["s"], m["delta"], m["feed"]["label"]
     free = _unlabelled(feed)

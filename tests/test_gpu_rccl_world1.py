@@ -19,12 +19,13 @@ noise, which Adam amplifies step by step: the first 40 steps are held to 5e-3 of
 
 The child process owns the process group: the pytest process never initialises one."""
 import os
-import socket
 import subprocess
 import sys
 
 import pytest
 import torch
+
+from dist_util import _free_port
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -43,7 +44,7 @@ import tcar_amd  # noqa: F401
 from tcar_amd.dp import DPEngine, preflight
 from tcar_amd.engine import TcarEngine
 from tcar_amd.sharded import ShardedEngine
-from test_gpu_parity import _case
+from step_cases import _case
 
 caps = preflight(dist.group.WORLD, "cuda:0", verbose=False)
 assert caps["backend"] == "nccl" and caps["world"] == 1 and caps["reduce_scatter"], caps
@@ -133,14 +134,6 @@ torch.cuda.synchronize()
 dist.destroy_process_group()
 print("RESULT " + json.dumps(out))
 '''
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _run(mode, steps):

@@ -14,7 +14,7 @@ import tcar_amd  # noqa: F401
 
 from retrieve_merge_ref import merge_shortlists
 from retrieve_ref import shortlist
-from select_util import lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

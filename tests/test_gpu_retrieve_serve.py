@@ -1,5 +1,5 @@
 """Retrieval and the two-stage call at the engine level (TcarEngine.retrieve / recommend_two_stage; tcar_retrieve_step /
-tcar_retrieve_rerank_step) on the reference setup of tests/test_gpu_serve.py: N = 700, B = 41, PANEL = 256.
+tcar_retrieve_rerank_step) on the reference setup of tests/serve_case.py: N = 700, B = 41, PANEL = 256.
 
 Where the coarse precision is the engine's own (scoring "bf16": the hi planes; "f32") the panel GEMM is the one recommend() runs and
 only the selector differs: the lists must be equal bit for bit.  On "bf16x3-mixed" the coarse scores come from the hi planes alone and
@@ -23,29 +23,12 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from select_util import _need_gpu, close
-from test_gpu_serve import B, N, PANEL, TOPK, check_band, reference
+from gpu_util import _kb32_index, _need_gpu, _np, close
+from serve_case import B, N, PANEL, SHORT, TOPK, _feed, _keys_and_windows, reference
+from serve_case import beta_of_operands as _beta
+from serve_shapes_ref import check_band
 
 pytestmark = pytest.mark.gpu
-
-U = 2.0 ** -8
-SHORT = 128
-
-
-def _np(*ts):
-    return [t.cpu().numpy().copy() for t in ts]
-
-
-def _feed():
-    return {n: v for n, v in reference()["batch"].items() if n not in ("label", "neg")}
-
-
-def _keys_and_windows():
-    rng = np.random.RandomState(31)
-    keys = rng.permutation(N).astype(np.int32)
-    lo = rng.randint(0, 300, B).astype(np.int32)
-    hi = (lo + rng.randint(30, 400, B)).astype(np.int32)              # pools of 30 .. 400 items: some shorter than 64
-    return keys, lo, hi
 
 
 @pytest.mark.parametrize("scoring", ["bf16", "f32"])
@@ -72,15 +55,6 @@ def test_retrieve_equals_recommend_where_the_coarse_precision_is_the_engines_own
         if "window" in name:
             assert (~live).any() and live.any()
     eng.check_forks()
-
-
-def _kb32_index(rows, inner):
-    """csrc/tcar_bf16_layout.h: flat element offset of every (row, k) of a KB32 plane"""
-    r = np.arange(rows)[:, None]
-    k = np.arange(inner)[None, :]
-    blk = (r >> 7) * (inner // 32) + (k >> 5)
-    rr, kk = r & 127, k & 31
-    return blk * 4096 + rr * 32 + ((((kk >> 3) ^ ((rr >> 2) & 3)) << 3) | (kk & 7))
 
 
 _MIXED = {}
@@ -114,11 +88,6 @@ def mixed():
     m["logits_nan"] = bool(torch.isnan(eng.logits).all())
     eng.check_forks()                                                                                     # (g)
     return m
-
-
-def _beta(m):
-    r = reference()
-    return U * (np.abs(m["A"]) @ np.abs(m["E"]).T) + r["delta"][:, None]
 
 
 def test_the_read_back_operands_are_the_oracles(mixed):

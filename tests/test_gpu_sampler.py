@@ -10,12 +10,9 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+from gpu_util import _need_gpu
+
 pytestmark = pytest.mark.gpu
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def _engine(fold, H=32, Ht=16):

@@ -1,6 +1,6 @@
-"""tcar_select_merge at the op level (include/tcar_serve_shard.h), exactly: the columns of the matrices of test_gpu_select are cut into S
+"""tcar_select_merge at the op level (include/tcar_serve_shard.h), exactly: the columns of the matrices of select_case are cut into S
 pieces, every piece is folded into its OWN state with the existing fold calls, and the S states are merged and finished.  The list, its
-scores and the rank must be the bits of the single-state run and of numpy; ce follows the repartitioned sum (test_gpu_select.close) and
+scores and the rank must be the bits of the single-state run and of numpy; ce follows the repartitioned sum (gpu_util.close) and
 is the same bits on every run."""
 import ctypes as C
 
@@ -10,8 +10,9 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+from gpu_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
+from select_case import KS, PANELS, case, check_lists, run
 from select_ref import capped_walk
-from test_gpu_select import KS, PANELS, case, check_lists, close, lib, ptr, run  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -12,40 +12,11 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from select_util import _need_gpu, close
-from serve_shapes_ref import check_band  # noqa: F401  (rules (a)-(d); the tests of the other serving calls import it from here)
+from gpu_util import _need_gpu, close
+from serve_case import B, N, PANEL, TOPK, reference
+from serve_shapes_ref import check_band  # rules (a)-(d)
 
 pytestmark = pytest.mark.gpu
-
-N, H, Ht, B, T, K = 700, 250, 64, 41, 3, 5        # the shape of test_python_sequenced_op_level_path_matches_the_cpp_driver
-PANEL, TOPK = 256, 20                             # three panels, the last one partial
-
-
-_REF = {}
-
-
-def reference():
-    """inputs and the oracle's fp64 logits / CE: computed once, shared, never written"""
-    if not _REF:
-        from oracle.tcar_oracle import TcarOracle, init_params_numpy
-        rng = np.random.RandomState(17)
-        params = init_params_numpy(N, H, Ht, 0.35, 0.12, rng)
-        content = (rng.standard_normal((N + 1, H)) * 0.5).astype(np.float32)
-        content[0] = 0
-        mw = np.stack([rng.randint(1, 13, N), rng.randint(1, 32, N), rng.randint(1, 8, N), rng.randint(1, 25, N),
-                       rng.randint(1, 61, N)], -1).astype(np.int32)
-        b = {"seq": rng.randint(1, N + 1, (B, T)), "label": rng.randint(0, N, B), "pm": rng.randint(1, 13, (B, T)),
-             "pd": rng.randint(1, 32, (B, T)), "pw": rng.randint(1, 8, (B, T)), "ph": rng.randint(1, 25, (B, T)),
-             "pmi": rng.randint(1, 61, (B, T)), "cw": rng.randint(0, 7, B), "ch": rng.randint(0, 24, B),
-             "gap": rng.randint(0, 12, (B, T)), "neg": rng.randint(0, N, (B, K))}
-        b = {k: v.astype(np.int32) for k, v in b.items()}
-        b["seq"][0, 1] = b["seq"][0, 0]
-        logits, ce = TcarOracle(params, content, mw).eval_batch(b)
-        s, ce = logits.numpy().astype(np.float64), ce.numpy().astype(np.float64)
-        for a in list(b.values()) + [s, ce]:
-            a.setflags(write=False)
-        _REF.update(params=params, content=content, mw=mw, batch=b, s=s, ce=ce, delta=1e-3 * np.abs(s).max(1))
-    return _REF
 
 
 @pytest.mark.parametrize("scoring", ["f32", "bf16x3-mixed"])

@@ -50,15 +50,11 @@ import torch
 import tcar_amd  # noqa: F401
 
 import serve_shapes_ref as R
-from select_util import _need_gpu, close
+from gpu_util import _need_gpu, _np, close
 
 pytestmark = pytest.mark.gpu
 
 K = R.TOPK
-
-
-def _np(*ts):
-    return [t.cpu().numpy().copy() for t in ts]
 
 
 def _engine(name, scoring):

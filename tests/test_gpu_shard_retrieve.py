@@ -1,13 +1,13 @@
 """Retrieval, candidate scoring and the two-stage call of the catalog-sharded engine (ShardedEngine.shard_retrieve /
-shard_recommend_two_stage / shard_score_candidates, include/tcar_retrieve_shard.h) on the inputs, helpers and split sizes of
-test_gpu_shard_serve: W engines ShardedEngine(world=W, rank=r) in ONE process without a process group, the collectives of
+shard_recommend_two_stage / shard_score_candidates, include/tcar_retrieve_shard.h) on the inputs of serve_case and the helpers and
+split sizes of shard_case: W engines ShardedEngine(world=W, rank=r) in ONE process without a process group, the collectives of
 ShardExchange.retrieve / .candidates played by hand (all-gather = concatenation in rank order, all-to-all = every rank takes its own
 rows of every rank's buffer), the variables those after two training steps.
 
 The merged shortlist is held against the numpy merge (retrieve_merge_ref) of the W shard states bit for bit, the combined exact scores
 against the owners' parts bit for bit, and both against the fp64 oracle of the trained variables in the bands of
-test_gpu_retrieve_serve: its coarse band `_beta` is taken from there as it is, over the operands read back from the W engines, with the
-logits gate delta_b of the TRAINED variables' oracle in the place of the untrained one's.
+test_gpu_retrieve_serve: its coarse band (serve_case.beta_of_operands, `_beta` here) is taken as it is, over the operands read back
+from the W engines, with the logits gate delta_b of the TRAINED variables' oracle in the place of the untrained one's.
 
 No bit equality is asserted between different W or against TcarEngine: a rank's session forward runs at its local batch size, and
 the projections change their split-K form with the row count, so attout may differ in the last bit."""
@@ -15,7 +15,6 @@ import ctypes as C
 import io
 import os
 import random
-import sys
 from contextlib import redirect_stdout
 
 import numpy as np
@@ -24,67 +23,19 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from cand_ref import rank_model  # noqa: E402
-from retrieve_merge_ref import merge_shortlists  # noqa: E402
-from select_util import _need_gpu, close  # noqa: E402
-from test_gpu_retrieve_serve import _beta, _kb32_index  # noqa: E402
-from test_gpu_serve import B, N, T, TOPK, check_band, reference  # noqa: E402
-from test_gpu_shard_serve import PANEL, _free_port, engines, split, trained  # noqa: E402
+from cand_ref import rank_model
+from dist_util import launch
+from gpu_util import _kb32_index, _need_gpu, _np, close
+from retrieve_merge_ref import merge_shortlists
+from serve_case import B, N, T, TOPK, _feed, reference
+from serve_case import beta_of_operands as _beta
+from serve_shapes_ref import check_band
+from shard_case import PANEL, engines, play_candidates, play_retrieve, split, trained
 
 pytestmark = pytest.mark.gpu
 
 CS = (64, 200, 1024)
 METRIC_RTOL = 1e-4           # >= C 2^-24 at C = 1024: the bound of an fp32 sum of C positive terms (test_gpu_cand_rank)
-
-
-def _np(*ts):
-    return [t.cpu().numpy().copy() for t in ts]
-
-
-def _feed():
-    return {n: v for n, v in reference()["batch"].items() if n not in ("label", "neg")}
-
-
-def _rows(t, r, cap):
-    """what rank r receives of an all-to-all over the ranks' buffers t [W, W*cap, x]: its own rows of every rank's buffer"""
-    return t[:, r * cap:(r + 1) * cap].contiguous()
-
-
-def play_retrieve(pcs, rerank):
-    """ShardExchange.retrieve with the collectives played by hand -> (states [W, W*cap, 2C+4], the W shortlists (ids, coarse) over
-    all cap rows, parts [W, W*cap, C] or None, per rank (topk, scores, exact [cap, C]) or None)"""
-    cap = pcs[0].cap
-    head_all = torch.cat([pc.begin().clone() for pc in pcs])
-    for pc in pcs:
-        pc.prepare(head_all)
-    states = torch.stack([pc.fold().clone() for pc in pcs])
-    ids = [pc.merge(_rows(states, r, cap)).clone() for r, pc in enumerate(pcs)]
-    short = [(i, pc.eng.rs_scores[:cap].clone()) for i, pc in zip(ids, pcs)]
-    parts = outs = None
-    if rerank:
-        lists = torch.cat(ids)
-        parts = torch.stack([pc.scores(lists).clone() for pc in pcs])
-        outs = []
-        for r, pc in enumerate(pcs):
-            topk, sc = pc.rerank(_rows(parts, r, cap))
-            outs.append((topk.clone(), sc.clone(), pc.eng.rs_exact[:cap].clone()))
-    torch.cuda.synchronize()
-    return states, short, parts, outs
-
-
-def play_candidates(pcs):
-    cap = pcs[0].cap
-    head_all = torch.cat([pc.begin().clone() for pc in pcs])
-    for pc in pcs:
-        pc.prepare(head_all)
-    lists = torch.cat([pc.lists().clone() for pc in pcs])
-    parts = torch.stack([pc.scores(lists).clone() for pc in pcs])
-    outs = [tuple(None if o is None else o.clone() for o in pc.rank(_rows(parts, r, cap))) for r, pc in enumerate(pcs)]
-    torch.cuda.synchronize()
-    return lists, parts, outs
 
 
 def finished(eng, state, C_):
@@ -100,7 +51,7 @@ def finished(eng, state, C_):
 
 def operands(engs, edges):
     """the operands the engines scored, read back: A = the local sessions' fp32 attout rows in batch order, E = hi + lo of every
-    shard's planes in catalog order (test_gpu_retrieve_serve: the `mixed` fixture)"""
+    shard's planes in catalog order (as the `mixed` fixture of test_gpu_retrieve_serve reads them)"""
     A = np.concatenate([e.attout[:edges[r + 1] - edges[r]].cpu().numpy().astype(np.float64) for r, e in enumerate(engs)])
     E = []
     for e in engs:
@@ -110,7 +61,7 @@ def operands(engs, edges):
 
 
 def band(engs, edges, t):
-    """_beta of test_gpu_retrieve_serve over the read-back operands, its logits gate that of the trained variables' oracle"""
+    """the coarse band of test_gpu_retrieve_serve (`_beta`) over the read-back operands, its logits gate that of the trained variables' oracle"""
     return _beta(operands(engs, edges)) - reference()["delta"][:, None] + t["delta"][:, None]
 
 
@@ -381,12 +332,9 @@ def _worker(rank, world, port, ret, scoring):
 
 def test_two_ranks_over_gloo_give_the_bits_of_the_two_engines_in_one_process():
     _need_gpu()
-    import torch.multiprocessing as mp
     from tcar_amd.sharded import ShardedEngine
     scoring, world = "bf16x3-mixed", 2
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, scoring), nprocs=world, join=True)
+    ret = launch(_worker, world, scoring, spawned_manager=True)
     for rk in range(world):
         assert isinstance(ret.get(rk), dict), ret.get(rk)
     print("all_to_all_rows over gloo on device tensors: %s" % ret[0]["path"])

@@ -1,5 +1,6 @@
 """Streamed evaluation and recommendation of the catalog-sharded engine (ShardedEngine.eval_step_streamed / recommend,
-include/tcar_serve_shard.h) on the inputs and bands of test_gpu_serve.
+include/tcar_serve_shard.h) on the inputs of serve_case and the bands of test_gpu_serve;
+the engines, the split and the played collectives are those of shard_case.
 
 W engines ShardedEngine(world=W, rank=r) run in ONE process without a process group; the test plays the three collectives of
 ShardExchange.serve by concatenating the ranks' buffers between the pieces.  The variables are those after two training steps (trained on
@@ -7,12 +8,9 @@ a one-rank sharded engine and loaded into the W engines, whose candidate-time pl
 them).  The merged result is held against the numpy merge (select_ref) of the W shard states bit for bit, and against the fp64 oracle of
 the trained variables in the bands of test_gpu_serve."""
 import copy
-import ctypes as C
 import io
 import os
 import random
-import socket
-import sys
 from contextlib import redirect_stdout
 
 import numpy as np
@@ -21,101 +19,14 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-
-from select_ref import merge_states  # noqa: E402
-from select_util import _need_gpu  # noqa: E402
-from test_gpu_serve import B, N, T, TOPK, check_band, close, reference  # noqa: E402
+from dist_util import launch
+from gpu_util import _need_gpu, close
+from select_ref import merge_states
+from serve_case import B, N, T, TOPK, reference
+from serve_shapes_ref import check_band
+from shard_case import PANEL, engines, play, shard_states, split, trained
 
 pytestmark = pytest.mark.gpu
-
-PANEL = 128                                     # shards of 384 / 316 rows (W = 2) and 256 / 256 / 188 (W = 3): several panels each, the last partial
-SPLITS = {2: ([25, 16], 27), 3: ([20, 0, 21], 23)}       # sessions per rank (uneven, one rank with none at W = 3), cap > the largest
-
-
-_TRAINED = {}
-
-
-def trained(scoring):
-    """the variables after two training steps on identical batches + the fp64 oracle's logits / CE of them: computed once per scoring
-    mode, shared, never written"""
-    if scoring not in _TRAINED:
-        from oracle.tcar_oracle import TcarOracle
-        from tcar_amd.sharded import ShardedEngine
-        r = reference()
-        eng = ShardedEngine(r["params"], r["content"], r["mw"], max_grad=2.0, scoring=scoring, world=1, rank=0)
-        for _ in range(2):
-            eng.train_step(r["batch"])
-        state = eng.export_state()
-        params = eng.export_params()
-        logits, ce = TcarOracle(params, r["content"], r["mw"]).eval_batch(r["batch"])
-        s, ce = logits.numpy().astype(np.float64), ce.numpy().astype(np.float64)
-        rng = np.random.RandomState(23)
-        keys = rng.randint(0, 1000, N).astype(np.int32)
-        cat = rng.randint(0, 12, N).astype(np.int32)
-        for a in (s, ce, keys, cat):
-            a.setflags(write=False)
-        _TRAINED[scoring] = dict(state=state, s=s, ce=ce, delta=1e-3 * np.abs(s).max(1), keys=keys, cat=cat)
-    return _TRAINED[scoring]
-
-
-def engines(scoring, W):
-    from tcar_amd.sharded import ShardedEngine
-    r, t = reference(), trained(scoring)
-    out = []
-    for rank in range(W):
-        e = ShardedEngine(r["params"], r["content"], r["mw"], max_grad=2.0, scoring=scoring, world=W, rank=rank)
-        e.load_state(t["state"])
-        assert e._time_dirty                                  # the candidate-time planes of the shard are stale
-        e.set_item_keys(t["keys"])
-        e.set_categories(t["cat"])
-        out.append(e)
-    return out
-
-
-def split(batch, W):
-    sizes, cap = SPLITS[W]
-    edges = np.r_[0, np.cumsum(sizes)]
-    subs = [({k: v[a:b] for k, v in batch.items()} if b > a else None) for a, b in zip(edges[:-1], edges[1:])]
-    return subs, edges, cap
-
-
-def play(pcs):
-    """ShardExchange.serve with the collectives played by hand: all-gather = concatenation of the ranks' buffers in rank order"""
-    head_all = torch.cat([pc.begin().clone() for pc in pcs])
-    parts = [pc.prepare(head_all) for pc in pcs]
-    if pcs[0].labelled:
-        parts_all = torch.stack([p.clone() for p in parts])
-        for pc in pcs:
-            pc.label_scores(parts_all)
-    states = torch.stack([pc.fold().clone() for pc in pcs])
-    outs = [tuple(o.clone() for o in pc.finish(states)) for pc in pcs]
-    torch.cuda.synchronize()
-    return head_all, states, outs
-
-
-def shard_states(eng, states, k):
-    """every shard's state of every gathered session, read through tcar_select_finish -> select_ref states [W][Bq]"""
-    W, Bq, rw = states.shape
-    out = []
-    for w in range(W):
-        topk = torch.empty(Bq, k, dtype=torch.int32, device="cuda")
-        score = torch.zeros(Bq, k, device="cuda")
-        rank = torch.zeros(Bq, dtype=torch.int32, device="cuda")
-        st = states[w].contiguous()
-        assert eng.lib.tcar_select_finish(Bq, k, C.c_void_p(st.data_ptr()), None, C.c_void_p(topk.data_ptr()), C.c_void_p(score.data_ptr()),
-                                          C.c_void_p(rank.data_ptr()), None, None) == 0
-        torch.cuda.synchronize()
-        tk, sc, cnt = topk.cpu().numpy(), score.cpu().numpy(), rank.cpu().numpy() - 1
-        ms = st[:, 2 * k + 1:2 * k + 3].contiguous().view(torch.float32).cpu().numpy()
-        row = []
-        for b in range(Bq):
-            n = int((tk[b] >= 0).sum())
-            assert (tk[b, n:] == -1).all()
-            row.append({"ids": tk[b, :n].tolist(), "scores": sc[b, :n].copy(), "count": int(cnt[b]), "m": float(ms[b, 0]), "s": float(ms[b, 1])})
-        out.append(row)
-    return out
 
 
 @pytest.mark.parametrize("W", [2, 3])
@@ -220,14 +131,6 @@ def test_one_rank_without_collectives_gives_the_bits_of_the_pieces_called_by_han
     assert (tk.cpu().numpy() == got[1]).all() and sc.cpu().numpy().tobytes() == got[3].tobytes()
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def _worker(rank, world, port, ret, scoring):
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
@@ -258,12 +161,9 @@ def _worker(rank, world, port, ret, scoring):
 
 def test_two_ranks_over_gloo_give_the_bits_of_the_two_engines_in_one_process():
     _need_gpu()
-    import torch.multiprocessing as mp
     from tcar_amd.sharded import ShardedEngine
     scoring, world = "bf16x3-mixed", 2
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, scoring), nprocs=world, join=True)
+    ret = launch(_worker, world, scoring, spawned_manager=True)
     for rk in range(world):
         assert isinstance(ret.get(rk), dict), ret.get(rk)
     r = reference()

@@ -8,7 +8,6 @@
 * the packed exchange rows (tcar_shard_pack_head / _unpack_head / _pack_ids, tcar_scatter_add_rows_packed) and the
   fixed-order dense norm at op level."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -19,25 +18,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from dist_util import launch  # noqa: E402
+from gpu_util import close  # noqa: E402
+from step_cases import _case, check_grads, rel_norm  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 # (N, H, Ht, B, T).  ldh = 256: the click-query input gradient of the session backward is the whole-row launch; ldh = 64 (a row of
-# test_gpu_parity.CASES): its small-GEMM form.  Both have ldt = 64: the mixed shard takes its one-hot form at either (_score_form)
+# step_cases.CASES): its small-GEMM form.  Both have ldt = 64: the mixed shard takes its one-hot form at either (_score_form)
 _GEO_LDH256, _GEO_LDH64 = (1000, 250, 64, 33, 5), (1000, 40, 16, 3, 40)
 
 
 @pytest.mark.parametrize("K,scoring,geometry",
                          [pytest.param(K, sc, _GEO_LDH256, id="%d-%s" % (K, sc)) for sc in ("bf16x3", "bf16x3-mixed") for K in (7, 0)] +
                          [pytest.param(K, sc, _GEO_LDH64, id="%d-%s-ldh64" % (K, sc)) for sc in ("bf16x3", "bf16x3-mixed") for K in (7, 0)])
+
+
 def test_single_rank_sharded_path_matches_oracle(K, scoring, geometry):
     """bf16x3: materialised logits of the shard; bf16x3-mixed (the benchmarked precision): the shard runs the single-GPU schedule —
     softmax epilogue with a label window, one-hot time segment, (q, z) form of dE, dP form of dX — between the same exchanges"""
@@ -46,7 +43,6 @@ def test_single_rank_sharded_path_matches_oracle(K, scoring, geometry):
     import tcar_amd  # noqa: F401
     from oracle.tcar_oracle import TcarOracle
     from tcar_amd.sharded import ShardedEngine
-    from test_gpu_parity import _case, check_grads, close
     N, H, Ht, B, T = geometry
     params, content, mw, batch = _case(N, H, Ht, B, T, max(K, 1), seed=321)
     if K == 0:
@@ -86,7 +82,6 @@ def test_single_rank_sharded_split_update_matches_the_update_inside_the_step(sco
         pytest.skip("no GPU")
     import tcar_amd  # noqa: F401
     from tcar_amd.sharded import ShardedEngine
-    from test_gpu_parity import _case
     N, H, Ht, B, K = 3000, 250, 64, 48, 5
     params, content, mw, b0 = _case(N, H, Ht, B, 3, K, seed=11)
     batches = [b0] + [_case(N, H, Ht, B, T, K, seed=12 + i)[3] for i, T in enumerate((1, 3, 6, 2))]
@@ -152,7 +147,6 @@ def test_single_rank_sharded_anchored_form_matches_oracle():
     import tcar_amd  # noqa: F401
     from oracle.tcar_oracle import TcarOracle
     from tcar_amd.sharded import ShardedEngine
-    from test_gpu_parity import _case, check_grads, close, rel_norm
     N, H, Ht, B, T, K = 3000, 250, 64, 253, 3, 7
     params, content, mw, batch = _case(N, H, Ht, B, T, K, seed=323)
     ora = TcarOracle(params, content, mw, max_grad=2.0)
@@ -184,7 +178,6 @@ def _worker(rank, world, port, ret, scoring="bf16x3", B=37):
         from tcar_amd.dp import shard_bounds
         from tcar_amd.engine import TcarEngine
         from tcar_amd.sharded import ShardedEngine
-        from test_gpu_parity import _case
         N, H, Ht, T, K = 1000, 250, 64, 4, 6                  # B = 37 sessions: uneven shards (19 + 18); 256: two whole 128-row blocks
         params, content, mw, batch = _case(N, H, Ht, B, T, K, seed=5)
         _, _, _, tiny = _case(N, H, Ht, 1, 2, K, seed=6)      # a batch of ONE session: rank 1's shard is empty
@@ -250,11 +243,8 @@ def _worker(rank, world, port, ret, scoring="bf16x3", B=37):
 def test_two_ranks_sharded_match_single_engine(scoring, B):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    import torch.multiprocessing as mp
     world = 2
-    mgr = mp.get_context("spawn").Manager()      # (a SPAWNED server: a fork of this process would inherit its GPU state)
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, scoring, B), nprocs=world, join=True)
+    ret = launch(_worker, world, scoring, B, spawned_manager=True)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 

@@ -20,7 +20,7 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from select_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +37,7 @@ _CASES = {}
 
 
 def case(N):
-    """inputs and the numpy reference of one catalog size (rows as in test_gpu_select.case, plus a row of -inf): computed once,
+    """inputs and the numpy reference of one catalog size (rows as in select_case.case, plus a row of -inf): computed once,
     shared by every k, never written"""
     if N in _CASES:
         return _CASES[N]

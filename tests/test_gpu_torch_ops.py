@@ -9,22 +9,11 @@ import torch
 
 import tcar_amd  # noqa: F401
 
+from gpu_util import _need_gpu
+from gpu_util import close_broadcast as close
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def close(got, want, rtol=1e-3, atol_scale=2e-5, name=""):
-    got = np.asarray(got.detach().cpu() if torch.is_tensor(got) else got, dtype=np.float64)
-    want = np.asarray(want.detach().cpu() if torch.is_tensor(want) else want, dtype=np.float64)
-    atol = atol_scale * max(1e-30, float(np.abs(want).max()))
-    bad = np.abs(got - want) > atol + rtol * np.abs(want)
-    assert not bad.any(), "%s: %d / %d off, max abs err %.3e (max |want| %.3e)" % (
-        name, int(bad.sum()), bad.size, float(np.abs(got - want).max()), float(np.abs(want).max()))
 
 
 def _tables(N, H, Ht, rng, scale=0.09):
@@ -407,6 +396,8 @@ def _mha_ref(queries, keys, wq, bq, wk, bk, wv, bv, h, causal):
 
 @pytest.mark.parametrize("N,T,C_,h,causal", [(5, 40, 256, 8, True), (3, 17, 128, 2, False), (4, 64, 64, 2, True),
                                                (2, 9, 48, 3, False)])
+
+
 def test_multihead_attention_block_on_the_matrix_cores(N, T, C_, h, causal):
     """head sizes 32 and 64 run the MFMA form, 16 the scalar one; padded keys / queries (all-zero rows) exercise the key and
     query masks, and one sample has EVERY key masked (the reference's softmax is then uniform over the masked keys)"""

@@ -16,7 +16,7 @@ import torch
 
 import tcar_amd  # noqa: F401
 
-from select_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
+from gpu_util import close, lib, ptr  # noqa: F401  (lib: the fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -393,3 +393,22 @@ def test_device_sampler_chunks_grow_to_the_full_size_and_tile_the_plan():
         assert [h - l for l, h in zip(lo, hi)] == want
         assert lo[0] == 0 and hi[-1] == n and lo[1:] == hi[:-1]
         assert all(0 < h - l <= max(ch, 1) for l, h in zip(lo, hi))
+
+
+def test_no_module_under_tests_imports_from_a_test_module():
+    """What two test modules share lives in a module that holds no tests (gpu_util.py, dist_util.py, the *_case.py and *_ref.py
+    modules): a test file is nobody's library, so editing one moves no other.  Every import statement of every tests/*.py is read,
+    those nested in function bodies included."""
+    import ast
+    import glob
+    found = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "tests", "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if isinstance(node, ast.Import):
+                names = [a.name for a in node.names]
+            elif isinstance(node, ast.ImportFrom):
+                names = [node.module or ""]
+            else:
+                continue
+            found += ["%s:%d imports %s" % (os.path.basename(path), node.lineno, n) for n in names if n.split(".")[-1].startswith("test_")]
+    assert not found, found

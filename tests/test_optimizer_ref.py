@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import optim_ref as R
+from gpu_util import close
 
 
 def _a_blocks(x):
@@ -140,10 +141,9 @@ def test_part_b_gates_reject_a_wrong_clip(scoring, wrong):
 
 @pytest.mark.parametrize("case", list(R.B_CASES))
 def test_evaluation_gate_rejects_a_stale_item_table(case):
-    """The evaluation behind the last update compares LOGITS at the suite's gate (test_gpu_parity.close, 1e-3): an item table left one
+    """The evaluation behind the last update compares LOGITS at the suite's gate (gpu_util.close, 1e-3): an item table left one
     update behind — everything else up to date — fails it, in every row of the table or only in the rows the last batch did not
     gather (a rest pass that never ran).  The cross-entropy alone would let the base size through (3e-4 relative)."""
-    from test_gpu_parity import close
     s = R.b_sequence(case)
     last = s["steps"][-1]
     close(R.eval_reference(s, last["state1"])[0], s["eval_logits"], name="logits")      # the reference repeats itself

@@ -1,21 +1,12 @@
 """CPU tests of the model oracle: golden fixture reproducibility, finite-difference gradient check, the
 IndexedSlices clip-norm semantics, TF-1 Adam, and data-parallel sum semantics."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import tcar_amd  # noqa: F401
 from oracle.tcar_oracle import TABLES, TcarOracle, init_params_numpy
-from helpers import GOLD
-
-
-def load_fixture():
-    z = np.load(os.path.join(GOLD, "oracle_step_small.npz"))
-    params = {k[2:]: z[k] for k in z.files if k.startswith("p/")}
-    batch = {k[2:]: z[k] for k in z.files if k.startswith("b/")}
-    return z, params, batch
+from helpers import load_fixture
 
 
 def test_oracle_reproduces_golden_fixture():

@@ -8,7 +8,6 @@ combine.
 Operands sit on a dyadic grid, so every score is exact in fp64 and in fp32 whatever the order of its sum: the shards' scores ARE the
 single process's, ties included.  The coarse scores of the first stage drop the low bits of the grid, the exact ones keep them."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -18,16 +17,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+from dist_util import launch  # noqa: E402
+
 SPLITS = {2: [5, 2], 3: [4, 0, 3]}            # the 7 sessions over the ranks: uneven, one rank with none at world 3
 CAPS = {2: 6, 3: 5}                           # rows every rank contributes: more than the largest local batch
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, ret, N=300, B=7):
@@ -224,10 +217,7 @@ def _worker(rank, world, port, ret, N=300, B=7):
 
 
 def _run(world):
-    import torch.multiprocessing as mp
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+    ret = launch(_worker, world)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 

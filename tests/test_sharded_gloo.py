@@ -5,7 +5,6 @@ shapes of uneven / empty shards, the asynchronous item-row all-gather, and the A
 per-shard softmax statistics and their combine, padding sessions of uneven shards, local dE, summed dX, the negative-term rows
 that fall into a shard, and the S5 norm of the dense item block as a sum over the shards)."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -15,13 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from dist_util import launch  # noqa: E402
 
 
 def _worker(rank, world, port, ret, N=300, B=7):
@@ -189,10 +182,7 @@ def _worker(rank, world, port, ret, N=300, B=7):
 
 
 def _run(world, N, B):
-    import torch.multiprocessing as mp
-    mgr = mp.Manager()
-    ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), ret, N, B), nprocs=world, join=True)
+    ret = launch(_worker, world, N, B)
     for r in range(world):
         assert ret.get(r) == "ok", ret.get(r)
 
