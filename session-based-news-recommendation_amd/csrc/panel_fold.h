@@ -55,3 +55,35 @@ __device__ __forceinline__ unsigned window_bits4(int lo, int hi, int4 q) {
   return (unsigned)((lo <= q.x) & (q.x < hi)) | (unsigned)((lo <= q.y) & (q.y < hi)) << 1 | (unsigned)((lo <= q.z) & (q.z < hi)) << 2 |
          (unsigned)((lo <= q.w) & (q.w < hi)) << 3;
 }
+
+// ---- the sortable key of a list entry: what the admitting selectors (retrieve.hip, sections.hip) keep in LDS
+typedef unsigned long long rt_key_t;
+
+// (score, id) -> a 64-bit key whose UNSIGNED order is the list order.  High word: the score's bits made monotone (negative: all bits
+// flipped, else the sign bit set), with -0.0 folded onto +0.0 first — the two compare equal, so the id must decide between them.  Low
+// word: id << 1 (ids are >= 0) with the folded sign of a zero in bit 0, so that rt_score gives back the score's own bits.  Every real
+// key is > 0 (the smallest high word, -inf's, is 0x007fffff): 0 is "nothing", the padding of the sort and the threshold of a list
+// that is not full.  NaN never gets here.
+__device__ __forceinline__ rt_key_t rt_key(float v, int id) {
+  unsigned u = __float_as_uint(v);
+  const unsigned nz = u == 0x80000000u;
+  if (nz) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((rt_key_t)u << 32) | (rt_key_t)(((unsigned)id << 1) | nz);
+}
+__device__ __forceinline__ int rt_id(rt_key_t k) { return (int)((unsigned)k >> 1); }
+__device__ __forceinline__ float rt_score(rt_key_t k) {
+  const unsigned u = (unsigned)(k >> 32);
+  if ((unsigned)k & 1u) return -0.f;
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// ---- the section codes of a sectioned fold (include/tcar_sections.h): 1 .. 16 of them, pairwise distinct, in host memory
+constexpr int SEC_MAX_G = 16;
+inline bool bad_sections(int G, const int32_t* sections) {
+  if (G < 1 || G > SEC_MAX_G || !sections) return true;
+  for (int i = 1; i < G; ++i)
+    for (int j = 0; j < i; ++j)
+      if (sections[i] == sections[j]) return true;
+  return false;
+}

@@ -22,32 +22,11 @@ constexpr int RT_SWEEP = RT_NT * 4 * RT_U;
 constexpr int RT_MIN_CAP = 256;                // the buffer of a small C: 2 Cp entries would prune every few admissions
 constexpr int RT_MAX_CAP = 2 * RT_MAX_C;       // 2,048 keys: 16 KB
 
-typedef unsigned long long rt_key_t;
-
 // state row (fold_row_words of panel_fold.h): score[C] | id[C] (-1: empty) | held, threshold key (low, high word), pad; reset: zeros
 __host__ __device__ inline int rt_cap(int C) {
   int p = 1;
   while (p < C) p <<= 1;
   return 2 * p < RT_MIN_CAP ? RT_MIN_CAP : 2 * p;
-}
-
-// (score, id) -> a 64-bit key whose UNSIGNED order is the list order.  High word: the score's bits made monotone (negative: all bits
-// flipped, else the sign bit set), with -0.0 folded onto +0.0 first — the two compare equal, so the id must decide between them.  Low
-// word: id << 1 (ids are >= 0) with the folded sign of a zero in bit 0, so that rt_score gives back the score's own bits.  Every real
-// key is > 0 (the smallest high word, -inf's, is 0x007fffff): 0 is "nothing", the padding of the sort and the threshold of a list
-// that is not full.  NaN never gets here.
-__device__ __forceinline__ rt_key_t rt_key(float v, int id) {
-  unsigned u = __float_as_uint(v);
-  const unsigned nz = u == 0x80000000u;
-  if (nz) u = 0u;
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((rt_key_t)u << 32) | (rt_key_t)(((unsigned)id << 1) | nz);
-}
-__device__ __forceinline__ int rt_id(rt_key_t k) { return (int)((unsigned)k >> 1); }
-__device__ __forceinline__ float rt_score(rt_key_t k) {
-  const unsigned u = (unsigned)(k >> 32);
-  if ((unsigned)k & 1u) return -0.f;
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
 // One workgroup per session.  LDS: the key buffer (cap = max(2 Cp, 256) entries used, Cp = C rounded up to a power of two) and the

@@ -6,6 +6,8 @@
 #include "../../include/tcar_serve_shard.h"
 #include "../../include/tcar_cand.h"
 #include "../../include/tcar_retrieve_shard.h"
+#include "../../include/tcar_sections.h"
+#include "panel_fold.h"
 #include <stdlib.h>
 
 static int env_int(const char* name, int dflt) {
@@ -1351,7 +1353,45 @@ int serve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t*
   RET(serve_fold(c, B, c->a16h, c->a16l, 0, bt->label, lab, s, w, q, stream));
   return tcar_select_finish(B, k, s->state, lab, s->topk, s->score, lab ? s->rank : nullptr, lab ? s->ce : nullptr, stream);
 }
+
+// Sectioned recommendation (include/tcar_sections.h): the head of a forward pass, then ONE GEMM per panel folded into the B G section
+// rows by tcar_section_panel and, where the descriptor asks for the overall list too, by the unlabelled tcar_select_panel_window into
+// the overall state while the panel is warm; the finishes.  Of *d->overall only k, state, state_bytes, topk and score are read.
+int sections_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_sections_t* d,
+                  void* stream) {
+  if (!c || !bt || bt->B < 0 || !d) return TCAR_E_ARG;
+  RET(check_panel_desc(d->panel, d->panel_buf, d->excl, d->X, d->window));
+  if (d->k < 1 || d->k > SEL_MAX_K || bad_sections(d->G, d->sections) || !d->cat || !d->state || !d->topk) return TCAR_E_ARG;
+  const int64_t rows = (int64_t)bt->B * d->G;
+  if (rows > 0x7fffffffL || d->state_bytes < rows * fold_row_words(d->k) * 4) return TCAR_E_ARG;
+  const tcar_serve_t* o = d->overall;
+  if (o && (o->k < 1 || o->k > SEL_MAX_K || !o->state || !o->topk || o->state_bytes < tcar_select_state_bytes(bt->B, o->k)))
+    return TCAR_E_ARG;
+  if (bt->B == 0) return TCAR_OK;
+  RET(serve_head(c, bt, rg, refresh_time, stream, c->scoring));
+  const int B = bt->B, BG = (int)rows, k = d->k;
+  const tcar_window_t* w = d->window;
+  const int32_t *key = w ? w->key : nullptr, *lo = w ? w->lo : nullptr, *hi = w ? w->hi : nullptr;
+  RET(tcar_select_reset(BG, k, d->state, stream));
+  if (o) RET(tcar_select_reset(B, o->k, o->state, stream));
+  RET(for_panels(c, B, c->a16h, c->a16l, c->scoring, d->panel, d->panel_buf, stream, [&](int n0, int n) {
+    RET(tcar_section_panel(B, n0, n, d->panel_buf, d->panel, k, d->G, d->sections, d->cat, d->excl, d->X, key, lo, hi, d->state, stream));
+    if (!o) return (int)TCAR_OK;
+    return tcar_select_panel_window(B, n0, n, d->panel_buf, d->panel, o->k, nullptr, nullptr, d->excl, d->X, o->state, stream, key, lo, hi);
+  }));
+  RET(tcar_select_finish(BG, k, d->state, nullptr, d->topk, d->score, nullptr, nullptr, stream));
+  if (!o) return TCAR_OK;
+  return tcar_select_finish(B, o->k, o->state, nullptr, o->topk, o->score, nullptr, nullptr, stream);
+}
 }  // namespace
+
+extern "C" int tcar_sections_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_sections_t* d, void* stream) {
+  return sections_step(c, bt, nullptr, refresh_time, d, stream);
+}
+extern "C" int tcar_sections_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
+                                         const tcar_sections_t* d, void* stream) {
+  return rg ? sections_step(c, bt, rg, refresh_time, d, stream) : (int)TCAR_E_ARG;
+}
 
 extern "C" int tcar_serve_step_quota(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_serve_t* s,
                                      const tcar_window_t* w, const tcar_quota_t* q, void* stream) {

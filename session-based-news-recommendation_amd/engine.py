@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, Cand, Dims, Grads, Ragged, Rerank, Retrieve, Segments, Quota, Serve, Tables, Window, check
+from ._lib import Batch, Cand, Dims, Grads, Ragged, Rerank, Retrieve, Sections, Segments, Quota, Serve, Tables, Window, check
 from .oplevel import OpLevelStep
 from .workspace import F32, HOST_I32, I32, U8, ScoreForm, Spec, Workspace, ru as _ru, scoring_specs
 
@@ -1166,6 +1166,80 @@ class TcarEngine(OpLevelStep):
         _, topk, _, scores = self._serve(bt, k, panel, excl, False, window, max_per_category)
         return topk, scores
 
+    # ---- one list per category from one pass over the catalog (include/tcar_sections.h)
+    MAX_SECTIONS = 16              # sections of one call (TCAR_MAX_SECTIONS)
+
+    def _sections_request(self, sections, k, overall, panel: Optional[int], window, width: int):
+        """The request of a recommend_sections call, validated before anything is uploaded -> (codes int32 [G], panel)."""
+        if getattr(self, "_cat", None) is None:
+            raise ValueError("sections are categories: call set_categories(cat_of_item) first")
+        try:
+            codes = list(sections)
+        except TypeError:
+            raise ValueError("sections: 1 to %d distinct integer category codes" % self.MAX_SECTIONS) from None
+        if not 1 <= len(codes) <= self.MAX_SECTIONS:
+            raise ValueError("sections: 1 to %d category codes, not %d" % (self.MAX_SECTIONS, len(codes)))
+        if any(isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) for c in codes):
+            raise ValueError("section codes must be integers")
+        codes = [int(c) for c in codes]
+        if min(codes) < -2 ** 31 or max(codes) >= 2 ** 31:
+            raise ValueError("section codes must fit int32")
+        if len(set(codes)) != len(codes):
+            raise ValueError("section codes must be pairwise distinct")
+        for name, v in (("k", k), ("overall", overall)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 64):
+                raise ValueError("%s must be an int in [1, 64]" % name)
+        if k is None:
+            raise ValueError("k must be an int in [1, 64]")
+        return np.asarray(codes, dtype=np.int32), self._panel_request(panel, window, width)
+
+    def recommend_sections(self, batch, sections, k: int = 10, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None,
+                           window=None, overall: Optional[int] = None) -> "SectionLists":
+        """One list PER CATEGORY from one pass over the catalog: `sections` names G category codes of set_categories(), 1 <= G <= 16,
+        pairwise distinct, and list g of a session is the k best items (1 <= k <= 64) of category sections[g] — best first (score, then
+        item id, descending), -1 where the category holds fewer than k eligible items.  One session forward, one scoring GEMM per panel
+        and one fold for all G lists; each list carries the bits of recommend(k, window=(code, code + 1)) on an engine whose item keys
+        are the categories.  exclude_seen, exclude, panel and window (a publish-time window over set_item_keys, on top of the section)
+        as recommend() takes them.  overall = k0 (1 .. 64): also the one list over all categories, the bits of recommend(k0) with the
+        same window and exclusions, from the same panels (one more fold, no more GEMM).
+        Returns SectionLists(topk [B, G, k] int32, scores [B, G, k] f32, overall_topk, overall_scores [B, k0] or None): views of the
+        workspace, valid until the next streamed call."""
+        g = self.geo
+        codes, panel = self._sections_request(sections, k, overall, panel, window, g.Npad)
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("sectioned selection needs the whole catalog on this engine (no shard)")
+        k, G = int(k), len(codes)
+        self.flush()
+        bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
+        B = bt.B
+        self._ensure_work(B, bt.T, self._rows(bt))
+        wb = self.work_B
+        words = lambda kk: int(self.lib.tcar_select_state_bytes(1, kk)) // 4      # noqa: E731
+        specs = [Spec("panel_buf", (wb, panel), F32), Spec("sec_state", (wb, G, words(k)), I32), Spec("sec_topk", (wb, G, k), I32),
+                 Spec("sec_score", (wb, G, k), F32)]
+        if overall is not None:
+            k0 = int(overall)
+            specs += [Spec("sel_state", (wb, words(k0)), I32), Spec("sel_topk", (wb, k0), I32), Spec("sel_score", (wb, k0), F32)]
+        d = Sections()
+        d.excl, d.X = self._ensure_fold(specs, excl, B)
+        d.k, d.G, d.cat = k, G, self._cat.data_ptr()
+        for i, c in enumerate(codes):
+            d.sections[i] = int(c)
+        d.panel, d.panel_buf = panel, self.panel_buf.data_ptr()
+        d.state, d.state_bytes = self.sec_state.data_ptr(), self.sec_state.numel() * 4
+        d.topk, d.score = self.sec_topk.data_ptr(), self.sec_score.data_ptr()
+        w = self._window(window, B) if window is not None else None
+        if w is not None:
+            d.window = C.addressof(w)            # (w and o stay alive until the call has returned)
+        o = None
+        if overall is not None:
+            o = self._serve_desc(k0, panel, self.panel_buf, self.sel_state, outputs=(self.sel_topk, self.sel_score))
+            d.overall = C.addressof(o)
+        self._head_step("sections_step", self._without_neg(bt, label=False), C.byref(d))
+        if o is None:
+            return SectionLists(self.sec_topk[:B], self.sec_score[:B], None, None)
+        return SectionLists(self.sec_topk[:B], self.sec_score[:B], self.sel_topk[:B], self.sel_score[:B])
+
     # ---- in-place catalog updates (include/tcar_catalog.h): publish, correct and retire articles in a live engine
     def _update_request(self, ids, content, item_rows, mwdhm, keys, categories):
         """The request of an update_items call, validated before anything is uploaded or launched -> (ids int32 [U], then content /
@@ -1425,6 +1499,14 @@ class TcarEngine(OpLevelStep):
         SHORTLIST: an item the coarse scores rank below `shortlist` cannot enter it.  k <= 64 and k <= shortlist <= 1024.  Views of
         the workspace, valid until the next call; the shortlist itself is in `rt_ids` / `rt_scores`."""
         return self._retrieve(batch, shortlist, k, exclude_seen, exclude, panel, window)
+
+
+class SectionLists(NamedTuple):
+    """what TcarEngine.recommend_sections returns: device views, valid until the next streamed call"""
+    topk: torch.Tensor                          # [B, G, k] int32
+    scores: torch.Tensor                        # [B, G, k] f32
+    overall_topk: Optional[torch.Tensor]        # [B, k0] int32, or None without `overall`
+    overall_scores: Optional[torch.Tensor]      # [B, k0] f32
 
 
 class CandResult(NamedTuple):

@@ -47,6 +47,7 @@ REFERENCE_FLAGS = [
 MAX_PANEL = 49152          # the widest panel a fold takes (SEL_MAX_N of csrc/tcar_common.h; engine.TcarEngine.SERVE_MAX_PANEL)
 
 
+MAX_SECTIONS = 16          # sections of one sectioned call (engine.TcarEngine.MAX_SECTIONS; TCAR_MAX_SECTIONS of include/tcar_sections.h)
 MAX_SHORTLIST = 1024       # entries of one shortlist (engine.TcarEngine.RETRIEVE_MAX_C); a list of up to 64 needs no first stage
 MAX_CANDIDATES = 1024      # slots of one candidate list (CAND_MAX_C of csrc/tcar_common.h; engine.TcarEngine.CAND_MAX_C)
 
@@ -108,6 +109,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "--batch_size sessions (include/tcar_ragged.h) and streams the catalog once per pack instead of once per batch.  "
                          "Needs --eval_panel; combines with --fresh_hours and --cat_cap; not with --dp_mode sharded, --gpus > 1, "
                          "--eval_candidates, --eval_shortlist.  0: one call per batch")
+    ap.add_argument("--eval_sections", default=0, type=int,
+                    help="G > 0: evaluation additionally asks for one list of 20 per CATEGORY on every batch (include/tcar_sections.h: "
+                         "the G categories with the most catalog items, all from one pass over the catalog) and prints the share of "
+                         "labels found in the list of their own category; 1 <= G <= " + str(MAX_SECTIONS) + ".  Needs --eval_panel; "
+                         "combines with --fresh_hours and --eval_mixed; not with --dp_mode sharded.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -148,6 +154,14 @@ def check_fresh_hours(fresh_hours, eval_panel, dp_mode):
 def check_cat_cap(cat_cap, eval_panel, dp_mode):
     """--cat_cap caps the lists of the streamed evaluation (include/tcar_quota.h): it needs --eval_panel and the whole catalog on one engine"""
     _check_streamed_option("cat_cap", cat_cap, "caps", "per-category cap", eval_panel, dp_mode)
+
+
+def check_eval_sections(eval_sections, eval_panel, dp_mode):
+    """--eval_sections asks one engine for a list per category beside its streamed evaluation (include/tcar_sections.h): it needs
+    --eval_panel and the whole catalog on one engine"""
+    if eval_sections > MAX_SECTIONS:
+        raise ValueError("--eval_sections must be in [1, %d] (0: off)" % MAX_SECTIONS)
+    _check_streamed_option("eval_sections", eval_sections, "lists the categories beside", "list per category", eval_panel, dp_mode)
 
 
 def check_shard_eval_panel(shard_eval_panel, dp_mode):
@@ -277,6 +291,7 @@ def main(argv=None):
     check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
     check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
+    check_eval_sections(args.eval_sections, args.eval_panel, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
     check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
     check_shard_eval_shortlist(args.shard_eval_shortlist, args.shard_eval_panel, args.dp_mode)

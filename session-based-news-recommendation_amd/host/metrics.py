@@ -26,6 +26,25 @@ def list_ranks(topk, labels, cutoff: int = 20) -> np.ndarray:
     return np.where(eq.any(1), eq.argmax(1) + 1, cutoff + 1).astype(np.int64)
 
 
+def largest_categories(cat, G: int) -> np.ndarray:
+    """The G category codes that the most items of the table `cat` [N] carry, the largest first; of two categories of one size the
+    smaller code comes first.  Fewer than G codes in the table: all of them.  What test() lists as sections (eval_sections)."""
+    codes, counts = np.unique(np.asarray(cat).reshape(-1), return_counts=True)        # codes ascending
+    order = np.argsort(-counts, kind="stable")                                        # stable: ties keep the ascending codes
+    return codes[order][:G].astype(np.int64)
+
+
+def section_hits(topk, labels, cat, sections):
+    """Sectioned lists topk [B, G, k] (0-based ids, -1 = no entry; list g holds items of category sections[g]) against the labels
+    [B] -> (hit [B] bool: the label is in the list of ITS OWN section, covered [B] bool: the label's category is a listed section).
+    Recall in the label's section = hit.sum() / covered.sum()."""
+    topk, labels = np.asarray(topk), np.asarray(labels, dtype=np.int64).reshape(-1)
+    mine = np.asarray(cat)[labels][:, None] == np.asarray(sections, dtype=np.int64)[None, :]       # [B, G], at most one per row
+    covered = mine.any(1)
+    own = topk[np.arange(len(labels)), mine.argmax(1)]                                             # [B, k] (row 0's where uncovered)
+    return covered & (own == labels[:, None]).any(1), covered
+
+
 def cau_metrics(preds, labels, cutoff=20):
     """Same contract as util.py:8-18: rank = 1 + #{j: preds[j] > preds[label]} (strict)."""
     preds = np.asarray(preds)

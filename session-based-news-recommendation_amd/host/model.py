@@ -145,6 +145,7 @@ class Seq2SeqAttNN():
         self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
         self.shard_eval_shortlist = self._shard_eval_shortlist(args)   # C > 0: test() also runs the SHARDED two-stage recommendation
         self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
+        self.eval_sections = self._eval_sections(args)               # G > 0: test() also asks for one list per category (G of them)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -220,6 +221,12 @@ class Seq2SeqAttNN():
                                       for n in ('eval_panel', 'eval_candidates', 'eval_shortlist', 'eval_mixed'))
         cli.check_eval_mixed(mixed, panel, args.get('dp_mode', 'replica'), max(int(args.get('gpus', 1) or 1), getattr(self, 'dp_world', 1)), ncand, short)
         return mixed
+
+    def _eval_sections(self, args) -> int:
+        """eval_sections of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        panel, nsec = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'eval_sections'))
+        cli.check_eval_sections(nsec, panel, args.get('dp_mode', 'replica'))
+        return nsec
 
     def _packs(self, feeds, mixed: bool):
         """test(): the sampler's feeds grouped into the packs of one streamed call each — consecutive feeds, never splitting one,
@@ -461,6 +468,18 @@ class Seq2SeqAttNN():
         self._install_categories()
         eng.reset_coverage()
         mixed = self._eval_mixed(args)
+        nsec = self._eval_sections(args)
+        # eval_sections: the categories with the most catalog items are the sections (include/tcar_sections.h), 20 items each
+        sections = M.largest_categories(self._category_table(), nsec) if nsec else None
+        sec_pending = []
+
+        def section_lists(feeds, window):
+            """the sectioned lists of the sessions of `feeds` (one feed, or the feeds of a pack: one ragged call), kept for the drain"""
+            bare = [{n: v for n, v in f.items() if n not in ("label", "neg")} for f in feeds]
+            res = eng.recommend_sections(bare[0] if len(bare) == 1 else pack_sessions(bare), sections, k=20, exclude_seen=False,
+                                         panel=panel, window=window)
+            sec_pending.append((np.concatenate([np.asarray(f["label"]).reshape(-1) for f in feeds]), res.topk.clone()))
+
         eval_calls = 0
         for pack in (self._packs(prefetch_batches(sampler), True) if mixed else ()):
             # eval_mixed: ONE streamed call per pack of feeds (a ragged batch, include/tcar_ragged.h); a pack of one feed goes the
@@ -485,6 +504,8 @@ class Seq2SeqAttNN():
                 if batch < 3:
                     self._print_batch(feed, tk[0].cpu().numpy().tolist(), args)
                 s0, r0 = s0 + b, r0 + b * T
+            if nsec:             # (behind the diversity counts: the call uploads the pack again)
+                section_lists(pack, window)
         for feed in (() if mixed else prefetch_batches(sampler)):
             batch += 1
             eval_calls += 1          # one evaluation call per feed (data parallel: a collective step, the same count on every rank)
@@ -523,6 +544,8 @@ class Seq2SeqAttNN():
                 two, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
                                                  exclude_seen=False, panel=panel, window=window)
                 short_pending.append((feed["label"], topk.clone(), two.clone()))       # (topk: the streamed step's own buffer, untouched)
+            if nsec:             # one list per category for the same sessions (include/tcar_sections.h), last: it uploads the feed again
+                section_lists([feed], window)
         eng.check_forks()             # (synchronises) nothing below is reported from a run whose flag forks timed out
         for feed, rank, topk, ce, ild_c, unexp_c, n_rec in pending:
             r = rank.cpu().numpy()
@@ -574,6 +597,14 @@ class Seq2SeqAttNN():
             t_hit, t_agree = [v / n for v in self._allsum([float(np.sum(inside)), float(np.sum(agree))])]
             print('two-stage lists (shortlist {}): Recall@20: {}, agreement with the streamed lists: {}'.format(short, t_hit, t_agree))
             self.last_metrics["two_stage"] = {"recall": t_hit, "agreement": t_agree, "shortlist": short}
+        if nsec:
+            cat = self._category_table()
+            hc = [M.section_hits(tk.cpu().numpy(), lab, cat, sections) for lab, tk in sec_pending]
+            s_hit, s_cov = self._allsum([float(sum(h.sum() for h, _ in hc)), float(sum(c.sum() for _, c in hc))])
+            s_recall, s_share = s_hit / max(s_cov, 1.0), s_cov / n
+            print('sections ({} categories, 20 per section): Recall@20 in the label\'s section: {}, labels in a listed section: {}'.format(
+                len(sections), s_recall, s_share))
+            self.last_metrics["sections"] = {"G": int(len(sections)), "recall": s_recall, "covered": s_share}
         if fresh:           # (these labels are still scored: a label is always in its session's pool)
             share = self._allsum([float(np.sum(outside))])[0] / n
             print('labels outside their window: {}'.format(share))
@@ -607,6 +638,18 @@ class Seq2SeqAttNN():
             two_stage = self.engine.shard_recommend_two_stage if self._sharded() else self.engine.recommend_two_stage
             return two_stage(sessions, k=k, shortlist=shortlist, window=window, **kw)
         return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)
+
+    def recommend_sections(self, sessions, sections, k=10, window=None, **kw):
+        """One list per CATEGORY for every session of `sessions` — a feed dict as `recommend` takes it: `sections` names G codes of
+        the fold's category table (1 <= G <= 16, pairwise distinct), and list g holds the k best items of category sections[g].
+        engine.SectionLists(topk [B, G, k] int32 0-based ids, scores [B, G, k] f32, overall_topk, overall_scores) on the device, from
+        ONE pass over the catalog (engine.TcarEngine.recommend_sections has the options: exclude_seen, exclude, panel, overall).
+        window as in `recommend`: "fresh sport" is a section inside a publish-time window.  Not on the catalog-sharded engine."""
+        sessions = self._feed(sessions)
+        self._install_categories()
+        if window is not None:
+            self._item_keys()
+        return self.engine.recommend_sections(sessions, sections, k=k, window=window, **kw)
 
     def retrieve(self, sessions, C, window=None, **kw):      # noqa: N803
         """A shortlist of the C best next items (1 <= C <= 1024) of every session of `sessions` — a feed dict as `recommend` takes

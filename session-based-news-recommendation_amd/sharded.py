@@ -916,6 +916,13 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("recommend_two_stage() needs the whole catalog on one engine (no shard): the catalog-sharded engine "
                              "has neither retrieve() nor score_candidates()")
 
+    def recommend_sections(self, batch, sections, k: int = 10, exclude_seen: bool = True, exclude=None, panel: Optional[int] = None,
+                           window=None, overall: Optional[int] = None):
+        """not on the catalog-sharded engine: the B G state rows of the shards are what tcar_select_merge merges, but the exchange
+        that would carry them is not built (include/tcar_sections.h takes the whole catalog)"""
+        raise _lib.TcarError("recommend_sections() needs the whole catalog on one engine (no shard): sections over shards are not "
+                             "built yet")
+
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
         """not under this name on the catalog-sharded engine (include/tcar_catalog.h takes the whole catalog): a row's derived state
         lives on the rank that owns it and the ranks have to agree on the update — that is shard_update_items(), a collective"""

@@ -46,6 +46,14 @@ the buffers the last call left: the shard's fold, tcar_retrieve_merge, the owner
 and ONE tcar_retrieve_panel launch over the engine's panel buffer for B sessions; and the fold with 300 of cap = 512 rows live beside
 512 live (a padding session must cost nothing: include/tcar_retrieve_shard.h, tcar_retrieve_panel_live).
 
+       python tools/eval_bench.py [iters] [--n_items N] --sections G[,G...] [--k K] [--cats NCAT] [--panel P] [--rounds R]
+
+--sections G: TcarEngine.recommend_sections (include/tcar_sections.h: the G largest categories as sections, K items each) beside one
+recommend() and beside the G windowed recommend() calls it replaces (item keys = categories, window = (code, code + 1)), on the same
+host batches, alternating for `rounds` rounds: ms per call (upload included), the ratios, whether the sectioned lists equal the G
+windowed ones, and the folds alone — device events around tcar_select_panel at K into a fresh state beside tcar_section_panel from an
+empty and from a full state, over the panel the last step left in the panel buffer.
+
        python tools/eval_bench.py [iters] [--n_items N] --ragged LMAX [--k K] [--panel P] [--rounds R]
 
 --ragged LMAX: B = 512 sessions whose lengths are drawn uniformly from 1 .. LMAX (fixed seed).  TcarEngine.recommend once per length
@@ -86,7 +94,8 @@ ap.add_argument("--cap_skew", action="store_true", help="also cap 1 on a catalog
 ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded engine at the shapes of rank 0 of W ranks (with --streamed, --retrieve or --update)")
 ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
 ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
-ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve)")
+ap.add_argument("--sections", type=str, default="", help="comma-separated section counts G (1 .. 16) for recommend_sections")
+ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve) and of a section (with --sections)")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
 ap.add_argument("--scoring", type=str, default="bf16x3-mixed", help="scoring mode of the engine (f32 | bf16x3 | bf16x3-mixed | bf16)")
@@ -377,6 +386,97 @@ if shorts:
             print("N=%d round %d C=%d: retrieve %.3f ms (%.3f of recommend), recommend_two_stage %.3f ms (%.3f of recommend); one fold of "
                   "%d columns alone: select k=%d %.4f ms, retrieve C=%d %.4f ms" % (
                       N, rnd, c, dr * 1e3, dr / dt, d2 * 1e3, d2 / dt, min(eng.panel_buf.shape[1], N), K, fs, c, fr))
+        sys.stdout.flush()
+    sys.exit(0)
+sects = [int(g) for g in a.sections.split(",") if g]
+if sects:
+    # --sections G: TcarEngine.recommend_sections (include/tcar_sections.h: G lists from one pass) beside ONE recommend() and beside
+    # the G windowed recommend() calls it replaces — an engine whose item keys are the categories, window = (code, code + 1).  The
+    # protocol of the --retrieve table: host clock around `iters` calls ending in a device synchronise, the upload included, rounds
+    # alternating; then the folds alone with device events over the panel buffer as the last step left it.
+    import ctypes as C_
+    from tcar_amd.host import metrics as M_
+    if a.sharded:
+        sys.exit("--sections needs the whole catalog on one engine: not with --sharded")
+    if any(not 1 <= g <= 16 for g in sects):
+        sys.exit("--sections G: 1 .. 16")
+    P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
+    K = a.k
+    cat = getattr(fold, "category", None)
+    if cat is None or len(cat) != N:
+        cat = np.random.RandomState(7).randint(0, a.cats, N)
+    cat = np.asarray(cat, dtype=np.int32)
+    eng.set_categories(cat)
+    eng.set_item_keys(cat)
+    feeds = [{n: v for n, v in b.items() if n not in ("label", "neg")} for b in batches]
+
+    def timed_host(step):
+        for i in range(5):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            step(feeds[i % len(feeds)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    def by_windows(f, codes):
+        for c in codes:
+            eng.recommend(f, k=K, panel=P, window=(int(c), int(c) + 1))
+
+    def folds_alone(codes):
+        """ms of one tcar_select_panel (k = K) into a freshly reset state, and of one tcar_section_panel over the same panel buffer
+        from an EMPTY state (reset inside the timed region, as for the select fold) and from a FULL one: the state the fold before
+        left, folded onto again.  That state is full, and nothing of the same panel can enter it again, only where every section holds
+        at least K items in the panel; a shorter section keeps the threshold "nothing" and would admit its items a second time, which
+        is neither a full state nor a fold the contract allows (every item once).  Then the third figure is nan and not measured."""
+        lib, st = eng.lib, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        G = len(codes)
+        arr = (C_.c_int32 * G)(*[int(c) for c in codes])
+        n, ld = min(eng.panel_buf.shape[1], N), eng.panel_buf.shape[1]
+        sel = torch.empty(B * (2 * K + 4), dtype=torch.int32, device=eng.dev)
+        sec = torch.empty(B * G * (2 * K + 4), dtype=torch.int32, device=eng.dev)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            lib.tcar_select_reset(B, K, vp(sel), st)
+            lib.tcar_select_panel(B, 0, n, vp(eng.panel_buf), ld, K, None, None, None, 0, vp(sel), st)
+        ev[1].record()
+        for it in range(iters):
+            lib.tcar_select_reset(B * G, K, vp(sec), st)
+            lib.tcar_section_panel(B, 0, n, vp(eng.panel_buf), ld, K, G, arr, vp(eng._cat), None, 0, None, None, None, vp(sec), st)
+        ev[2].record()
+        full = min(int((cat[:n] == c).sum()) for c in codes) >= K          # every row of the state holds K entries
+        for it in range(iters if full else 0):
+            lib.tcar_section_panel(B, 0, n, vp(eng.panel_buf), ld, K, G, arr, vp(eng._cat), None, 0, None, None, None, vp(sec), st)
+        ev[3].record()
+        torch.cuda.synchronize()
+        return [ev[i].elapsed_time(ev[i + 1]) / iters for i in range(2)] + [ev[2].elapsed_time(ev[3]) / iters if full else float("nan")]
+
+    for G in sects:              # the same lists?  on every batch, outside the timed loops
+        codes = M_.largest_categories(cat, G)
+        same = []
+        for f in feeds[:4]:
+            got = eng.recommend_sections(f, codes, k=K, panel=P).topk.clone()
+            want = torch.stack([eng.recommend(f, k=K, panel=P, window=(int(c), int(c) + 1))[0].clone() for c in codes], 1)
+            same.append((got == want).all().item())
+        print("N=%d k=%d G=%d (%d categories, sections of %d .. %d items): sectioned lists equal to the G windowed lists on every batch: %s" % (
+            N, K, len(codes), len(np.unique(cat)), min((cat == c).sum() for c in codes), max((cat == c).sum() for c in codes), all(same)))
+    for rnd in range(a.rounds):
+        dt = timed_host(lambda f: eng.recommend(f, k=K, panel=P))
+        print("N=%d round %d recommend k=%d: %.3f ms = %.0f sessions/s" % (N, rnd, K, dt * 1e3, B / dt))
+        for G in sects:
+            codes = M_.largest_categories(cat, G)
+            ds = timed_host(lambda f: eng.recommend_sections(f, codes, k=K, panel=P))
+            dw = timed_host(lambda f: by_windows(f, codes))
+            fs, fe, ff = folds_alone(codes)
+            print("N=%d round %d G=%d: recommend_sections %.3f ms (%.3f of one recommend, %.3f of the G windowed calls), G windowed "
+                  "recommend calls %.3f ms; one fold of %d columns alone: select k=%d %.4f ms, sections from an empty state %.4f ms, "
+                  "from a full state %.4f ms%s" % (
+                      N, rnd, len(codes), ds * 1e3, ds / dt, ds / dw, dw * 1e3, min(eng.panel_buf.shape[1], N), K, fs, fe, ff,
+                      "" if ff == ff else " (not measured: a section holds fewer than k = %d items in the panel, so no state of it is full)" % K))
         sys.stdout.flush()
     sys.exit(0)
 if a.ragged:
