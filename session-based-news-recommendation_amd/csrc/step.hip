@@ -7,6 +7,7 @@
 #include "../../include/tcar_cand.h"
 #include "../../include/tcar_retrieve_shard.h"
 #include "../../include/tcar_sections.h"
+#include "../../include/tcar_mmr.h"
 #include "panel_fold.h"
 #include <stdlib.h>
 
@@ -1462,9 +1463,10 @@ int retrieve_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged
 }
 
 int retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time, const tcar_retrieve_t* d,
-                         const tcar_rerank_t* r, void* stream) {
+                         const tcar_rerank_t* r, void* stream, const tcar_mmr_t* m = nullptr) {
   RET(check_retrieve_desc(c, bt, d));
   if (!r || r->k < 1 || r->k > SEL_MAX_K || r->k > d->C || !r->cand_score || !r->order || !r->topk) return TCAR_E_ARG;
+  if (m && (!(m->mu >= 0.f) || m->mu > 3.402823466e+38f)) return TCAR_E_ARG;          // the penalty of the diversified close
   if (bt->B == 0) return TCAR_OK;
   if (c->scoring == 3 && (!c->a16l || !c->e16l)) return TCAR_E_ARG;
   RET(retrieve_impl(c, bt, rg, refresh_time, d, stream));
@@ -1473,7 +1475,10 @@ int retrieve_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar
   RET(tcar_cand_scores(B, C, g.N, g.ek, c->attout, g.ek, c->E, g.ek, c->scoring ? c->a16h : nullptr, c->a16l, g.ek, c->e16h, c->e16l, g.ek,
                        c->scoring, d->ids, C, r->cand_score, C, stream));
   RET(tcar_cand_rank(B, C, r->cand_score, C, d->ids, C, nullptr, 0, r->rank_of, r->order, nullptr, nullptr, stream));
-  return tcar_rerank_take(B, C, r->k, d->ids, r->cand_score, r->order, r->topk, r->score, stream);
+  if (!m) return tcar_rerank_take(B, C, r->k, d->ids, r->cand_score, r->order, r->topk, r->score, stream);
+  // the diversified close (include/tcar_mmr.h): the walk reads the content columns of E in place
+  return tcar_mmr_walk(B, C, r->k, m->mu, g.N, g.H, c->E + g.ldh, g.ek, d->ids, C, r->cand_score, C, r->order, r->topk, r->score, m->msim,
+                       stream);
 }
 }  // namespace
 
@@ -1512,6 +1517,17 @@ extern "C" int tcar_retrieve_step_ragged(const tcar_ctx_t* c, const tcar_batch_t
 extern "C" int tcar_retrieve_rerank_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const tcar_ragged_t* rg, int refresh_time,
                                                 const tcar_retrieve_t* d, const tcar_rerank_t* r, void* stream) {
   return rg ? retrieve_rerank_step(c, bt, rg, refresh_time, d, r, stream) : (int)TCAR_E_ARG;
+}
+
+// Diversified two-stage recommendation (include/tcar_mmr.h): the body of tcar_retrieve_rerank_step with the MMR walk as its close.
+extern "C" int tcar_mmr_rerank_step(const tcar_ctx_t* c, const tcar_batch_t* bt, int refresh_time, const tcar_retrieve_t* d,
+                                    const tcar_rerank_t* r, const tcar_mmr_t* m, void* stream) {
+  return m ? retrieve_rerank_step(c, bt, nullptr, refresh_time, d, r, stream, m) : (int)TCAR_E_ARG;
+}
+extern "C" int tcar_mmr_rerank_step_ragged(const tcar_ctx_t* c, const tcar_batch_t* bt, const void* ragged, int refresh_time,
+                                           const tcar_retrieve_t* d, const tcar_rerank_t* r, const tcar_mmr_t* m, void* stream) {
+  return m && ragged ? retrieve_rerank_step(c, bt, static_cast<const tcar_ragged_t*>(ragged), refresh_time, d, r, stream, m)
+                     : (int)TCAR_E_ARG;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1442,12 +1442,25 @@ class TcarEngine(OpLevelStep):
                 raise ValueError("k = %d items cannot come out of a shortlist of %d" % (k, C_))
         return self._panel_request(panel, window, width)
 
-    def _retrieve(self, batch, C_: int, k: Optional[int], exclude_seen: bool, exclude, panel: Optional[int], window):
-        """one tcar_retrieve_step (k None) or tcar_retrieve_rerank_step; returns views of the workspace"""
+    @staticmethod
+    def _diversity_request(diversity) -> float:
+        """The penalty of a diversified call (include/tcar_mmr.h), validated before anything is uploaded: a finite number >= 0 that is
+        finite as fp32 too."""
+        if isinstance(diversity, (bool, np.bool_)) or not isinstance(diversity, (int, float, np.integer, np.floating)):
+            raise ValueError("diversity must be a number >= 0 (the penalty mu of include/tcar_mmr.h, in score units), or None")
+        mu = float(diversity)
+        if not 0.0 <= mu <= float(np.finfo(np.float32).max):
+            raise ValueError("diversity must be finite and >= 0, not %r" % (diversity,))
+        return mu
+
+    def _retrieve(self, batch, C_: int, k: Optional[int], exclude_seen: bool, exclude, panel: Optional[int], window, diversity=None):
+        """one tcar_retrieve_step (k None), tcar_retrieve_rerank_step or, with a penalty, tcar_mmr_rerank_step; returns views of the
+        workspace"""
         g = self.geo
         if self.shard != (0, g.N):
             raise _lib.TcarError("retrieval needs the whole catalog on this engine (no shard)")
         panel = self._retrieve_request(C_, k, panel, window, g.Npad)
+        mu = self._diversity_request(diversity) if diversity is not None else None
         C_ = int(C_)
         self.flush()
         bt, excl = self._recommend_inputs(batch, exclude_seen, exclude)
@@ -1461,6 +1474,8 @@ class TcarEngine(OpLevelStep):
             k = int(k)
             specs += [Spec("rt_exact", (wb, C_), F32), Spec("rt_rank", (2, wb, C_), I32), Spec("rt_topk", (wb, k), I32),
                       Spec("rt_topscore", (wb, k), F32)]
+            if mu is not None:
+                specs.append(Spec("rt_msim", (wb, k), F32))
         d = Retrieve()
         d.excl, d.X = self._ensure_fold(specs, excl, B)
         d.C, d.panel, d.panel_buf = C_, panel, self.panel_buf.data_ptr()
@@ -1477,7 +1492,12 @@ class TcarEngine(OpLevelStep):
             r.k, r.cand_score = k, self.rt_exact.data_ptr()
             r.rank_of, r.order = self.rt_rank[0].data_ptr(), self.rt_rank[1].data_ptr()
             r.topk, r.score = self.rt_topk.data_ptr(), self.rt_topscore.data_ptr()
-            self._head_step("retrieve_rerank_step", bt, C.byref(d), C.byref(r))
+            if mu is None:
+                self._head_step("retrieve_rerank_step", bt, C.byref(d), C.byref(r))
+            else:
+                m = _lib.Mmr()
+                m.mu, m.msim = mu, self.rt_msim.data_ptr()
+                self._head_step("mmr_rerank_step", bt, C.byref(d), C.byref(r), C.byref(m))
         if k is None:
             return self.rt_ids[:B], self.rt_scores[:B]
         return self.rt_topk[:B], self.rt_topscore[:B]
@@ -1492,13 +1512,58 @@ class TcarEngine(OpLevelStep):
         return self._retrieve(batch, C, None, exclude_seen, exclude, panel, window)
 
     def recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
-                            panel: Optional[int] = None, window=None):
+                            panel: Optional[int] = None, window=None, diversity: Optional[float] = None):
         """recommend() in two stages with one session forward: retrieve(batch, shortlist) from coarse scores, then the exact scores
         of the shortlist (score_candidates' kernel, the engine's own scoring precision) and its k best: (topk [B,k] int32, scores
         [B,k] f32), best first; -1 where fewer than k items are eligible.  The list is the top k of the exact scores OVER THE
         SHORTLIST: an item the coarse scores rank below `shortlist` cannot enter it.  k <= 64 and k <= shortlist <= 1024.  Views of
-        the workspace, valid until the next call; the shortlist itself is in `rt_ids` / `rt_scores`."""
-        return self._retrieve(batch, shortlist, k, exclude_seen, exclude, panel, window)
+        the workspace, valid until the next call; the shortlist itself is in `rt_ids` / `rt_scores`.
+        diversity = mu >= 0 (finite): the k items are taken by the greedy MMR walk of include/tcar_mmr.h over the first 256 slots of
+        the shortlist's exact order — each pick is the largest s - mu * m, m the largest content cosine to what the list already
+        holds, so a verbatim duplicate of a listed item loses mu logits (mu = (1 - lambda) / lambda of the textbook weight).  The
+        scores returned are the exact scores of the picks; `rt_msim` [B, k] holds m of every pick, beside `rt_ids` / `rt_exact`.
+        mu = 0 gives the bits of the plain call; None IS the plain call, with its launches."""
+        return self._retrieve(batch, shortlist, k, exclude_seen, exclude, panel, window, diversity)
+
+    def diversify(self, candidates, scores, k: int = 20, diversity: float = 1.0):
+        """The MMR walk of recommend_two_stage(diversity=...) for lists the caller already holds, e.g. what score_candidates returned:
+        candidates int [B, C] (0-based ids; -1 or any id outside the catalog: an empty slot; repeats allowed), scores float [B, C],
+        host arrays or tensors, 1 <= C <= 1024, 1 <= k <= 64, k <= C.  tcar_cand_rank, then tcar_mmr_walk over the engine's content
+        table: no session forward.  Returns (topk [B, k] int32 (-1 once the pool is used up), scores [B, k] f32 (the given score of
+        each pick), msim [B, k] f32 (m of each pick)); slots behind the last pick hold -1 / 0 / 0.  Views of the workspace, valid
+        until the next call."""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("diversify needs the whole catalog on this engine (no shard)")
+        mu = self._diversity_request(diversity)
+        cand = candidates if isinstance(candidates, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(candidates))
+        sc = scores if isinstance(scores, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(scores))
+        if cand.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or cand.dim() != 2:
+            raise ValueError("candidates must be an integer array [B, C]")
+        if not sc.dtype.is_floating_point or tuple(sc.shape) != tuple(cand.shape):
+            raise ValueError("scores must be a float array of the shape of candidates")
+        B, C_ = int(cand.shape[0]), int(cand.shape[1])
+        if not 1 <= C_ <= self.CAND_MAX_C:
+            raise ValueError("C must be in [1, %d]" % self.CAND_MAX_C)
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64 or k > C_:
+            raise ValueError("k must be in [1, 64] and <= C = %d" % C_)
+        k = int(k)
+        self.flush()
+        rows = max(B, 1)
+        self.ws.ensure([Spec("dv_cand", (rows, C_), I32), Spec("dv_score", (rows, C_), F32), Spec("dv_rank", (2, rows, C_), I32),
+                        Spec("dv_topk", (rows, k), I32), Spec("dv_topscore", (rows, k), F32), Spec("dv_msim", (rows, k), F32)])
+        c64 = cand.to(self.dev).to(torch.int64)
+        self.dv_cand[:B].copy_(torch.where((c64 < 0) | (c64 >= g.N), torch.full_like(c64, -1), c64))
+        self.dv_score[:B].copy_(sc.to(self.dev))
+        self.dv_topscore[:B].zero_()
+        self.dv_msim[:B].zero_()
+        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+        check(self.lib.tcar_cand_rank(B, C_, p(self.dv_score), C_, p(self.dv_cand), C_, None, 0, p(self.dv_rank[0]), p(self.dv_rank[1]),
+                                      None, None, self._stream()), "tcar_cand_rank")
+        check(self.lib.tcar_mmr_walk(B, C_, k, mu, g.N, g.H, C.c_void_p(self.E.data_ptr() + 4 * g.ldh), g.ek, p(self.dv_cand), C_,
+                                     p(self.dv_score), C_, p(self.dv_rank[1]), p(self.dv_topk), p(self.dv_topscore), p(self.dv_msim),
+                                     self._stream()), "tcar_mmr_walk")
+        return self.dv_topk[:B], self.dv_topscore[:B], self.dv_msim[:B]
 
 
 class SectionLists(NamedTuple):

@@ -104,6 +104,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "shortlist of C items from coarse scores, re-scored exactly and cut to 20) and prints the share of labels in those "
                          "lists and their agreement with the streamed lists; 65 <= C <= " + str(MAX_SHORTLIST) + ".  Needs --eval_panel; "
                          "not with --dp_mode sharded, not with --cat_cap.  0: off")
+    ap.add_argument("--eval_diversity", default=0, type=float,
+                    help="MU > 0: evaluation additionally runs the DIVERSIFIED two-stage recommendation on every batch (include/tcar_mmr.h: "
+                         "the shortlist's k best under the greedy MMR walk over content, a verbatim duplicate of a listed item losing MU "
+                         "logits) and prints its Recall@20, ILD and content ILD beside those of the plain two-stage lists.  Needs "
+                         "--eval_shortlist C; not with --dp_mode sharded.  0: off")
     ap.add_argument("--eval_mixed", default=0, type=int,
                     help="1: evaluation packs consecutive batches of DIFFERENT session lengths into one ragged batch of at most "
                          "--batch_size sessions (include/tcar_ragged.h) and streams the catalog once per pack instead of once per batch.  "
@@ -197,6 +202,21 @@ def check_eval_shortlist(eval_shortlist, eval_panel, dp_mode, cat_cap=0):
         raise ValueError("--eval_shortlist needs --eval_panel P: its lists are compared with those of the streamed evaluation")
     if cat_cap:
         raise ValueError("--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap")
+
+
+def check_eval_diversity(eval_diversity, eval_shortlist, dp_mode):
+    """--eval_diversity runs the diversified two-stage recommendation (include/tcar_mmr.h) beside the plain one: a finite penalty
+    MU > 0 in score units, the shortlist of --eval_shortlist, and the whole catalog on one engine"""
+    if isinstance(eval_diversity, bool) or not isinstance(eval_diversity, (int, float, np.integer, np.floating)):
+        raise ValueError("--eval_diversity must be a number (0: off)")
+    if eval_diversity != eval_diversity or eval_diversity in (float("inf"), float("-inf")) or eval_diversity < 0:
+        raise ValueError("--eval_diversity must be a finite penalty > 0 (0: off)")
+    if not eval_diversity:
+        return
+    if dp_mode == "sharded":
+        raise ValueError("--eval_diversity diversifies the two-stage lists of ONE engine; it cannot be combined with --dp_mode sharded")
+    if not eval_shortlist:
+        raise ValueError("--eval_diversity needs --eval_shortlist C: the walk re-ranks the shortlist of the two-stage call")
 
 
 def check_shard_eval_shortlist(shard_eval_shortlist, shard_eval_panel, dp_mode):
@@ -294,6 +314,7 @@ def main(argv=None):
     check_eval_sections(args.eval_sections, args.eval_panel, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
     check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
+    check_eval_diversity(args.eval_diversity, args.eval_shortlist, args.dp_mode)
     check_shard_eval_shortlist(args.shard_eval_shortlist, args.shard_eval_panel, args.dp_mode)
     check_eval_mixed(args.eval_mixed, args.eval_panel, args.dp_mode, args.gpus, args.eval_candidates, args.eval_shortlist)
     dp_group = None

@@ -66,6 +66,24 @@ def ild_batch(topk: np.ndarray, cat_of_item: np.ndarray) -> np.ndarray:
     return diff / float(k * (k - 1))
 
 
+def content_ild_batch(topk, content) -> np.ndarray:
+    """Intra-list distance over CONTENT: for every list of topk [B, k] (0-based ids, -1 = no entry) the mean of 1 - cos(x_i, x_j) over
+    the ordered pairs (i != j) of its entries, x_n = content[n] (float [N, H]); an all-zero row has cosine 0 with everything.  NaN
+    for a list of fewer than 2 entries.  float64 [B].  The content twin of ild_batch, which compares category labels."""
+    topk = np.asarray(topk)
+    x = np.asarray(content, dtype=np.float64)
+    norm = np.sqrt((x * x).sum(1))
+    x = x * np.where(norm > 0, 1.0 / np.where(norm > 0, norm, 1.0), 0.0)[:, None]
+    out = np.full(topk.shape[0], np.nan)
+    for b, row in enumerate(topk):
+        ids = row[row >= 0]
+        n = len(ids)
+        if n >= 2:
+            cos = x[ids] @ x[ids].T
+            out[b] = ((n * (n - 1)) - (cos.sum() - np.trace(cos))) / float(n * (n - 1))
+    return out
+
+
 def unexp_batch(seq: np.ndarray, topk: np.ndarray, cat_of_item: np.ndarray) -> np.ndarray:
     """model_combine.py:184-194: share of (recommended, input) pairs with different category; `seq` holds
     1-based ids."""

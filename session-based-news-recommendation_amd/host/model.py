@@ -144,6 +144,7 @@ class Seq2SeqAttNN():
         self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
         self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
         self.shard_eval_shortlist = self._shard_eval_shortlist(args)   # C > 0: test() also runs the SHARDED two-stage recommendation
+        self.eval_diversity = self._eval_diversity(args)             # MU > 0: test() also runs the DIVERSIFIED two-stage recommendation
         self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
         self.eval_sections = self._eval_sections(args)               # G > 0: test() also asks for one list per category (G of them)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
@@ -208,6 +209,13 @@ class Seq2SeqAttNN():
         panel, cap, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'cat_cap', 'eval_shortlist'))
         cli.check_eval_shortlist(short, panel, args.get('dp_mode', 'replica'), cap)
         return short
+
+    def _eval_diversity(self, args) -> float:
+        """eval_diversity of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        mu = args.get('eval_diversity', getattr(self, 'eval_diversity', 0)) or 0
+        short = int(args.get('eval_shortlist', getattr(self, 'eval_shortlist', 0)) or 0)
+        cli.check_eval_diversity(mu, short, args.get('dp_mode', 'replica'))
+        return float(mu)
 
     def _shard_eval_shortlist(self, args) -> int:
         """shard_eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
@@ -451,6 +459,8 @@ class Seq2SeqAttNN():
         sshort = self._shard_eval_shortlist(args)                # the sharded two-stage call: the same line, the same metrics
         short = self._eval_shortlist(args) or sshort
         short_pending = []
+        mu = self._eval_diversity(args)                          # the diversified two-stage call (include/tcar_mmr.h), beside the plain one
+        div_pending = []
         if spanel and not hasattr(eng, "xch"):
             raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         time_dict = test_data[2] if len(test_data) > 2 else None
@@ -543,7 +553,12 @@ class Seq2SeqAttNN():
             elif short:          # the two-stage lists of the same sessions (include/tcar_retrieve.h), beside the streamed ones
                 two, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
                                                  exclude_seen=False, panel=panel, window=window)
-                short_pending.append((feed["label"], topk.clone(), two.clone()))       # (topk: the streamed step's own buffer, untouched)
+                two = two.clone()            # (the diversified call below writes the same workspace)
+                short_pending.append((feed["label"], topk.clone(), two))       # (topk: the streamed step's own buffer, untouched)
+                if mu:           # ... and their diversified form: the same shortlist, the MMR walk over content as its close
+                    div, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
+                                                     exclude_seen=False, panel=panel, window=window, diversity=mu)
+                    div_pending.append((feed["label"], two, div.clone()))
             if nsec:             # one list per category for the same sessions (include/tcar_sections.h), last: it uploads the feed again
                 section_lists([feed], window)
         eng.check_forks()             # (synchronises) nothing below is reported from a run whose flag forks timed out
@@ -597,6 +612,24 @@ class Seq2SeqAttNN():
             t_hit, t_agree = [v / n for v in self._allsum([float(np.sum(inside)), float(np.sum(agree))])]
             print('two-stage lists (shortlist {}): Recall@20: {}, agreement with the streamed lists: {}'.format(short, t_hit, t_agree))
             self.last_metrics["two_stage"] = {"recall": t_hit, "agreement": t_agree, "shortlist": short}
+        if mu and not sshort:
+            cat, content = self._category_table(), np.asarray(eng._content)[1:]
+
+            def list_means(lists):
+                """sums over the sessions whose list is full (category ILD divides by k (k - 1), as getILD does) -> their count too"""
+                full = lists[(lists >= 0).all(1)]
+                return [float(M.ild_batch(full, cat).sum()), float(M.content_ild_batch(full, content).sum()), float(len(full))]
+            tot = np.zeros(7)
+            for label, two, div in div_pending:
+                two, div = two.cpu().numpy(), div.cpu().numpy()
+                tot += [float((div == np.asarray(label)[:, None]).any(1).sum())] + list_means(div) + list_means(two)
+            tot = self._allsum(tot.tolist())
+            d_hit, d_ild, d_cild = tot[0] / n, tot[1] / max(tot[3], 1.0), tot[2] / max(tot[3], 1.0)
+            t_ild, t_cild = tot[4] / max(tot[6], 1.0), tot[5] / max(tot[6], 1.0)
+            print('diversified lists (shortlist {}, penalty {}): Recall@20: {}, ILD: {}, content ILD: {} (two-stage lists: ILD {}, '
+                  'content ILD {})'.format(short, mu, d_hit, d_ild, d_cild, t_ild, t_cild))
+            self.last_metrics["diversified"] = {"recall": d_hit, "ild": d_ild, "content_ild": d_cild, "two_stage_ild": t_ild,
+                                                "two_stage_content_ild": t_cild, "shortlist": short, "penalty": mu}
         if nsec:
             cat = self._category_table()
             hc = [M.section_hits(tk.cpu().numpy(), lab, cat, sections) for lab, tk in sec_pending]
@@ -616,7 +649,7 @@ class Seq2SeqAttNN():
         return m_hit
 
     # ---------------------------------------------------------------------------------------- recommend
-    def recommend(self, sessions, k=20, window=None, max_per_category=None, shortlist=None, **kw):
+    def recommend(self, sessions, k=20, window=None, max_per_category=None, shortlist=None, diversity=None, **kw):
         """The k best next items of every session of `sessions` — a feed dict as the samplers build it (seq, pm, pd, pw, ph, pmi,
         gap, cw, ch; no label, no neg) — as (topk [B, k] int32 0-based ids, scores [B, k] f32) on the device; items the session
         has already read are left out (engine.TcarEngine.recommend has the options).  window = (lo, hi), scalars or arrays [B], in
@@ -626,7 +659,12 @@ class Seq2SeqAttNN():
         where it has none, with cap= and T= (sharded.ShardedEngine.recommend).
         shortlist = C (k <= C <= 1024): the two-stage form — C items retrieved from coarse scores, re-scored exactly, the k best of
         them returned (engine.TcarEngine.recommend_two_stage; the catalog-sharded engine: shard_recommend_two_stage, a collective
-        like its recommend); None: the streamed selection over exact scores, as ever."""
+        like its recommend); None: the streamed selection over exact scores, as ever.
+        diversity = mu >= 0 (only with shortlist): the k items are taken from the shortlist by the MMR walk over content
+        (engine.TcarEngine.recommend_two_stage: a verbatim duplicate of a listed item loses mu logits); refused by the
+        catalog-sharded engine."""
+        if diversity is not None and shortlist is None:
+            raise ValueError("diversity re-ranks the shortlist of the two-stage recommendation: pass shortlist=C with it")
         if shortlist is not None and max_per_category is not None:
             raise ValueError("the two-stage recommendation takes no per-category cap (shortlist and max_per_category exclude each other)")
         sessions = self._feed(sessions)
@@ -636,6 +674,8 @@ class Seq2SeqAttNN():
             self._install_categories()
         if shortlist is not None:
             two_stage = self.engine.shard_recommend_two_stage if self._sharded() else self.engine.recommend_two_stage
+            if diversity is not None:
+                kw = dict(kw, diversity=diversity)
             return two_stage(sessions, k=k, shortlist=shortlist, window=window, **kw)
         return self.engine.recommend(sessions, k=k, window=window, max_per_category=max_per_category, **kw)
 

@@ -910,9 +910,20 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("retrieve() needs the whole catalog on one engine (no shard): the catalog-sharded engine cannot merge "
                              "shortlists")
 
+    @staticmethod
+    def _refuse_diversity(diversity) -> None:
+        if diversity is not None:
+            raise _lib.TcarError("diversity (the MMR walk of recommend_two_stage) needs the whole catalog on one engine: the "
+                                 "catalog-sharded two-stage call does not take the keyword yet")
+
+    def diversify(self, candidates, scores, k: int = 20, diversity: float = 1.0):
+        """not on the catalog-sharded engine (TcarEngine.diversify reads the content table of a whole-catalog engine)"""
+        raise _lib.TcarError("diversify() needs the whole catalog on one engine (no shard)")
+
     def recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
-                            panel: Optional[int] = None, window=None):
+                            panel: Optional[int] = None, window=None, diversity=None):
         """not on the catalog-sharded engine: its first stage is retrieve(), its second score_candidates()"""
+        self._refuse_diversity(diversity)
         raise _lib.TcarError("recommend_two_stage() needs the whole catalog on one engine (no shard): the catalog-sharded engine "
                              "has neither retrieve() nor score_candidates()")
 
@@ -1037,10 +1048,14 @@ class ShardedEngine(TcarEngine):
         return out
 
     def shard_recommend_two_stage(self, batch, k: int = 20, shortlist: int = 256, exclude_seen: bool = True, exclude=None,
-                                  panel: Optional[int] = None, window=None, cap: Optional[int] = None, T: Optional[int] = None):
+                                  panel: Optional[int] = None, window=None, cap: Optional[int] = None, T: Optional[int] = None,
+                                  diversity=None):
         """TcarEngine.recommend_two_stage over the shards: (topk [B, k] int32, scores [B, k] f32), the k best of the shortlist's exact
         scores, each slot scored by the shard that owns its row (the bits a whole-catalog engine computes from the same operands).
-        A COLLECTIVE, as shard_retrieve.  `last_shortlist` / `last_exact` hold the shortlist [B, shortlist] and its exact scores."""
+        A COLLECTIVE, as shard_retrieve.  `last_shortlist` / `last_exact` hold the shortlist [B, shortlist] and its exact scores.
+        diversity: refused — the MMR walk of include/tcar_mmr.h is not run over shards yet (every rank keeps the fp32 image E whole,
+        so the owner rank of a session could run it)."""
+        self._refuse_diversity(diversity)
         pc = self.retrieve_pieces(batch, shortlist, k, exclude_seen, exclude, panel, window, cap, T)
         out = self.xch.retrieve(pc, pc.cap, True)
         self.poll_fork_errors()

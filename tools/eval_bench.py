@@ -34,7 +34,8 @@ coarse scores) and recommend_two_stage (shortlist C, re-scored exactly, cut to K
 rounds: ms per step (upload included in all three), the agreement of the two-stage lists with the streamed ones (mean share of a
 streamed list found in the two-stage list, and the share of sessions whose lists are equal), and the two selectors alone — device
 events around one fold of the panel the last step left in the panel buffer into a fresh state, tcar_select_panel at K beside
-tcar_retrieve_panel at C.
+tcar_retrieve_panel at C.  --diversity MU adds recommend_two_stage(diversity=MU) (include/tcar_mmr.h) between two runs of the plain
+two-stage call, and the tcar_mmr_walk launch alone on the buffers the call left: at k and at k = 1 (the gather with one pick).
 
        python tools/eval_bench.py [iters] [--n_items N] --retrieve C[,C...] --sharded W [--k K] [--panel P] [--rounds R]
 
@@ -95,6 +96,9 @@ ap.add_argument("--sharded", type=int, default=0, help="W: the catalog-sharded e
 ap.add_argument("--candidates", type=str, default="", help="comma-separated list lengths C (1 .. 1024) for score_candidates")
 ap.add_argument("--retrieve", type=str, default="", help="comma-separated shortlist lengths C (1 .. 1024) for retrieve / recommend_two_stage")
 ap.add_argument("--sections", type=str, default="", help="comma-separated section counts G (1 .. 16) for recommend_sections")
+ap.add_argument("--diversity", type=float, default=0.0,
+                help="MU > 0 (with --retrieve, one engine): also time recommend_two_stage(diversity=MU) (include/tcar_mmr.h), interleaved "
+                     "with the plain two-stage call, and the tcar_mmr_walk launch alone with the bytes/s of its gather")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve) and of a section (with --sections)")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
@@ -386,6 +390,32 @@ if shorts:
             print("N=%d round %d C=%d: retrieve %.3f ms (%.3f of recommend), recommend_two_stage %.3f ms (%.3f of recommend); one fold of "
                   "%d columns alone: select k=%d %.4f ms, retrieve C=%d %.4f ms" % (
                       N, rnd, c, dr * 1e3, dr / dt, d2 * 1e3, d2 / dt, min(eng.panel_buf.shape[1], N), K, fs, c, fr))
+            if a.diversity > 0:
+                # interleaved with the plain call of the same build: plain, diversified, plain; the walk alone on the buffers the
+                # diversified call left (device events around `iters` launches), k = 1 being the gather with no round behind it
+                g = eng.geo
+                dd = timed_host(lambda f: eng.recommend_two_stage(f, k=K, shortlist=c, panel=P, diversity=a.diversity))
+                d3 = timed_host(lambda f: eng.recommend_two_stage(f, k=K, shortlist=c, panel=P))
+                eng.recommend_two_stage(feeds[0], k=K, shortlist=c, panel=P, diversity=a.diversity)
+                vp = lambda t, off=0: C_.c_void_p(t.data_ptr() + 4 * off)
+
+                def walk_alone(kk):
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                    for it in range(5 + iters):
+                        if it == 5:
+                            ev[0].record()
+                        eng.lib.tcar_mmr_walk(B, c, kk, a.diversity, g.N, g.H, vp(eng.E, g.ldh), g.ek, vp(eng.rt_ids), c, vp(eng.rt_exact), c,
+                                              vp(eng.rt_rank[1]), vp(eng.rt_topk), vp(eng.rt_topscore), vp(eng.rt_msim), eng._stream())
+                    ev[1].record()
+                    torch.cuda.synchronize()
+                    return ev[0].elapsed_time(ev[1]) / iters
+                wk, w1 = walk_alone(K), walk_alone(1)
+                pool = int(((eng.rt_ids[:B] >= 0).sum(1).clamp(max=256)).sum().item())
+                gathered = pool * g.H * 4
+                print("N=%d round %d C=%d diversity=%g: two-stage %.3f / %.3f ms around diversified %.3f ms (+%.3f ms); walk alone k=%d "
+                      "%.4f ms = %.3f of the diversified call; k=1 (the gather and one pick) %.4f ms: %.1f MB of rows = %.2f TB/s; %.4f ms "
+                      "per further round" % (N, rnd, c, a.diversity, d2 * 1e3, d3 * 1e3, dd * 1e3, (dd - 0.5 * (d2 + d3)) * 1e3, K, wk,
+                                             wk / (dd * 1e3), w1, gathered / 1e6, gathered / (w1 * 1e-3) / 1e12, (wk - w1) / max(K - 1, 1)))
         sys.stdout.flush()
     sys.exit(0)
 sects = [int(g) for g in a.sections.split(",") if g]
