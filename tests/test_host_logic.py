@@ -168,6 +168,47 @@ def test_c_abi_rejects_bad_arguments_without_touching_a_gpu():
     assert lib.tcar_clip_adam_rest(16, 832, 16, 16, 16, 10, 256, 0, 16, 16, 16, 1.0, 1e-3, 0.9, 0.999, 1e-8, None, None, 0,
                                    None, None) == -1
     assert lib.tcar_cand_time_bwd_indexed(C.byref(d), None, None, None, None, 0, None, None, None) == -1
+    # the grouped GEMMs: every refusal fill_prob documents (csrc/gemm_f32.hip).  Each descriptor is a launchable one (dummy
+    # 16-byte-aligned addresses, never dereferenced) but for the ONE field named, so the refusal is that field's
+    from tcar_amd._lib import GemmDesc
+
+    def desc(nseg=1, M=4, N=4, **kw):
+        g = GemmDesc()
+        g.nseg, g.M, g.N, g.C, g.ldc, g.splitk = nseg, M, N, 16, 4, 1
+        for s in range(min(nseg, 3)):
+            g.A[s], g.B[s], g.lda[s], g.ldb[s], g.K[s] = 16, 16, 64, 64, 64
+        for k, v in kw.items():
+            setattr(g, k, v)
+        return g
+
+    def call(entry, *descs, nprob=None):
+        return getattr(lib, entry)(0, len(descs) if nprob is None else nprob, (GemmDesc * max(len(descs), 1))(*descs), None)
+
+    planes = dict(plane_hi=16, plane_lo=16, plane_inner=32, plane_col0=0)
+    for entry in ("tcar_gemm_f32_grouped", "tcar_gemm_x3_grouped"):
+        assert call(entry, desc(nseg=0)) == -1 and call(entry, desc(nseg=4)) == -1
+        assert call(entry, *[desc() for _ in range(11)]) == -1                                       # more than 10 problems
+        for bad in (dict(bias=16), dict(act=1), dict(beta=1), dict(nseg=2)):                          # split K is plain and single
+            assert call(entry, desc(splitk=2, **bad)) == -1, (entry, bad)
+        assert call(entry, desc(), desc(nseg=0)) == -1                                               # any problem of the group
+        # no-ops: a group of empty problems only, and no problems at all
+        assert call(entry, desc(M=0), desc(N=0), desc(M=0, nseg=0)) == 0
+        assert call(entry, nprob=0) == 0
+    x3_bad = [dict(dact=3, dact_y=16, ld_dact_y=4), dict(dact=1), dict(dact=2),                    # dact in {1, 2}, with dact_y
+              dict(plane_hi=16, plane_inner=32), dict(planes, plane_inner=48), dict(planes, plane_inner=0),
+              dict(planes, plane_col0=29), dict(planes, plane_col0=-1),                               # col0 + N <= plane_inner
+              dict(pack_hi=16, pack_lo=16, pack_inner=32, pack_c0=0, pack_c1=0),                      # a pack pair needs planes
+              dict(planes, pack_hi=16, pack_inner=32), dict(planes, pack_hi=16, pack_lo=16, pack_inner=40),
+              dict(planes, pack_hi=16, pack_lo=16, pack_inner=32, pack_c0=3, pack_c1=2),
+              dict(dact=1, dact_y=16, ld_dact_y=4, splitk=2), dict(planes, splitk=2)]                 # neither with split K
+    for bad in x3_bad:
+        assert call("tcar_gemm_x3_grouped", desc(**bad)) == -1, bad
+    # tcar_gemm_splitk_effective against its restatement (K is cut in multiples of 32: fewer chunks than requested)
+    import gemm_ref
+    for K in range(1, 301):
+        for s in range(0, 41):
+            assert lib.tcar_gemm_splitk_effective(K, s) == gemm_ref.eff_split(K, s)[1], (K, s)
+    assert lib.tcar_gemm_splitk_effective(96, 7) == 3 and lib.tcar_gemm_splitk_effective(28, 3) == 1
 
 
 def test_geometry_and_arena_cover_all_variables():
