@@ -8,6 +8,7 @@
 #include "../../include/tcar_retrieve_shard.h"
 #include "../../include/tcar_sections.h"
 #include "../../include/tcar_mmr.h"
+#include "../../include/tcar_similar.h"
 #include "panel_fold.h"
 #include <stdlib.h>
 
@@ -1528,6 +1529,29 @@ extern "C" int tcar_mmr_rerank_step_ragged(const tcar_ctx_t* c, const tcar_batch
                                            const tcar_retrieve_t* d, const tcar_rerank_t* r, const tcar_mmr_t* m, void* stream) {
   return m && ragged ? retrieve_rerank_step(c, bt, static_cast<const tcar_ragged_t*>(ragged), refresh_time, d, r, stream, m)
                      : (int)TCAR_E_ARG;
+}
+
+// Related items (include/tcar_similar.h): no session forward — the query rows and their 1 / norm once, then per panel of the content
+// columns of E the cosine block into panel_buf and the unlabelled fold every streamed list call uses, and the finish.
+extern "C" int tcar_similar_step(const tcar_ctx_t* c, int Q, const tcar_similar_t* q, const tcar_serve_t* s, const tcar_window_t* w,
+                                 const tcar_quota_t* quota, void* stream) {
+  if (!c || Q < 0 || !q) return TCAR_E_ARG;
+  RET(check_serve_desc(s, w, quota, true));
+  if (s->state_bytes < tcar_select_state_bytes(Q, s->k) || !q->qid == !q->qrow || !q->xq || !q->rq || !c->E) return TCAR_E_ARG;
+  const Geo g(c->d);
+  if (g.N < 1 || g.H < 1 || g.ldh < g.H || (q->qrow && q->ld_qrow < g.H)) return TCAR_E_ARG;
+  if (Q == 0) return TCAR_OK;
+  const float* content = c->E + g.ldh;
+  RET(tcar_sim_queries(Q, g.N, g.H, content, g.ek, q->qid, q->qrow, q->ld_qrow, q->xq, g.ldh, q->rq, stream));
+  RET(tcar_select_reset(Q, s->k, s->state, stream));
+  for (int n0 = 0; n0 < g.N; n0 += s->panel) {
+    const int n = g.N - n0 < s->panel ? g.N - n0 : s->panel;
+    RET(tcar_sim_panel(Q, n0, n, g.H, content, g.ek, q->xq, g.ldh, q->rq, s->panel_buf, s->panel, stream));
+    RET(tcar_select_panel_quota(Q, n0, n, s->panel_buf, s->panel, s->k, nullptr, nullptr, s->excl, s->X, s->state, stream,
+                                w ? w->key : nullptr, w ? w->lo : nullptr, w ? w->hi : nullptr, quota ? quota->cat : nullptr,
+                                quota ? quota->cap : 0));
+  }
+  return tcar_select_finish(Q, s->k, s->state, nullptr, s->topk, s->score, nullptr, nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -1565,6 +1565,97 @@ class TcarEngine(OpLevelStep):
                                      self._stream()), "tcar_mmr_walk")
         return self.dv_topk[:B], self.dv_topscore[:B], self.dv_msim[:B]
 
+    # ---- related items by content cosine (include/tcar_similar.h): no session, no model — the content table under the panel folds
+    def _similar_request(self, ids, k, content, exclude_self, exclude, panel: Optional[int], window, max_per_category):
+        """The request of a similar_items call, validated before anything is uploaded -> (Q, qid int32 [Q] or None, rows f32 [Q, H]
+        or None, excl int32 [Q, X] or None, (lo, hi) or None, quota or None, panel).  An id outside [0, N) becomes -1, the empty
+        query."""
+        g = self.geo
+        if (ids is None) == (content is None):
+            raise ValueError("similar_items takes exactly one of ids (catalog rows) and content (rows that are in no catalog)")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64:
+            raise ValueError("k must be an int in [1, 64]")
+        qid = rows = None
+        if ids is not None:
+            a = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+            if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_:
+                raise ValueError("ids must be an integer array [Q], Q >= 1 (0-based catalog rows; -1: an empty query)")
+            a64 = a.astype(np.int64)
+            qid = np.ascontiguousarray(np.where((a64 < 0) | (a64 >= g.N), -1, a64), dtype=np.int32)
+        else:
+            a = content.detach().cpu().numpy() if isinstance(content, torch.Tensor) else np.asarray(content)
+            if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] != g.H or not np.issubdtype(a.dtype, np.floating):
+                raise ValueError("content must be a float array [Q, H = %d], Q >= 1" % g.H)
+            rows = np.ascontiguousarray(a, dtype=np.float32)
+        Q = int(a.shape[0])
+        if not isinstance(exclude_self, (bool, np.bool_)):
+            raise ValueError("exclude_self must be True or False")
+        parts = [qid[:, None]] if qid is not None and exclude_self else []
+        if exclude is not None:
+            ex = exclude.detach().cpu().numpy() if isinstance(exclude, torch.Tensor) else np.asarray(exclude)
+            if ex.ndim != 2 or ex.shape[0] != Q or not np.issubdtype(ex.dtype, np.integer):
+                raise ValueError("exclude must be an integer array [Q, X] with Q = %d queries" % Q)
+            e64 = ex.astype(np.int64)
+            if ex.shape[1]:
+                parts.append(np.where((e64 < 0) | (e64 >= 2 ** 31), -1, e64).astype(np.int32))
+        excl = np.ascontiguousarray(np.concatenate(parts, axis=1)) if parts else None
+        quota = self._quota(max_per_category) if max_per_category is not None else None
+        panel = self._panel_request(panel, window, g.Npad)
+        bounds = self._window_bounds(window, Q) if window is not None else None
+        return Q, qid, rows, excl, bounds, quota, panel
+
+    def similar_items(self, ids=None, k: int = 20, content=None, exclude_self: bool = True, exclude=None, panel: Optional[int] = None,
+                      window=None, max_per_category: Optional[int] = None):
+        """The k catalog items whose CONTENT is most similar to each of Q query rows: (topk [Q, k] int32, sims [Q, k] f32), best
+        first (cosine, then item id, descending); -1 (and a sim of 0) where fewer than k items are eligible.  The cosine is the
+        `sim` of include/tcar_mmr.h over the frozen fp32 content columns, bit for bit what diversify() / `rt_msim` report for the
+        same pair.  Exactly one of `ids` (int [Q], 0-based catalog rows; an id outside the catalog, e.g. -1, is an empty query and
+        lists -1) and `content` (float [Q, H]: drafts that are in no catalog).  exclude_self (ids only) keeps a query out of its
+        own list; exclude [Q, X], window = (lo, hi) per query, max_per_category and panel as recommend() takes them.  No session
+        forward and no [Q, N] matrix: one cosine panel and one fold per `panel` columns (include/tcar_similar.h), ordered on the
+        engine's stream behind every earlier update_items.  Views of the workspace, valid until the next streamed call."""
+        Q, qid, rows, excl, bounds, quota, panel = self._similar_request(ids, k, content, exclude_self, exclude, panel, window,
+                                                                         max_per_category)
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("similar_items needs the whole catalog on this engine (no shard)")
+        k = int(k)
+        self.flush()
+        words = int(self.lib.tcar_select_state_bytes(1, k)) // 4
+        self._sm_rows = max(getattr(self, "_sm_rows", 0), Q)
+        specs = [Spec("panel_buf", (Q, panel), F32), Spec("sel_state", (Q, words), I32), Spec("sel_topk", (Q, k), I32),
+                 Spec("sel_score", (Q, k), F32), Spec("sm_xq", (Q, g.ldh), F32), Spec("sm_rq", (Q,), F32)]
+        specs.append(Spec("sm_qid", (Q,), I32) if qid is not None else Spec("sm_qrow", (Q, g.H), F32))
+        if excl is not None:
+            specs.append(Spec("excl", (Q, int(excl.shape[1])), I32))
+        if bounds is not None:
+            specs.append(Spec("sm_lohi", (2, self._sm_rows), I32))
+        self.ws.ensure(specs)
+        d = _lib.Similar()
+        d.xq, d.rq = self.sm_xq.data_ptr(), self.sm_rq.data_ptr()
+        if qid is not None:
+            self.sm_qid[:Q].copy_(torch.from_numpy(qid))
+            d.qid = self.sm_qid.data_ptr()
+        else:
+            self.sm_qrow[:Q].copy_(torch.from_numpy(rows))
+            d.qrow, d.ld_qrow = self.sm_qrow.data_ptr(), g.H
+        s = self._serve_desc(k, panel, self.panel_buf, self.sel_state, outputs=(self.sel_topk, self.sel_score))
+        if excl is not None:
+            self.excl[:Q].copy_(torch.from_numpy(excl))
+            s.excl, s.X = self.excl.data_ptr(), int(excl.shape[1])
+        w = None
+        if bounds is not None:
+            self.sm_lohi[:, :Q].copy_(torch.from_numpy(np.stack(bounds)))
+            w = self._window_desc(self._item_keys, self.sm_lohi)
+        self.sel_score[:Q].zero_()             # (the finish leaves the score of an empty place untouched: it reads 0)
+        check(self.lib.tcar_similar_step(C.byref(self._catalog_ctx()), Q, C.byref(d), C.byref(s), C.byref(w) if w is not None else None,
+                                         C.byref(quota) if quota is not None else None, self._stream()), "tcar_similar_step")
+        if qid is not None and (qid < 0).any():    # an empty query lists nothing (the kernels scored a zero row)
+            gone = torch.from_numpy(np.flatnonzero(qid < 0)).to(self.dev)
+            self.sel_topk[gone] = -1
+            self.sel_score[gone] = 0.0
+        return self.sel_topk[:Q], self.sel_score[:Q]
+
 
 class SectionLists(NamedTuple):
     """what TcarEngine.recommend_sections returns: device views, valid until the next streamed call"""

@@ -48,6 +48,7 @@ MAX_PANEL = 49152          # the widest panel a fold takes (SEL_MAX_N of csrc/tc
 
 
 MAX_SECTIONS = 16          # sections of one sectioned call (engine.TcarEngine.MAX_SECTIONS; TCAR_MAX_SECTIONS of include/tcar_sections.h)
+MAX_RELATED = 64           # entries of one related-articles list (the k of engine.TcarEngine.similar_items; SEL_MAX_K of csrc/tcar_common.h)
 MAX_SHORTLIST = 1024       # entries of one shortlist (engine.TcarEngine.RETRIEVE_MAX_C); a list of up to 64 needs no first stage
 MAX_CANDIDATES = 1024      # slots of one candidate list (CAND_MAX_C of csrc/tcar_common.h; engine.TcarEngine.CAND_MAX_C)
 
@@ -119,6 +120,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "the G categories with the most catalog items, all from one pass over the catalog) and prints the share of "
                          "labels found in the list of their own category; 1 <= G <= " + str(MAX_SECTIONS) + ".  Needs --eval_panel; "
                          "combines with --fresh_hours and --eval_mixed; not with --dp_mode sharded.  0: off")
+    ap.add_argument("--eval_related", default=0, type=int,
+                    help="K > 0: evaluation additionally lists, once behind its batches, the K articles most similar in CONTENT to every "
+                         "distinct label article of the data (include/tcar_similar.h: the content cosine of the diversity re-rank, the "
+                         "catalog streamed in panels, no session) and prints their mean cosine and the share that is of the article's own "
+                         "category; 1 <= K <= " + str(MAX_RELATED) + ".  Not with --dp_mode sharded.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
@@ -167,6 +173,20 @@ def check_eval_sections(eval_sections, eval_panel, dp_mode):
     if eval_sections > MAX_SECTIONS:
         raise ValueError("--eval_sections must be in [1, %d] (0: off)" % MAX_SECTIONS)
     _check_streamed_option("eval_sections", eval_sections, "lists the categories beside", "list per category", eval_panel, dp_mode)
+
+
+def check_eval_related(eval_related, dp_mode):
+    """--eval_related lists the articles related to every label article (include/tcar_similar.h), which takes the whole catalog on
+    one engine"""
+    if isinstance(eval_related, bool) or not isinstance(eval_related, (int, np.integer)):
+        raise ValueError("--eval_related must be an integer in [1, %d] (0: off)" % MAX_RELATED)
+    if not eval_related:
+        return
+    if eval_related < 1 or eval_related > MAX_RELATED:
+        raise ValueError("--eval_related must be in [1, %d] (0: off)" % MAX_RELATED)
+    if dp_mode == "sharded":
+        raise ValueError("--eval_related reads the content of the WHOLE catalog on one engine; it cannot be combined with "
+                         "--dp_mode sharded")
 
 
 def check_shard_eval_panel(shard_eval_panel, dp_mode):
@@ -312,6 +332,7 @@ def main(argv=None):
     check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
     check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
     check_eval_sections(args.eval_sections, args.eval_panel, args.dp_mode)
+    check_eval_related(args.eval_related, args.dp_mode)
     check_eval_candidates(args.eval_candidates, args.dp_mode)
     check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
     check_eval_diversity(args.eval_diversity, args.eval_shortlist, args.dp_mode)

@@ -45,6 +45,17 @@ def section_hits(topk, labels, cat, sections):
     return covered & (own == labels[:, None]).any(1), covered
 
 
+def related_sums(topk, sims, ids, cat):
+    """Related lists topk [Q, k] (0-based ids, -1 = no entry) with their cosines sims [Q, k] of the articles ids [Q] -> (the sum
+    of the listed cosines in double precision, the number of listed items of their article's own category).  Divide both by
+    (topk >= 0).sum(): mean cosine, same-category share."""
+    topk, cat = np.asarray(topk), np.asarray(cat)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    listed = topk >= 0
+    same = listed & (cat[np.where(listed, topk, 0)] == cat[ids][:, None])
+    return float(np.asarray(sims, dtype=np.float64)[listed].sum()), float(same.sum())
+
+
 def cau_metrics(preds, labels, cutoff=20):
     """Same contract as util.py:8-18: rank = 1 + #{j: preds[j] > preds[label]} (strict)."""
     preds = np.asarray(preds)

@@ -147,6 +147,7 @@ class Seq2SeqAttNN():
         self.eval_diversity = self._eval_diversity(args)             # MU > 0: test() also runs the DIVERSIFIED two-stage recommendation
         self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
         self.eval_sections = self._eval_sections(args)               # G > 0: test() also asks for one list per category (G of them)
+        self.eval_related = self._eval_related(args)                 # K > 0: test() also lists the K related articles of every label article
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -235,6 +236,12 @@ class Seq2SeqAttNN():
         panel, nsec = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'eval_sections'))
         cli.check_eval_sections(nsec, panel, args.get('dp_mode', 'replica'))
         return nsec
+
+    def _eval_related(self, args) -> int:
+        """eval_related of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
+        nrel = args.get('eval_related', getattr(self, 'eval_related', 0)) or 0
+        cli.check_eval_related(nrel, args.get('dp_mode', 'replica'))
+        return int(nrel)
 
     def _packs(self, feeds, mixed: bool):
         """test(): the sampler's feeds grouped into the packs of one streamed call each — consecutive feeds, never splitting one,
@@ -482,6 +489,7 @@ class Seq2SeqAttNN():
         # eval_sections: the categories with the most catalog items are the sections (include/tcar_sections.h), 20 items each
         sections = M.largest_categories(self._category_table(), nsec) if nsec else None
         sec_pending = []
+        nrel = self._eval_related(args)
 
         def section_lists(feeds, window):
             """the sectioned lists of the sessions of `feeds` (one feed, or the feeds of a pack: one ragged call), kept for the drain"""
@@ -638,6 +646,22 @@ class Seq2SeqAttNN():
             print('sections ({} categories, 20 per section): Recall@20 in the label\'s section: {}, labels in a listed section: {}'.format(
                 len(sections), s_recall, s_share))
             self.last_metrics["sections"] = {"G": int(len(sections)), "recall": s_recall, "covered": s_share}
+        if nrel:
+            # eval_related: the related articles (include/tcar_similar.h) of every distinct label article of this rank's sessions,
+            # batch_size queries a call; the sums go over the ranks
+            cat = self._category_table()
+            arts = np.unique(np.concatenate([np.asarray(p[0]["label"], dtype=np.int64).reshape(-1) for p in pending])) if pending \
+                else np.zeros(0, np.int64)
+            tot = np.zeros(4)
+            for i in range(0, len(arts), max(int(self.batch_size), 1)):
+                ids = arts[i:i + max(int(self.batch_size), 1)]
+                tk, sims = (t.cpu().numpy() for t in eng.similar_items(ids, k=nrel))
+                cos, same = M.related_sums(tk, sims, ids, cat)
+                tot += [cos, same, float((tk >= 0).sum()), float(len(ids))]
+            tot = self._allsum(tot.tolist())
+            r_cos, r_same = tot[0] / max(tot[2], 1.0), tot[1] / max(tot[2], 1.0)
+            print('related articles ({} per article): mean cosine: {}, same category: {}'.format(nrel, r_cos, r_same))
+            self.last_metrics["related"] = {"k": nrel, "mean_cosine": r_cos, "same_category": r_same, "articles": int(tot[3])}
         if fresh:           # (these labels are still scored: a label is always in its session's pool)
             share = self._allsum([float(np.sum(outside))])[0] / n
             print('labels outside their window: {}'.format(share))
@@ -690,6 +714,26 @@ class Seq2SeqAttNN():
         if window is not None:
             self._item_keys()
         return self.engine.recommend_sections(sessions, sections, k=k, window=window, **kw)
+
+    def related_articles(self, ids, k=10, window=None, max_per_category=None, **kw):
+        """The k articles whose CONTENT is most similar to each article of `ids` (int [Q], 0-based as the lists `recommend` returns):
+        (topk [Q, k] int32, cosines [Q, k] f32) on the device, best first, the article itself left out, -1 where fewer than k are
+        eligible.  No session and no model: the cosine of the frozen content rows, the one the diversity re-rank charges
+        (engine.TcarEngine.similar_items has the options: exclude_self, exclude, panel).  window = (lo, hi), scalars or arrays [Q],
+        in minutes since the earliest publish time, and max_per_category as in `recommend`.  Not on the catalog-sharded engine."""
+        return self._similar(dict(ids=ids), k, window, max_per_category, kw)
+
+    def similar_to_content(self, rows, k=10, window=None, max_per_category=None, **kw):
+        """`related_articles` for rows that are in no catalog — float [Q, H] content vectors, e.g. a draft before update_articles
+        publishes it: is this story already in the catalog?"""
+        return self._similar(dict(content=rows), k, window, max_per_category, kw)
+
+    def _similar(self, query, k, window, max_per_category, kw):
+        if window is not None:
+            self._item_keys()
+        if max_per_category is not None:
+            self._install_categories()
+        return self.engine.similar_items(k=k, window=window, max_per_category=max_per_category, **query, **kw)
 
     def retrieve(self, sessions, C, window=None, **kw):      # noqa: N803
         """A shortlist of the C best next items (1 <= C <= 1024) of every session of `sessions` — a feed dict as `recommend` takes

@@ -934,6 +934,13 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("recommend_sections() needs the whole catalog on one engine (no shard): sections over shards are not "
                              "built yet")
 
+    def similar_items(self, ids=None, k: int = 20, content=None, exclude_self: bool = True, exclude=None, panel: Optional[int] = None,
+                      window=None, max_per_category: Optional[int] = None):
+        """not on the catalog-sharded engine (TcarEngine.similar_items is written for a whole-catalog engine and its workspace; the
+        form over shards is not built)"""
+        raise _lib.TcarError("similar_items() needs the whole catalog on one engine (no shard): related items over shards are not "
+                             "built yet")
+
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
         """not under this name on the catalog-sharded engine (include/tcar_catalog.h takes the whole catalog): a row's derived state
         lives on the rank that owns it and the ranks have to agree on the update — that is shard_update_items(), a collective"""

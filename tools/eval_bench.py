@@ -63,6 +63,15 @@ ragged feed of the same sessions (include/tcar_ragged.h), alternating for `round
 both.  Then the head alone, device events around tcar_ragged_forward on resident batches: one ragged head of all 512 sessions beside
 the heads of the buckets (each a ragged call of uniform lengths, which runs exactly the launches of the rectangular head).
 
+       python tools/eval_bench.py [iters] [--n_items N] --similar Q [--k K] [--panel P] [--rounds R]
+
+--similar Q: TcarEngine.similar_items (include/tcar_similar.h) for Q random catalog ids, K items each, beside what a user without it
+writes in torch on the same content table: normalize(content) @ normalize(content[q]).T, then torch.topk over the [N, Q] matrix it
+materialises — once as written (the table normalised in every call) and once with the normalised table kept between calls.  Host
+clock around `iters` calls ending in a device synchronise, the upload of the ids included in all three, alternating for `rounds`
+rounds.  Then the split of the call on the device: events around the whole tcar_similar_step and around its cosine panels alone
+(tcar_sim_panel over every panel, on the buffers the call left); the rest is the folds with the prologue and the finish.
+
        python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --update U[,U...] [--sharded W] [--rounds R]
 
 --update U: TcarEngine.update_items (include/tcar_catalog.h) of U random distinct rows on an engine whose time block is clean (so the
@@ -100,6 +109,7 @@ ap.add_argument("--diversity", type=float, default=0.0,
                 help="MU > 0 (with --retrieve, one engine): also time recommend_two_stage(diversity=MU) (include/tcar_mmr.h), interleaved "
                      "with the plain two-stage call, and the tcar_mmr_walk launch alone with the bytes/s of its gather")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve) and of a section (with --sections)")
+ap.add_argument("--similar", type=int, default=0, help="Q: similar_items for Q catalog ids beside the torch workaround that materialises [N, Q]")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
 ap.add_argument("--scoring", type=str, default="bf16x3-mixed", help="scoring mode of the engine (f32 | bf16x3 | bf16x3-mixed | bf16)")
@@ -416,6 +426,78 @@ if shorts:
                       "%.4f ms = %.3f of the diversified call; k=1 (the gather and one pick) %.4f ms: %.1f MB of rows = %.2f TB/s; %.4f ms "
                       "per further round" % (N, rnd, c, a.diversity, d2 * 1e3, d3 * 1e3, dd * 1e3, (dd - 0.5 * (d2 + d3)) * 1e3, K, wk,
                                              wk / (dd * 1e3), w1, gathered / 1e6, gathered / (w1 * 1e-3) / 1e12, (wk - w1) / max(K - 1, 1)))
+        sys.stdout.flush()
+    sys.exit(0)
+if a.similar:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--similar needs the whole catalog on one engine: not with --sharded")
+    Q, K, g = a.similar, a.k, eng.geo
+    P = ([int(p) for p in a.panel.split(",") if p] or [0])[0] or None
+    rng = np.random.RandomState(5)
+    queries = [rng.choice(N, Q, replace=False).astype(np.int32) for _ in range(8)]
+    table = eng.E[:N, g.ldh:g.ldh + g.H]                 # the content columns in place (a strided view)
+    kept = torch.nn.functional.normalize(table, dim=1)
+
+    def ours(q):
+        return eng.similar_items(q, k=K, exclude_self=False, panel=P)
+
+    def as_written(q):
+        xn = torch.nn.functional.normalize(table, dim=1)
+        return torch.topk(xn @ xn[torch.from_numpy(q).to(eng.dev).long()].T, K, dim=0)
+
+    def table_kept(q):
+        return torch.topk(kept @ kept[torch.from_numpy(q).to(eng.dev).long()].T, K, dim=0)
+
+    def timed_host(step):
+        for i in range(3):
+            step(queries[i % len(queries)])
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(iters):
+            step(queries[i % len(queries)])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / iters
+
+    def on_device():
+        """ms of the whole tcar_similar_step and of its cosine panels alone, device events, on the buffers the last call left"""
+        lib, st = eng.lib, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        ours(queries[0])
+        ld = eng.panel_buf.shape[1]
+        cp = C_.c_void_p(eng.E.data_ptr() + 4 * g.ldh)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        qd = torch.from_numpy(queries[0]).to(eng.dev)
+        from tcar_amd import _lib as L_
+        d, s_ = L_.Similar(), eng._serve_desc(K, ld, eng.panel_buf, eng.sel_state, outputs=(eng.sel_topk, eng.sel_score))
+        d.qid, d.xq, d.rq = qd.data_ptr(), eng.sm_xq.data_ptr(), eng.sm_rq.data_ptr()
+        ctx = eng._catalog_ctx()
+        for it in range(3 + iters):
+            if it == 3:
+                ev[0].record()
+            assert lib.tcar_similar_step(C_.byref(ctx), Q, C_.byref(d), C_.byref(s_), None, None, st) == 0
+        ev[1].record()
+        for it in range(iters):
+            for n0 in range(0, N, ld):
+                assert lib.tcar_sim_panel(Q, n0, min(ld, N - n0), g.H, cp, g.ek, vp(eng.sm_xq), g.ldh, vp(eng.sm_rq), vp(eng.panel_buf), ld, st) == 0
+        ev[2].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters, ev[1].elapsed_time(ev[2]) / iters, (N + ld - 1) // ld, ld
+
+    # the same lists?  outside the timed loops; rounding may order near-ties differently, so the share of equal lists is reported
+    got = ours(queries[0])[0].clone().cpu().numpy()
+    want = table_kept(queries[0])[1].T.cpu().numpy()
+    inter = np.mean([len(set(x.tolist()) & set(y.tolist())) / float(K) for x, y in zip(got, want)])
+    print("N=%d Q=%d k=%d: lists equal to the workaround's in %.3f of the queries, mean overlap %.4f" % (
+        N, Q, K, float((got == want).all(1).mean()), inter))
+    for rnd in range(a.rounds):
+        do, dw, dk = timed_host(ours), timed_host(as_written), timed_host(table_kept)
+        whole, panels, npan, ld = on_device()
+        flops = 2.0 * Q * N * ((g.H + 7) // 8 * 8)
+        print("N=%d Q=%d k=%d round %d: similar_items %.3f ms; workaround as written %.3f ms (%.2fx), with the normalised table kept "
+              "%.3f ms (%.2fx); on the device: the step %.3f ms, its %d cosine panels of %d columns alone %.3f ms (%.1f TFLOP/s fp32), "
+              "folds + prologue + finish %.3f ms" % (N, Q, K, rnd, do * 1e3, dw * 1e3, dw / do, dk * 1e3, dk / do, whole, npan, ld, panels,
+                                                    flops / (panels * 1e-3) / 1e12, whole - panels))
         sys.stdout.flush()
     sys.exit(0)
 sects = [int(g) for g in a.sections.split(",") if g]
