@@ -14,6 +14,7 @@ import os
 import pickle
 import random
 import sys
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -53,6 +54,166 @@ MAX_SHORTLIST = 1024       # entries of one shortlist (engine.TcarEngine.RETRIEV
 MAX_CANDIDATES = 1024      # slots of one candidate list (CAND_MAX_C of csrc/tcar_common.h; engine.TcarEngine.CAND_MAX_C)
 
 
+class Rule(NamedTuple):
+    """One refusal of an evaluation option.  kind and arg say when it applies, text is the refusal, word for word:
+      "type" (classes)       the value is a bool or none of `classes`; the only rule that also looks at a value that is off
+      "finite"               the value is NaN, infinite or negative
+      "range" (lo, hi, step) the value is below lo, above hi or no multiple of step (None: no such bound)
+      "engine" which         "one": the option takes ONE engine with the whole catalog, so not --dp_mode sharded;
+                             "sharded": it takes the catalog-sharded engine, so only --dp_mode sharded
+      "one_process"          more than one data-parallel rank
+      "needs" flag           `flag` is off
+      "excludes" flag        `flag` is on"""
+    kind: str
+    arg: object
+    text: str
+
+
+class EvalOption(NamedTuple):
+    """One option of the evaluation loop (host/model.py: test()): a command-line flag, a key of the model's args, 0 = off.  `rules`
+    holds its accepted range and what it needs and excludes, in the order they are checked."""
+    name: str
+    type: type
+    help: str
+    rules: Tuple[Rule, ...]
+
+
+def _panel_range(flag):
+    return Rule("range", (128, MAX_PANEL, 128), "--%s must be a multiple of 128 in [128, %d] (0: off)" % (flag, MAX_PANEL))
+
+
+def _in(flag, lo, hi):
+    return Rule("range", (lo, hi, None), "--%s must be in [%d, %d] (0: off)" % (flag, lo, hi))
+
+
+def _streamed(flag, what, takes):
+    """an option of the streamed evaluation of ONE engine: positive, refused under --dp_mode sharded, and it needs --eval_panel"""
+    return (Rule("range", (0, None, None), "--%s must be positive (0: off)" % flag),
+            Rule("engine", "one", "--%s %s the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded" % (flag, what)),
+            Rule("needs", "eval_panel", "--%s needs --eval_panel P: only the streamed evaluation takes a %s" % (flag, takes)))
+
+
+# In the order check_eval_options walks them: a request that breaks several rules is refused with the first one.
+EVAL_OPTIONS = (
+    EvalOption("eval_panel", int,
+               "P > 0: evaluation scores the catalog P columns at a time and selects while it streams (no [B, N] score matrix, "
+               "any catalog size; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  0: the materialised evaluation.  Not with --dp_mode sharded",
+               (Rule("engine", "one", "--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded "
+                                      "(the catalog-sharded engine evaluates with its own exchange)"),
+                _panel_range("eval_panel"))),
+    EvalOption("fresh_hours", float,
+               "H > 0: evaluation ranks every session inside its POOL — the items published in the H hours up to the label's "
+               "click (and the label) — not against the whole catalog.  Needs --eval_panel; not with --dp_mode sharded.  0: off",
+               _streamed("fresh_hours", "windows", "publish-time window")),
+    EvalOption("cat_cap", int,
+               "M > 0: evaluation lists hold at most M items of one category (the walk of include/tcar_quota.h); ILD, unexp and "
+               "coverage describe the capped lists, and one more line gives their accuracy.  Needs --eval_panel; not with "
+               "--dp_mode sharded; combines with --fresh_hours.  0: off",
+               _streamed("cat_cap", "caps", "per-category cap")),
+    EvalOption("shard_eval_panel", int,
+               "P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
+               "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  "
+               "0: the materialised evaluation of the catalog-sharded engine",
+               (_panel_range("shard_eval_panel"),
+                Rule("engine", "sharded", "--shard_eval_panel streams the shards of the catalog-sharded engine: it needs --dp_mode sharded "
+                                          "(one engine with the whole catalog: --eval_panel)"))),
+    EvalOption("eval_sections", int,
+               "G > 0: evaluation additionally asks for one list of 20 per CATEGORY on every batch (include/tcar_sections.h: "
+               "the G categories with the most catalog items, all from one pass over the catalog) and prints the share of "
+               "labels found in the list of their own category; 1 <= G <= " + str(MAX_SECTIONS) + ".  Needs --eval_panel; "
+               "combines with --fresh_hours and --eval_mixed; not with --dp_mode sharded.  0: off",
+               (Rule("range", (None, MAX_SECTIONS, None), "--eval_sections must be in [1, %d] (0: off)" % MAX_SECTIONS),)
+               + _streamed("eval_sections", "lists the categories beside", "list per category")),
+    EvalOption("eval_related", int,
+               "K > 0: evaluation additionally lists, once behind its batches, the K articles most similar in CONTENT to every "
+               "distinct label article of the data (include/tcar_similar.h: the content cosine of the diversity re-rank, the "
+               "catalog streamed in panels, no session) and prints their mean cosine and the share that is of the article's own "
+               "category; 1 <= K <= " + str(MAX_RELATED) + ".  Not with --dp_mode sharded.  0: off",
+               (Rule("type", (int, np.integer), "--eval_related must be an integer in [1, %d] (0: off)" % MAX_RELATED),
+                _in("eval_related", 1, MAX_RELATED),
+                Rule("engine", "one", "--eval_related reads the content of the WHOLE catalog on one engine; it cannot be combined with "
+                                      "--dp_mode sharded"))),
+    EvalOption("eval_candidates", int,
+               "C > 0: evaluation additionally ranks every label among C - 1 other items drawn uniformly from the catalog "
+               "(include/tcar_cand.h: only those C rows are scored) and prints their AUC / MRR / nDCG@5 / nDCG@10; "
+               "2 <= C <= " + str(MAX_CANDIDATES) + ".  Not with --dp_mode sharded; combines with everything else.  0: off",
+               (_in("eval_candidates", 2, MAX_CANDIDATES),
+                Rule("engine", "one", "--eval_candidates scores candidate lists against the WHOLE catalog on one engine; it cannot be "
+                                      "combined with --dp_mode sharded"))),
+    EvalOption("eval_shortlist", int,
+               "C > 0: evaluation additionally runs the two-stage recommendation on every batch (include/tcar_retrieve.h: a "
+               "shortlist of C items from coarse scores, re-scored exactly and cut to 20) and prints the share of labels in those "
+               "lists and their agreement with the streamed lists; 65 <= C <= " + str(MAX_SHORTLIST) + ".  Needs --eval_panel; "
+               "not with --dp_mode sharded, not with --cat_cap.  0: off",
+               (_in("eval_shortlist", 65, MAX_SHORTLIST),
+                Rule("engine", "one", "--eval_shortlist retrieves from the WHOLE catalog on one engine; it cannot be combined with --dp_mode sharded"),
+                Rule("needs", "eval_panel", "--eval_shortlist needs --eval_panel P: its lists are compared with those of the streamed evaluation"),
+                Rule("excludes", "cat_cap", "--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap"))),
+    EvalOption("eval_diversity", float,
+               "MU > 0: evaluation additionally runs the DIVERSIFIED two-stage recommendation on every batch (include/tcar_mmr.h: "
+               "the shortlist's k best under the greedy MMR walk over content, a verbatim duplicate of a listed item losing MU "
+               "logits) and prints its Recall@20, ILD and content ILD beside those of the plain two-stage lists.  Needs "
+               "--eval_shortlist C; not with --dp_mode sharded.  0: off",
+               (Rule("type", (int, float, np.integer, np.floating), "--eval_diversity must be a number (0: off)"),
+                Rule("finite", None, "--eval_diversity must be a finite penalty > 0 (0: off)"),
+                Rule("engine", "one", "--eval_diversity diversifies the two-stage lists of ONE engine; it cannot be combined with --dp_mode sharded"),
+                Rule("needs", "eval_shortlist", "--eval_diversity needs --eval_shortlist C: the walk re-ranks the shortlist of the two-stage call"))),
+    EvalOption("shard_eval_shortlist", int,
+               "C > 0 (only with --dp_mode sharded and --shard_eval_panel P): evaluation additionally runs the two-stage "
+               "recommendation over the shards on every batch (include/tcar_retrieve_shard.h: every shard's shortlist of C items "
+               "from coarse scores merged exactly, re-scored by the rows' owners, cut to 20) and prints the line of "
+               "--eval_shortlist; 65 <= C <= " + str(MAX_SHORTLIST) + ".  0: off",
+               (_in("shard_eval_shortlist", 65, MAX_SHORTLIST),
+                Rule("engine", "sharded", "--shard_eval_shortlist merges the shortlists of the catalog-sharded engine: it needs --dp_mode sharded "
+                                          "(one engine with the whole catalog: --eval_shortlist)"),
+                Rule("needs", "shard_eval_panel", "--shard_eval_shortlist needs --shard_eval_panel P: its lists are compared with those of the "
+                                                  "streamed evaluation"))),
+    EvalOption("eval_mixed", int,
+               "1: evaluation packs consecutive batches of DIFFERENT session lengths into one ragged batch of at most "
+               "--batch_size sessions (include/tcar_ragged.h) and streams the catalog once per pack instead of once per batch.  "
+               "Needs --eval_panel; combines with --fresh_hours and --cat_cap; not with --dp_mode sharded, --gpus > 1, "
+               "--eval_candidates, --eval_shortlist.  0: one call per batch",
+               (Rule("range", (0, 1, None), "--eval_mixed must be 0 or 1"),
+                Rule("engine", "one", "--eval_mixed packs the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded"),
+                Rule("one_process", None, "--eval_mixed cannot be combined with --gpus > 1: the ranks split every batch by rows"),
+                Rule("needs", "eval_panel", "--eval_mixed needs --eval_panel P: only the streamed evaluation takes a ragged batch"),
+                Rule("excludes", "eval_candidates", "--eval_mixed cannot be combined with --eval_candidates"),
+                Rule("excludes", "eval_shortlist", "--eval_mixed cannot be combined with --eval_shortlist"))),
+)
+# where --help lists them (the order the flags were added in)
+_HELP_ORDER = ("eval_panel", "fresh_hours", "cat_cap", "shard_eval_panel", "shard_eval_shortlist", "eval_candidates", "eval_shortlist",
+               "eval_diversity", "eval_mixed", "eval_sections", "eval_related")
+# what Seq2SeqAttNN._eval_request resolves: every option under its name, in its type
+EvalRequest = NamedTuple("EvalRequest", [(o.name, o.type) for o in EVAL_OPTIONS])
+
+
+def check_eval_options(values, gpus=1):
+    """Refuse a request for the evaluation loop that cannot work: `values` maps dp_mode and any of the options of EVAL_OPTIONS to
+    their values (an absent option is off), `gpus` is the number of data-parallel ranks.  The options are walked in the table's
+    order, each one's rules in theirs, and the first broken rule is raised as a ValueError."""
+    sharded = values.get("dp_mode", "replica") == "sharded"
+    for opt in EVAL_OPTIONS:
+        v = values.get(opt.name, 0)
+        for kind, arg, text in opt.rules:
+            if kind == "type":
+                broken = isinstance(v, bool) or not isinstance(v, arg)
+            elif not v:
+                break                                        # off: nothing else of it to check
+            elif kind == "finite":
+                broken = v != v or v in (float("inf"), float("-inf")) or v < 0
+            elif kind == "range":
+                lo, hi, step = arg
+                broken = (lo is not None and v < lo) or (hi is not None and v > hi) or (step is not None and v % step)
+            elif kind == "engine":
+                broken = sharded if arg == "one" else not sharded
+            elif kind == "one_process":
+                broken = gpus and gpus > 1
+            else:
+                broken = not values.get(arg) if kind == "needs" else values.get(arg)
+            if broken:
+                raise ValueError(text)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="TCAR trainer (MI355X-native hot path)")
     for name, default, typ, hlp in REFERENCE_FLAGS:
@@ -77,199 +238,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dp_mode", default="replica", choices=["replica", "sharded"],
                     help="multi-GPU exchange: replica = all-reduce of the dense item gradient (dp.py); sharded = catalog-sharded "
                          "scoring (sharded.py: the item gradient stays on the rank that owns the rows)")
-    ap.add_argument("--eval_panel", default=0, type=int,
-                    help="P > 0: evaluation scores the catalog P columns at a time and selects while it streams (no [B, N] score matrix, "
-                         "any catalog size; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  0: the materialised evaluation.  Not with --dp_mode sharded")
-    ap.add_argument("--fresh_hours", default=0, type=float,
-                    help="H > 0: evaluation ranks every session inside its POOL — the items published in the H hours up to the label's "
-                         "click (and the label) — not against the whole catalog.  Needs --eval_panel; not with --dp_mode sharded.  0: off")
-    ap.add_argument("--cat_cap", default=0, type=int,
-                    help="M > 0: evaluation lists hold at most M items of one category (the walk of include/tcar_quota.h); ILD, unexp and "
-                         "coverage describe the capped lists, and one more line gives their accuracy.  Needs --eval_panel; not with "
-                         "--dp_mode sharded; combines with --fresh_hours.  0: off")
-    ap.add_argument("--shard_eval_panel", default=0, type=int,
-                    help="P > 0 (only with --dp_mode sharded): evaluation streams every rank's SHARD of the catalog P columns at a time "
-                         "and merges the ranks' select states (no [B, N] score matrix on any rank; P % 128 == 0, P <= " + str(MAX_PANEL) + ").  "
-                         "0: the materialised evaluation of the catalog-sharded engine")
-    ap.add_argument("--shard_eval_shortlist", default=0, type=int,
-                    help="C > 0 (only with --dp_mode sharded and --shard_eval_panel P): evaluation additionally runs the two-stage "
-                         "recommendation over the shards on every batch (include/tcar_retrieve_shard.h: every shard's shortlist of C items "
-                         "from coarse scores merged exactly, re-scored by the rows' owners, cut to 20) and prints the line of "
-                         "--eval_shortlist; 65 <= C <= " + str(MAX_SHORTLIST) + ".  0: off")
-    ap.add_argument("--eval_candidates", default=0, type=int,
-                    help="C > 0: evaluation additionally ranks every label among C - 1 other items drawn uniformly from the catalog "
-                         "(include/tcar_cand.h: only those C rows are scored) and prints their AUC / MRR / nDCG@5 / nDCG@10; "
-                         "2 <= C <= " + str(MAX_CANDIDATES) + ".  Not with --dp_mode sharded; combines with everything else.  0: off")
-    ap.add_argument("--eval_shortlist", default=0, type=int,
-                    help="C > 0: evaluation additionally runs the two-stage recommendation on every batch (include/tcar_retrieve.h: a "
-                         "shortlist of C items from coarse scores, re-scored exactly and cut to 20) and prints the share of labels in those "
-                         "lists and their agreement with the streamed lists; 65 <= C <= " + str(MAX_SHORTLIST) + ".  Needs --eval_panel; "
-                         "not with --dp_mode sharded, not with --cat_cap.  0: off")
-    ap.add_argument("--eval_diversity", default=0, type=float,
-                    help="MU > 0: evaluation additionally runs the DIVERSIFIED two-stage recommendation on every batch (include/tcar_mmr.h: "
-                         "the shortlist's k best under the greedy MMR walk over content, a verbatim duplicate of a listed item losing MU "
-                         "logits) and prints its Recall@20, ILD and content ILD beside those of the plain two-stage lists.  Needs "
-                         "--eval_shortlist C; not with --dp_mode sharded.  0: off")
-    ap.add_argument("--eval_mixed", default=0, type=int,
-                    help="1: evaluation packs consecutive batches of DIFFERENT session lengths into one ragged batch of at most "
-                         "--batch_size sessions (include/tcar_ragged.h) and streams the catalog once per pack instead of once per batch.  "
-                         "Needs --eval_panel; combines with --fresh_hours and --cat_cap; not with --dp_mode sharded, --gpus > 1, "
-                         "--eval_candidates, --eval_shortlist.  0: one call per batch")
-    ap.add_argument("--eval_sections", default=0, type=int,
-                    help="G > 0: evaluation additionally asks for one list of 20 per CATEGORY on every batch (include/tcar_sections.h: "
-                         "the G categories with the most catalog items, all from one pass over the catalog) and prints the share of "
-                         "labels found in the list of their own category; 1 <= G <= " + str(MAX_SECTIONS) + ".  Needs --eval_panel; "
-                         "combines with --fresh_hours and --eval_mixed; not with --dp_mode sharded.  0: off")
-    ap.add_argument("--eval_related", default=0, type=int,
-                    help="K > 0: evaluation additionally lists, once behind its batches, the K articles most similar in CONTENT to every "
-                         "distinct label article of the data (include/tcar_similar.h: the content cosine of the diversity re-rank, the "
-                         "catalog streamed in panels, no session) and prints their mean cosine and the share that is of the article's own "
-                         "category; 1 <= K <= " + str(MAX_RELATED) + ".  Not with --dp_mode sharded.  0: off")
+    by_name = {o.name: o for o in EVAL_OPTIONS}
+    for name in _HELP_ORDER:                                 # every evaluation option defaults to 0: off
+        ap.add_argument("--" + name, default=0, type=by_name[name].type, help=by_name[name].help)
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
     ap.add_argument("--seed", default=2020, type=int)
     return ap
-
-
-def _check_panel(flag, panel):
-    if panel < 0 or panel % 128 or panel > MAX_PANEL:
-        raise ValueError("--%s must be a multiple of 128 in [128, %d] (0: off)" % (flag, MAX_PANEL))
-
-
-def _check_streamed_option(flag, value, what, takes, eval_panel, dp_mode):
-    """an option of the streamed evaluation of ONE engine: positive, refused under --dp_mode sharded, and it needs --eval_panel"""
-    if not value:
-        return
-    if value < 0:
-        raise ValueError("--%s must be positive (0: off)" % flag)
-    if dp_mode == "sharded":
-        raise ValueError("--%s %s the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded" % (flag, what))
-    if not eval_panel:
-        raise ValueError("--%s needs --eval_panel P: only the streamed evaluation takes a %s" % (flag, takes))
-
-
-def check_eval_panel(eval_panel, dp_mode):
-    """--eval_panel is the single-engine streamed evaluation: the catalog-sharded engine keeps its own evaluation"""
-    if eval_panel and dp_mode == "sharded":
-        raise ValueError("--eval_panel streams the WHOLE catalog through one engine; it cannot be combined with --dp_mode sharded "
-                         "(the catalog-sharded engine evaluates with its own exchange)")
-    _check_panel("eval_panel", eval_panel)
-
-
-def check_fresh_hours(fresh_hours, eval_panel, dp_mode):
-    """--fresh_hours windows the streamed evaluation (include/tcar_window.h): it needs --eval_panel and the whole catalog on one engine"""
-    _check_streamed_option("fresh_hours", fresh_hours, "windows", "publish-time window", eval_panel, dp_mode)
-
-
-def check_cat_cap(cat_cap, eval_panel, dp_mode):
-    """--cat_cap caps the lists of the streamed evaluation (include/tcar_quota.h): it needs --eval_panel and the whole catalog on one engine"""
-    _check_streamed_option("cat_cap", cat_cap, "caps", "per-category cap", eval_panel, dp_mode)
-
-
-def check_eval_sections(eval_sections, eval_panel, dp_mode):
-    """--eval_sections asks one engine for a list per category beside its streamed evaluation (include/tcar_sections.h): it needs
-    --eval_panel and the whole catalog on one engine"""
-    if eval_sections > MAX_SECTIONS:
-        raise ValueError("--eval_sections must be in [1, %d] (0: off)" % MAX_SECTIONS)
-    _check_streamed_option("eval_sections", eval_sections, "lists the categories beside", "list per category", eval_panel, dp_mode)
-
-
-def check_eval_related(eval_related, dp_mode):
-    """--eval_related lists the articles related to every label article (include/tcar_similar.h), which takes the whole catalog on
-    one engine"""
-    if isinstance(eval_related, bool) or not isinstance(eval_related, (int, np.integer)):
-        raise ValueError("--eval_related must be an integer in [1, %d] (0: off)" % MAX_RELATED)
-    if not eval_related:
-        return
-    if eval_related < 1 or eval_related > MAX_RELATED:
-        raise ValueError("--eval_related must be in [1, %d] (0: off)" % MAX_RELATED)
-    if dp_mode == "sharded":
-        raise ValueError("--eval_related reads the content of the WHOLE catalog on one engine; it cannot be combined with "
-                         "--dp_mode sharded")
-
-
-def check_shard_eval_panel(shard_eval_panel, dp_mode):
-    """--shard_eval_panel is the streamed evaluation of the catalog-sharded engine (include/tcar_serve_shard.h)"""
-    _check_panel("shard_eval_panel", shard_eval_panel)
-    if shard_eval_panel and dp_mode != "sharded":
-        raise ValueError("--shard_eval_panel streams the shards of the catalog-sharded engine: it needs --dp_mode sharded "
-                         "(one engine with the whole catalog: --eval_panel)")
-
-
-def check_eval_candidates(eval_candidates, dp_mode):
-    """--eval_candidates ranks the label among sampled items through candidate-list scoring (include/tcar_cand.h), which takes the
-    whole catalog on one engine"""
-    if not eval_candidates:
-        return
-    if eval_candidates < 2 or eval_candidates > MAX_CANDIDATES:
-        raise ValueError("--eval_candidates must be in [2, %d] (0: off)" % MAX_CANDIDATES)
-    if dp_mode == "sharded":
-        raise ValueError("--eval_candidates scores candidate lists against the WHOLE catalog on one engine; it cannot be combined with "
-                         "--dp_mode sharded")
-
-
-def check_eval_shortlist(eval_shortlist, eval_panel, dp_mode, cat_cap=0):
-    """--eval_shortlist runs the two-stage recommendation (include/tcar_retrieve.h) beside the streamed evaluation of ONE engine and
-    compares their lists: it needs --eval_panel and the whole catalog on one engine, and retrieval takes no per-category cap"""
-    if not eval_shortlist:
-        return
-    if eval_shortlist < 65 or eval_shortlist > MAX_SHORTLIST:
-        raise ValueError("--eval_shortlist must be in [65, %d] (0: off)" % MAX_SHORTLIST)
-    if dp_mode == "sharded":
-        raise ValueError("--eval_shortlist retrieves from the WHOLE catalog on one engine; it cannot be combined with --dp_mode sharded")
-    if not eval_panel:
-        raise ValueError("--eval_shortlist needs --eval_panel P: its lists are compared with those of the streamed evaluation")
-    if cat_cap:
-        raise ValueError("--eval_shortlist cannot be combined with --cat_cap: retrieval takes no per-category cap")
-
-
-def check_eval_diversity(eval_diversity, eval_shortlist, dp_mode):
-    """--eval_diversity runs the diversified two-stage recommendation (include/tcar_mmr.h) beside the plain one: a finite penalty
-    MU > 0 in score units, the shortlist of --eval_shortlist, and the whole catalog on one engine"""
-    if isinstance(eval_diversity, bool) or not isinstance(eval_diversity, (int, float, np.integer, np.floating)):
-        raise ValueError("--eval_diversity must be a number (0: off)")
-    if eval_diversity != eval_diversity or eval_diversity in (float("inf"), float("-inf")) or eval_diversity < 0:
-        raise ValueError("--eval_diversity must be a finite penalty > 0 (0: off)")
-    if not eval_diversity:
-        return
-    if dp_mode == "sharded":
-        raise ValueError("--eval_diversity diversifies the two-stage lists of ONE engine; it cannot be combined with --dp_mode sharded")
-    if not eval_shortlist:
-        raise ValueError("--eval_diversity needs --eval_shortlist C: the walk re-ranks the shortlist of the two-stage call")
-
-
-def check_shard_eval_shortlist(shard_eval_shortlist, shard_eval_panel, dp_mode):
-    """--shard_eval_shortlist runs the two-stage recommendation of the catalog-sharded engine (include/tcar_retrieve_shard.h) beside
-    its streamed evaluation and compares their lists: it needs --dp_mode sharded and --shard_eval_panel"""
-    if not shard_eval_shortlist:
-        return
-    if shard_eval_shortlist < 65 or shard_eval_shortlist > MAX_SHORTLIST:
-        raise ValueError("--shard_eval_shortlist must be in [65, %d] (0: off)" % MAX_SHORTLIST)
-    if dp_mode != "sharded":
-        raise ValueError("--shard_eval_shortlist merges the shortlists of the catalog-sharded engine: it needs --dp_mode sharded "
-                         "(one engine with the whole catalog: --eval_shortlist)")
-    if not shard_eval_panel:
-        raise ValueError("--shard_eval_shortlist needs --shard_eval_panel P: its lists are compared with those of the streamed evaluation")
-
-
-def check_eval_mixed(eval_mixed, eval_panel, dp_mode, gpus=1, eval_candidates=0, eval_shortlist=0):
-    """--eval_mixed packs the batches of the streamed evaluation of ONE engine into ragged batches (include/tcar_ragged.h): it needs
-    --eval_panel and one process; the candidate and two-stage passes keep their rectangular batches"""
-    if not eval_mixed:
-        return
-    if eval_mixed not in (0, 1):
-        raise ValueError("--eval_mixed must be 0 or 1")
-    if dp_mode == "sharded":
-        raise ValueError("--eval_mixed packs the streamed evaluation of ONE engine; it cannot be combined with --dp_mode sharded")
-    if gpus and gpus > 1:
-        raise ValueError("--eval_mixed cannot be combined with --gpus > 1: the ranks split every batch by rows")
-    if not eval_panel:
-        raise ValueError("--eval_mixed needs --eval_panel P: only the streamed evaluation takes a ragged batch")
-    if eval_candidates:
-        raise ValueError("--eval_mixed cannot be combined with --eval_candidates")
-    if eval_shortlist:
-        raise ValueError("--eval_mixed cannot be combined with --eval_shortlist")
 
 
 def load_datas(args):
@@ -327,17 +303,7 @@ def main(argv=None):
     random.seed(args.seed)                       # main.py:10-12
     np.random.seed(args.seed)
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
-    check_eval_panel(args.eval_panel, args.dp_mode)
-    check_fresh_hours(args.fresh_hours, args.eval_panel, args.dp_mode)
-    check_cat_cap(args.cat_cap, args.eval_panel, args.dp_mode)
-    check_shard_eval_panel(args.shard_eval_panel, args.dp_mode)
-    check_eval_sections(args.eval_sections, args.eval_panel, args.dp_mode)
-    check_eval_related(args.eval_related, args.dp_mode)
-    check_eval_candidates(args.eval_candidates, args.dp_mode)
-    check_eval_shortlist(args.eval_shortlist, args.eval_panel, args.dp_mode, args.cat_cap)
-    check_eval_diversity(args.eval_diversity, args.eval_shortlist, args.dp_mode)
-    check_shard_eval_shortlist(args.shard_eval_shortlist, args.shard_eval_panel, args.dp_mode)
-    check_eval_mixed(args.eval_mixed, args.eval_panel, args.dp_mode, args.gpus, args.eval_candidates, args.eval_shortlist)
+    check_eval_options(vars(args), args.gpus)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -26,6 +26,7 @@ import torch
 from ..engine import TIME_NAMES, TIME_VOCAB, TcarEngine, VAR_ORDER
 from . import cli, metrics as M
 from .data import pack_sessions, publish_fields
+from .eval_passes import FeedResult, active_passes
 from .sampler import Sampler
 
 
@@ -138,16 +139,9 @@ class Seq2SeqAttNN():
         self.neg_fast = bool(args.get('neg_fast', 0))
         self.device_sampler = bool(args.get('device_sampler', 0))   # form batches + draw negatives on the GPU
         self.seed = int(args.get('seed', 2020))
-        # test(): eval_panel > 0 selects while the catalog streams by in panels, shard_eval_panel > 0 (dp_mode sharded) streams every
-        # rank's shard, fresh_hours > 0 ranks every session inside its publish-time pool, cat_cap > 0 caps the items of one category
-        self.eval_panel, self.shard_eval_panel, self.fresh_hours, self.cat_cap = self._eval_options(args)
-        self.eval_candidates = self._eval_candidates(args)           # C > 0: test() also ranks every label among C - 1 sampled items
-        self.eval_shortlist = self._eval_shortlist(args)             # C > 0: test() also runs the two-stage recommendation (shortlist C)
-        self.shard_eval_shortlist = self._shard_eval_shortlist(args)   # C > 0: test() also runs the SHARDED two-stage recommendation
-        self.eval_diversity = self._eval_diversity(args)             # MU > 0: test() also runs the DIVERSIFIED two-stage recommendation
-        self.eval_mixed = self._eval_mixed(args)                     # 1: test() packs feeds of different lengths into ragged batches
-        self.eval_sections = self._eval_sections(args)               # G > 0: test() also asks for one list per category (G of them)
-        self.eval_related = self._eval_related(args)                 # K > 0: test() also lists the K related articles of every label article
+        # test(): the evaluation options this model is built with (cli.EVAL_OPTIONS: eval_panel ... eval_mixed), each under its name
+        for name, value in self._eval_request(args)._asdict().items():
+            setattr(self, name, value)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -187,61 +181,17 @@ class Seq2SeqAttNN():
         else:
             self.dp_rank, self.dp_world = 0, 1
 
-    def _eval_options(self, args):
-        """(eval_panel, shard_eval_panel, fresh_hours, cat_cap) of a test() call: `args` over the values the model was built with,
-        refused where they cannot work (the command line's checks, host/cli.py)"""
-        dp_mode = args.get('dp_mode', 'replica')
-        panel, spanel, cap = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'shard_eval_panel', 'cat_cap'))
-        fresh = float(args.get('fresh_hours', getattr(self, 'fresh_hours', 0)) or 0)
-        cli.check_eval_panel(panel, dp_mode)
-        cli.check_fresh_hours(fresh, panel, dp_mode)
-        cli.check_cat_cap(cap, panel, dp_mode)
-        cli.check_shard_eval_panel(spanel, dp_mode)
-        return panel, spanel, fresh, cap
-
-    def _eval_candidates(self, args) -> int:
-        """eval_candidates of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        ncand = int(args.get('eval_candidates', getattr(self, 'eval_candidates', 0)) or 0)
-        cli.check_eval_candidates(ncand, args.get('dp_mode', 'replica'))
-        return ncand
-
-    def _eval_shortlist(self, args) -> int:
-        """eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        panel, cap, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'cat_cap', 'eval_shortlist'))
-        cli.check_eval_shortlist(short, panel, args.get('dp_mode', 'replica'), cap)
-        return short
-
-    def _eval_diversity(self, args) -> float:
-        """eval_diversity of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        mu = args.get('eval_diversity', getattr(self, 'eval_diversity', 0)) or 0
-        short = int(args.get('eval_shortlist', getattr(self, 'eval_shortlist', 0)) or 0)
-        cli.check_eval_diversity(mu, short, args.get('dp_mode', 'replica'))
-        return float(mu)
-
-    def _shard_eval_shortlist(self, args) -> int:
-        """shard_eval_shortlist of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        spanel, short = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('shard_eval_panel', 'shard_eval_shortlist'))
-        cli.check_shard_eval_shortlist(short, spanel, args.get('dp_mode', 'replica'))
-        return short
-
-    def _eval_mixed(self, args) -> int:
-        """eval_mixed of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        panel, ncand, short, mixed = (int(args.get(n, getattr(self, n, 0)) or 0)
-                                      for n in ('eval_panel', 'eval_candidates', 'eval_shortlist', 'eval_mixed'))
-        cli.check_eval_mixed(mixed, panel, args.get('dp_mode', 'replica'), max(int(args.get('gpus', 1) or 1), getattr(self, 'dp_world', 1)), ncand, short)
-        return mixed
-
-    def _eval_sections(self, args) -> int:
-        """eval_sections of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        panel, nsec = (int(args.get(n, getattr(self, n, 0)) or 0) for n in ('eval_panel', 'eval_sections'))
-        cli.check_eval_sections(nsec, panel, args.get('dp_mode', 'replica'))
-        return nsec
-
-    def _eval_related(self, args) -> int:
-        """eval_related of a test() call: `args` over the value the model was built with, refused as the command line refuses it"""
-        nrel = args.get('eval_related', getattr(self, 'eval_related', 0)) or 0
-        cli.check_eval_related(nrel, args.get('dp_mode', 'replica'))
-        return int(nrel)
+    def _eval_request(self, args) -> cli.EvalRequest:
+        """the evaluation options of a test() call: for every option `args` over the value the model was built with, else off,
+        refused as the command line refuses them (cli.check_eval_options: the first broken rule, in its order)"""
+        values = {}
+        for opt in cli.EVAL_OPTIONS:
+            v = args.get(opt.name, getattr(self, opt.name, 0)) or 0
+            # (an option with a rule about its type is checked as it came, the others as the number they stand for)
+            values[opt.name] = v if opt.rules[0].kind == "type" else opt.type(v)
+        gpus = max(int(args.get('gpus', 1) or 1), getattr(self, 'dp_world', 1))
+        cli.check_eval_options(dict(values, dp_mode=args.get('dp_mode', 'replica')), gpus=gpus)
+        return cli.EvalRequest(**{opt.name: opt.type(values[opt.name]) for opt in cli.EVAL_OPTIONS})
 
     def _packs(self, feeds, mixed: bool):
         """test(): the sampler's feeds grouped into the packs of one streamed call each — consecutive feeds, never splitting one,
@@ -316,12 +266,10 @@ class Seq2SeqAttNN():
         return (np.asarray(when, dtype="datetime64[s]") - self._key_t0).astype(np.int64) // 60
 
     def _fresh_window(self, feed, time_dict, hours):
-        """the pools of a test batch: hi = the minute of the label's click + 1, lo = hi - 60 hours -> (lo, hi, label outside its window)"""
+        """the pools of a test batch: hi = the minute of the label's click + 1, lo = hi - 60 hours -> (lo, hi)"""
         T = feed["seq"].shape[1]
         hi = self.minute_of([time_dict[key][T]['click_t'] for key in feed["keys"]]) + 1
-        lo = hi - int(round(60 * hours))
-        kl = self._item_keys()[np.asarray(feed["label"], dtype=np.int64)].astype(np.int64)
-        return lo, hi, ~((lo <= kl) & (kl < hi))
+        return hi - int(round(60 * hours)), hi
 
     def _sampler(self, data, neighbor_dict=None, item_dict=None, neg_num=None):
         # (len_dict, session_dict, session_time_dict) as util.py:56 returns it, or with a 4th element: a prebuilt
@@ -455,139 +403,84 @@ class Seq2SeqAttNN():
         print('batch pred:', tk[:10])
 
     def test(self, sess, test_data, args):
+        """The evaluation loop.  Per streamed call its engine calls come in ONE order: the streamed (or materialised) evaluation,
+        eval_diversity for every feed of the call, then the optional passes in the order of eval_passes.active_passes.  Everything
+        kept of a feed is a clone on the device: but for the lists printed of the first two feeds, nothing is copied to the host and
+        nothing synchronises before check_forks()."""
         print('Measuring...')
         eng = self.engine
-        panel, spanel, fresh, cap = self._eval_options(args)
-        ncand = self._eval_candidates(args)
-        if ncand and self.candidate_n - 1 < 2:
+        req = self._eval_request(args)
+        if req.eval_candidates and self.candidate_n - 1 < 2:
             raise ValueError("eval_candidates ranks the label among OTHER items: the catalog holds fewer than two")
-        cand_rng = np.random.RandomState(self.seed) if ncand else None       # a stream of its own: no other random stream of the run moves
-        cand_pending = []
-        sshort = self._shard_eval_shortlist(args)                # the sharded two-stage call: the same line, the same metrics
-        short = self._eval_shortlist(args) or sshort
-        short_pending = []
-        mu = self._eval_diversity(args)                          # the diversified two-stage call (include/tcar_mmr.h), beside the plain one
-        div_pending = []
-        if spanel and not hasattr(eng, "xch"):
+        if req.shard_eval_panel and not hasattr(eng, "xch"):
             raise ValueError("shard_eval_panel needs the catalog-sharded engine (dp_mode sharded when the model is built)")
         time_dict = test_data[2] if len(test_data) > 2 else None
-        if fresh:
+        if req.fresh_hours:
             if not time_dict:
                 raise ValueError("fresh_hours takes the label's click time from the fold's session_time_dict, which this fold lacks")
             self._item_keys()
-        outside = []
-        hits, mrrs, ndcgs, ilds, unexps, losses = [], [], [], [], [], []
-        c_hits, c_mrrs, c_ndcgs = [], [], []
         sampler = self._sampler(test_data)
-        batch = 0
-        pending = []
         # ILD / unexp pair counts and the set of recommended items stay on the device (tcar_eval_diversity)
         self._install_categories()
         eng.reset_coverage()
-        mixed = self._eval_mixed(args)
-        nsec = self._eval_sections(args)
-        # eval_sections: the categories with the most catalog items are the sections (include/tcar_sections.h), 20 items each
-        sections = M.largest_categories(self._category_table(), nsec) if nsec else None
-        sec_pending = []
-        nrel = self._eval_related(args)
-
-        def section_lists(feeds, window):
-            """the sectioned lists of the sessions of `feeds` (one feed, or the feeds of a pack: one ragged call), kept for the drain"""
-            bare = [{n: v for n, v in f.items() if n not in ("label", "neg")} for f in feeds]
-            res = eng.recommend_sections(bare[0] if len(bare) == 1 else pack_sessions(bare), sections, k=20, exclude_seen=False,
-                                         panel=panel, window=window)
-            sec_pending.append((np.concatenate([np.asarray(f["label"]).reshape(-1) for f in feeds]), res.topk.clone()))
-
-        eval_calls = 0
-        for pack in (self._packs(prefetch_batches(sampler), True) if mixed else ()):
-            # eval_mixed: ONE streamed call per pack of feeds (a ragged batch, include/tcar_ragged.h); a pack of one feed goes the
-            # rectangular way.  The sessions of a feed are contiguous in the pack and their flat rows are its [B_g, T_g] block, so
-            # the diversity counts are taken per feed on that block of the uploaded batch and on the feed's rows of topk.
+        passes = active_passes(self, req)
+        panel, mixed = req.eval_panel or req.shard_eval_panel, bool(req.eval_mixed)
+        keep_lists = args.get('is_print') or req.cat_cap
+        results, batch, eval_calls = [], 0, 0
+        # One streamed call per pack of feeds.  eval_mixed packs feeds of different lengths into a ragged batch (include/tcar_ragged.h;
+        # a pack of one feed goes the rectangular way); without it every feed is its own pack.  The sessions of a feed are contiguous
+        # in the pack and their flat rows are its [B_g, T_g] block, so the diversity counts are taken per feed on that block of the
+        # uploaded batch and on the feed's rows of topk.
+        for pack in self._packs(prefetch_batches(sampler), mixed):
+            eval_calls += 1          # (data parallel: a collective step, the same count on every rank)
+            rows_cap = None
+            if not mixed:            # data parallel: every rank scores its shard of the batch
+                T = pack[0]["seq"].shape[1]
+                feed, rows_cap = self._shard(pack[0])
+                if feed is None:     # the sharded calls are COLLECTIVES: a rank without sessions still joins every exchange
+                    batch += 1
+                    if req.shard_eval_panel:
+                        eng.eval_step_streamed(None, k=20, panel=panel, cap=rows_cap, T=T)
+                    for p in passes:
+                        p.idle(rows_cap, T)
+                    continue
+                pack = [feed]
             bt = eng.upload(pack_sessions(pack) if len(pack) > 1 else pack[0])
             window = None
-            if fresh:
-                wins = [self._fresh_window(feed, time_dict, fresh) for feed in pack]
-                outside += [o for w in wins for o in w[2].tolist()]
-                window = (np.concatenate([w[0] for w in wins]), np.concatenate([w[1] for w in wins]))
-            rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=window, max_per_category=cap or None)
-            eval_calls += 1
+            if req.fresh_hours:
+                window = tuple(np.concatenate(w) for w in zip(*[self._fresh_window(f, time_dict, req.fresh_hours) for f in pack]))
+            if panel:                # streamed: no [B, N] score matrix; inside the sessions' pools (fresh_hours), capped per category
+                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel, window=window, max_per_category=req.cat_cap or None,
+                                                        **({"cap": rows_cap} if req.shard_eval_panel else {}))
+            else:
+                rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
             s0 = r0 = 0
             for feed in pack:
                 batch += 1
                 b, T = feed["seq"].shape
-                tk = topk[s0:s0 + b]
-                ild_c, unexp_c, n_rec = eng.eval_diversity(bt, tk, block=(r0, b, T))
-                pending.append((feed, rank[s0:s0 + b].clone(), tk.clone() if args.get('is_print') or cap else None, ce[s0:s0 + b].clone(),
-                                ild_c, unexp_c, n_rec))
+                rows, block = (slice(s0, s0 + b), (r0, b, T)) if mixed else (slice(None), None)
+                tk = topk[rows]
+                ild_c, unexp_c, n_rec = eng.eval_diversity(bt, tk, block=block)
+                results.append(FeedResult(feed, rank[rows].clone(), tk.clone() if keep_lists else None, ce[rows].clone(), ild_c, unexp_c, n_rec))
                 if batch < 3:
                     self._print_batch(feed, tk[0].cpu().numpy().tolist(), args)
                 s0, r0 = s0 + b, r0 + b * T
-            if nsec:             # (behind the diversity counts: the call uploads the pack again)
-                section_lists(pack, window)
-        for feed in (() if mixed else prefetch_batches(sampler)):
-            batch += 1
-            eval_calls += 1          # one evaluation call per feed (data parallel: a collective step, the same count on every rank)
-            T = feed["seq"].shape[1]
-            feed, _cap = self._shard(feed)           # data parallel: every rank scores its shard of the batch
-            if feed is None:
-                if spanel:       # a COLLECTIVE: a rank without sessions still joins every exchange (sharded.ShardExchange.serve)
-                    eng.eval_step_streamed(None, k=20, panel=spanel, cap=_cap, T=T)
-                if sshort:       # ... and those of the two-stage call (sharded.ShardExchange.retrieve)
-                    eng.shard_recommend_two_stage(None, k=20, shortlist=sshort, exclude_seen=False, panel=spanel, cap=_cap, T=T)
-                continue
-            bt = eng.upload(feed)
-            if panel or spanel:  # streamed: no [B, N] score matrix; inside the sessions' pools (fresh), capped per category (cap)
-                window = None
-                if fresh:
-                    w_lo, w_hi, out = self._fresh_window(feed, time_dict, fresh)
-                    outside += out.tolist()
-                    window = (w_lo, w_hi)
-                rank, topk, ce = eng.eval_step_streamed(None, k=20, bt=bt, panel=panel or spanel, window=window,
-                                                        max_per_category=cap or None, **({"cap": _cap} if spanel else {}))
-            else:
-                rank, topk, ce = eng.eval_step(None, k=20, bt=bt)
-            ild_c, unexp_c, n_rec = eng.eval_diversity(bt, topk)
-            pending.append((feed, rank.clone(), topk.clone() if args.get('is_print') or cap else None, ce.clone(), ild_c, unexp_c, n_rec))     # device results; drained below
-            if batch < 3:
-                self._print_batch(feed, topk[0].cpu().numpy().tolist(), args)
-            if ncand:            # the label among ncand - 1 sampled items: only those rows are scored (include/tcar_cand.h)
-                res = eng.score_candidates(None, *self._label_among_sampled(feed["label"], ncand, cand_rng), bt=bt)
-                cand_pending.append((res.counts.clone(), res.metrics.clone()))
-            if sshort:           # the two-stage lists over the shards (include/tcar_retrieve_shard.h), beside the streamed ones
-                topk = topk.clone()          # (the sharded calls share the gathered-row workspace: keep the streamed lists)
-                two, _ = eng.shard_recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20,
-                                                       shortlist=sshort, exclude_seen=False, panel=spanel, window=window, cap=_cap)
-                short_pending.append((feed["label"], topk, two.clone()))
-            elif short:          # the two-stage lists of the same sessions (include/tcar_retrieve.h), beside the streamed ones
-                two, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
-                                                 exclude_seen=False, panel=panel, window=window)
-                two = two.clone()            # (the diversified call below writes the same workspace)
-                short_pending.append((feed["label"], topk.clone(), two))       # (topk: the streamed step's own buffer, untouched)
-                if mu:           # ... and their diversified form: the same shortlist, the MMR walk over content as its close
-                    div, _ = eng.recommend_two_stage({n: v for n, v in feed.items() if n not in ("label", "neg")}, k=20, shortlist=short,
-                                                     exclude_seen=False, panel=panel, window=window, diversity=mu)
-                    div_pending.append((feed["label"], two, div.clone()))
-            if nsec:             # one list per category for the same sessions (include/tcar_sections.h), last: it uploads the feed again
-                section_lists([feed], window)
+            for p in passes:
+                p.after_feed(pack, bt, topk, window, rows_cap)
         eng.check_forks()             # (synchronises) nothing below is reported from a run whose flag forks timed out
-        for feed, rank, topk, ce, ild_c, unexp_c, n_rec in pending:
-            r = rank.cpu().numpy()
-            h, m, n = M.metrics_from_ranks(r, 20)
+        hits, mrrs, ndcgs, ilds, unexps, losses = [], [], [], [], [], []
+        for r in results:
+            h, m, n = M.metrics_from_ranks(r.rank.cpu().numpy(), 20)
             hits += h.tolist()
             mrrs += m.tolist()
             ndcgs += n.tolist()
-            losses += ce.cpu().numpy().tolist()
-            il, un = M.diversity_from_counts(ild_c.cpu().numpy(), unexp_c.cpu().numpy(), n_rec.cpu().numpy(), feed["seq"].shape[1])
+            losses += r.ce.cpu().numpy().tolist()
+            il, un = M.diversity_from_counts(r.ild_c.cpu().numpy(), r.unexp_c.cpu().numpy(), r.n_rec.cpu().numpy(), r.feed["seq"].shape[1])
             ilds += il.tolist()
             unexps += un.tolist()
-            if cap:             # accuracy of the capped LISTS: the label's place in the list (the rank above is that of the whole pool)
-                h, m, n = M.metrics_from_ranks(M.list_ranks(topk.cpu().numpy(), feed["label"], 20), 20)
-                c_hits += h.tolist()
-                c_mrrs += m.tolist()
-                c_ndcgs += n.tolist()
             if args.get('is_print'):
-                self.printData(str(args['foldnum']) + '_' + str(self.curEpoch), feed["seq"].tolist(),
-                               feed["label"].tolist(), topk.cpu().numpy().astype(np.int64).tolist())
+                self.printData(str(args['foldnum']) + '_' + str(self.curEpoch), r.feed["seq"].tolist(),
+                               r.feed["label"].tolist(), r.topk.cpu().numpy().astype(np.int64).tolist())
         # sums over this rank's sessions, then over the ranks; coverage = union of the recommended items
         sums = self._allsum([float(np.sum(x)) for x in (losses, ilds, unexps, mrrs, hits, ndcgs)] + [float(len(hits))])
         n = max(sums[6], 1.0)
@@ -603,73 +496,8 @@ class Seq2SeqAttNN():
         print('MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(m_mrr, m_hit, m_ndcg))
         self.last_metrics = {"mrr": m_mrr, "recall": m_hit, "ndcg": m_ndcg, "loss": m_loss, "ild": m_ild,
                              "unexp": m_unexp, "coverage": n_covered, "eval_calls": eval_calls, "sessions": int(sums[6])}
-        if ncand:
-            per = [M.impression_metrics(c.cpu().numpy(), m.cpu().numpy()) for c, m in cand_pending]
-            cols = [np.concatenate([p[i] for p in per]) if per else np.zeros(0) for i in range(4)]
-            keep = ~np.isnan(cols[0])                # (a label and its negatives always hold both classes; kept for the rule's sake)
-            tot = self._allsum([float(np.sum(x[keep])) for x in cols] + [float(keep.sum())])
-            c_auc, c_mrr, c_n5, c_n10 = [v / max(tot[4], 1.0) for v in tot[:4]]
-            print('candidates ({} per session): AUC: {}, MRR: {}, nDCG@5: {}, nDCG@10: {}'.format(ncand, c_auc, c_mrr, c_n5, c_n10))
-            self.last_metrics["candidates"] = {"auc": c_auc, "mrr": c_mrr, "ndcg5": c_n5, "ndcg10": c_n10}
-        if short:
-            inside, agree = [], []
-            for label, streamed, two in short_pending:
-                two, streamed = two.cpu().numpy(), streamed.cpu().numpy()
-                inside += (two == np.asarray(label)[:, None]).any(1).tolist()
-                agree += [len(set(t[t >= 0].tolist()) & set(s_.tolist())) / 20.0 for t, s_ in zip(two, streamed)]
-            t_hit, t_agree = [v / n for v in self._allsum([float(np.sum(inside)), float(np.sum(agree))])]
-            print('two-stage lists (shortlist {}): Recall@20: {}, agreement with the streamed lists: {}'.format(short, t_hit, t_agree))
-            self.last_metrics["two_stage"] = {"recall": t_hit, "agreement": t_agree, "shortlist": short}
-        if mu and not sshort:
-            cat, content = self._category_table(), np.asarray(eng._content)[1:]
-
-            def list_means(lists):
-                """sums over the sessions whose list is full (category ILD divides by k (k - 1), as getILD does) -> their count too"""
-                full = lists[(lists >= 0).all(1)]
-                return [float(M.ild_batch(full, cat).sum()), float(M.content_ild_batch(full, content).sum()), float(len(full))]
-            tot = np.zeros(7)
-            for label, two, div in div_pending:
-                two, div = two.cpu().numpy(), div.cpu().numpy()
-                tot += [float((div == np.asarray(label)[:, None]).any(1).sum())] + list_means(div) + list_means(two)
-            tot = self._allsum(tot.tolist())
-            d_hit, d_ild, d_cild = tot[0] / n, tot[1] / max(tot[3], 1.0), tot[2] / max(tot[3], 1.0)
-            t_ild, t_cild = tot[4] / max(tot[6], 1.0), tot[5] / max(tot[6], 1.0)
-            print('diversified lists (shortlist {}, penalty {}): Recall@20: {}, ILD: {}, content ILD: {} (two-stage lists: ILD {}, '
-                  'content ILD {})'.format(short, mu, d_hit, d_ild, d_cild, t_ild, t_cild))
-            self.last_metrics["diversified"] = {"recall": d_hit, "ild": d_ild, "content_ild": d_cild, "two_stage_ild": t_ild,
-                                                "two_stage_content_ild": t_cild, "shortlist": short, "penalty": mu}
-        if nsec:
-            cat = self._category_table()
-            hc = [M.section_hits(tk.cpu().numpy(), lab, cat, sections) for lab, tk in sec_pending]
-            s_hit, s_cov = self._allsum([float(sum(h.sum() for h, _ in hc)), float(sum(c.sum() for _, c in hc))])
-            s_recall, s_share = s_hit / max(s_cov, 1.0), s_cov / n
-            print('sections ({} categories, 20 per section): Recall@20 in the label\'s section: {}, labels in a listed section: {}'.format(
-                len(sections), s_recall, s_share))
-            self.last_metrics["sections"] = {"G": int(len(sections)), "recall": s_recall, "covered": s_share}
-        if nrel:
-            # eval_related: the related articles (include/tcar_similar.h) of every distinct label article of this rank's sessions,
-            # batch_size queries a call; the sums go over the ranks
-            cat = self._category_table()
-            arts = np.unique(np.concatenate([np.asarray(p[0]["label"], dtype=np.int64).reshape(-1) for p in pending])) if pending \
-                else np.zeros(0, np.int64)
-            tot = np.zeros(4)
-            for i in range(0, len(arts), max(int(self.batch_size), 1)):
-                ids = arts[i:i + max(int(self.batch_size), 1)]
-                tk, sims = (t.cpu().numpy() for t in eng.similar_items(ids, k=nrel))
-                cos, same = M.related_sums(tk, sims, ids, cat)
-                tot += [cos, same, float((tk >= 0).sum()), float(len(ids))]
-            tot = self._allsum(tot.tolist())
-            r_cos, r_same = tot[0] / max(tot[2], 1.0), tot[1] / max(tot[2], 1.0)
-            print('related articles ({} per article): mean cosine: {}, same category: {}'.format(nrel, r_cos, r_same))
-            self.last_metrics["related"] = {"k": nrel, "mean_cosine": r_cos, "same_category": r_same, "articles": int(tot[3])}
-        if fresh:           # (these labels are still scored: a label is always in its session's pool)
-            share = self._allsum([float(np.sum(outside))])[0] / n
-            print('labels outside their window: {}'.format(share))
-            self.last_metrics["labels_outside"] = share
-        if cap:
-            c_mrr, c_hit, c_ndcg = [v / n for v in self._allsum([float(np.sum(x)) for x in (c_mrrs, c_hits, c_ndcgs)])]
-            print('capped lists (<= {} per category): MRR@20: {}, Recall@20: {}, nDCG@20: {}'.format(cap, c_mrr, c_hit, c_ndcg))
-            self.last_metrics["capped"] = {"mrr": c_mrr, "recall": c_hit, "ndcg": c_ndcg}
+        for p in passes:              # every rank, every pass, this order: their sums over the ranks are collectives
+            self.last_metrics[p.key] = p.report(n, results)
         return m_hit
 
     # ---------------------------------------------------------------------------------------- recommend

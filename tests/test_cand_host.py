@@ -173,13 +173,14 @@ def test_eval_candidates_is_range_checked_and_refused_with_the_catalog_sharded_m
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (1, -3, 1025):
         with pytest.raises(ValueError, match=r"--eval_candidates must be in \[2, 1024\]"):
-            cli.check_eval_candidates(bad, "replica")
+            check(eval_candidates=bad, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_candidates.*sharded"):
-        cli.check_eval_candidates(16, "sharded")
+        check(eval_candidates=16, dp_mode="sharded")
     for ok in ((0, "sharded"), (0, "replica"), (2, "replica"), (1024, "replica")):
-        cli.check_eval_candidates(*ok)
+        check(eval_candidates=ok[0], dp_mode=ok[1])
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_candidates == 0 and ap.parse_args(["--eval_candidates", "16"]).eval_candidates == 16
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)

@@ -111,12 +111,13 @@ def test_eval_panel_with_the_catalog_sharded_mode_is_refused():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     with pytest.raises(ValueError, match="eval_panel"):
-        cli.check_eval_panel(128, "sharded")
+        check(eval_panel=128, dp_mode="sharded")
     with pytest.raises(ValueError, match="eval_panel"):
-        cli.check_eval_panel(100, "replica")
-    cli.check_eval_panel(0, "sharded")
-    cli.check_eval_panel(256, "replica")
+        check(eval_panel=100, dp_mode="replica")
+    check(eval_panel=0, dp_mode="sharded")
+    check(eval_panel=256, dp_mode="replica")
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
     args = fold.model_args(batch_size=8, epoch=1, neg_num=2, hidden_size=8, time_hidden_size=4, lr=0.003, emb_stddev=0.3, stddev=0.1,
                            eval_panel=128, dp_mode="sharded")

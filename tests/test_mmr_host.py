@@ -161,15 +161,16 @@ def test_the_engine_validates_the_penalty_before_any_device_call():
 
 def test_eval_diversity_is_checked_and_refused_where_it_cannot_work():
     from tcar_amd.host import cli
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (-1.0, float("nan"), float("inf"), "1", True):
         with pytest.raises(ValueError, match="--eval_diversity must be"):
-            cli.check_eval_diversity(bad, 128, "replica")
+            check(eval_diversity=bad, eval_shortlist=128, eval_panel=256, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_diversity needs --eval_shortlist"):
-        cli.check_eval_diversity(1.0, 0, "replica")
+        check(eval_diversity=1.0, eval_shortlist=0, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_diversity.*sharded"):
-        cli.check_eval_diversity(1.0, 128, "sharded")
+        check(eval_diversity=1.0, dp_mode="sharded")       # (with --eval_shortlist the refusal of --eval_shortlist comes first)
     for ok in ((0, 0, "sharded"), (0.0, 128, "replica"), (0.5, 65, "replica"), (3, 1024, "replica")):
-        cli.check_eval_diversity(*ok)
+        check(eval_diversity=ok[0], eval_shortlist=ok[1], eval_panel=256 if ok[1] else 0, dp_mode=ok[2])
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_diversity == 0 and ap.parse_args(["--eval_diversity", "1.5"]).eval_diversity == 1.5
 

@@ -78,15 +78,16 @@ def test_cat_cap_is_refused_where_it_cannot_work():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     with pytest.raises(ValueError, match="cat_cap"):
-        cli.check_cat_cap(-1, 128, "replica")
+        check(cat_cap=-1, eval_panel=128, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_panel"):
-        cli.check_cat_cap(2, 0, "replica")
+        check(cat_cap=2, eval_panel=0, dp_mode="replica")
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_cat_cap(2, 128, "sharded")
-    cli.check_cat_cap(0, 0, "sharded")
-    cli.check_cat_cap(0, 0, "replica")
-    cli.check_cat_cap(2, 128, "replica")
+        check(cat_cap=2, eval_panel=128, dp_mode="sharded")
+    check(cat_cap=0, eval_panel=0, dp_mode="sharded")
+    check(cat_cap=0, eval_panel=0, dp_mode="replica")
+    check(cat_cap=2, eval_panel=128, dp_mode="replica")
     assert cli.build_parser().parse_args([]).cat_cap == 0
     a = cli.build_parser().parse_args(["--cat_cap", "3", "--eval_panel", "128", "--fresh_hours", "48"])
     assert a.cat_cap == 3 and a.fresh_hours == 48

@@ -192,24 +192,24 @@ def test_eval_mixed_is_refused_where_it_cannot_work_and_defaults_to_off():
     from tcar_amd.host.synth import SynthFold
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_mixed == 0 and ap.parse_args(["--eval_mixed", "1"]).eval_mixed == 1
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     with pytest.raises(ValueError, match="eval_mixed needs --eval_panel"):
-        cli.check_eval_mixed(1, 0, "replica")
+        check(eval_mixed=1, eval_panel=0, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_mixed.*sharded"):
-        cli.check_eval_mixed(1, 256, "sharded")
+        check(eval_mixed=1, dp_mode="sharded")             # (with --eval_panel the refusal of --eval_panel comes first)
     with pytest.raises(ValueError, match="eval_mixed.*gpus"):
-        cli.check_eval_mixed(1, 256, "replica", 2)
+        check(eval_mixed=1, eval_panel=256, dp_mode="replica", gpus=2)
     with pytest.raises(ValueError, match="eval_mixed.*eval_candidates"):
-        cli.check_eval_mixed(1, 256, "replica", 1, 50)
+        check(eval_mixed=1, eval_panel=256, dp_mode="replica", gpus=1, eval_candidates=50)
     with pytest.raises(ValueError, match="eval_mixed.*eval_shortlist"):
-        cli.check_eval_mixed(1, 256, "replica", 1, 0, 80)
+        check(eval_mixed=1, eval_panel=256, dp_mode="replica", gpus=1, eval_candidates=0, eval_shortlist=80)
     with pytest.raises(ValueError, match="eval_mixed must be 0 or 1"):
-        cli.check_eval_mixed(2, 256, "replica")
-    for ok in ((0, 0, "sharded", 8, 50, 80), (1, 128, "replica"), (1, 49152, "replica", 1, 0, 0)):
-        cli.check_eval_mixed(*ok)
+        check(eval_mixed=2, eval_panel=256, dp_mode="replica")
+    # (off, it refuses nothing: eight ranks, and the candidate and two-stage passes beside the streamed evaluation)
+    for ok in ((0, 0, "sharded", 8), (0, 256, "replica", 8, 50, 80), (1, 128, "replica"), (1, 49152, "replica", 1, 0, 0)):
+        check(**dict(zip(("eval_mixed", "eval_panel", "dp_mode", "gpus", "eval_candidates", "eval_shortlist"), ok)))
     # it combines with --fresh_hours and --cat_cap: their own checks pass beside it
-    cli.check_fresh_hours(2.0, 256, "replica")
-    cli.check_cat_cap(3, 256, "replica")
-    cli.check_eval_mixed(1, 256, "replica", 1, 0, 0)
+    check(fresh_hours=2.0, cat_cap=3, eval_mixed=1, eval_panel=256, dp_mode="replica", gpus=1, eval_candidates=0, eval_shortlist=0)
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
     for kw in (dict(eval_mixed=1), dict(eval_mixed=1, eval_panel=128, eval_candidates=20), dict(eval_mixed=1, eval_panel=128, gpus=2),
                dict(eval_mixed=1, eval_panel=128, eval_shortlist=80)):

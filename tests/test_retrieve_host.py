@@ -173,17 +173,18 @@ def test_eval_shortlist_is_range_checked_and_refused_where_it_cannot_work():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (1, 64, -3, 1025):
         with pytest.raises(ValueError, match=r"--eval_shortlist must be in \[65, 1024\]"):
-            cli.check_eval_shortlist(bad, 256, "replica")
+            check(eval_shortlist=bad, eval_panel=256, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_shortlist needs --eval_panel"):
-        cli.check_eval_shortlist(80, 0, "replica")
+        check(eval_shortlist=80, eval_panel=0, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_shortlist.*sharded"):
-        cli.check_eval_shortlist(80, 256, "sharded")
+        check(eval_shortlist=80, dp_mode="sharded")        # (with --eval_panel the refusal of --eval_panel comes first)
     with pytest.raises(ValueError, match="eval_shortlist.*cat_cap"):
-        cli.check_eval_shortlist(80, 256, "replica", 3)
-    for ok in ((0, 0, "sharded", 0), (0, 0, "replica", 3), (65, 128, "replica", 0), (1024, 49152, "replica", 0)):
-        cli.check_eval_shortlist(*ok)
+        check(eval_shortlist=80, eval_panel=256, dp_mode="replica", cat_cap=3)
+    for ok in ((0, 0, "sharded", 0), (0, 128, "replica", 3), (65, 128, "replica", 0), (1024, 49152, "replica", 0)):
+        check(eval_shortlist=ok[0], eval_panel=ok[1], dp_mode=ok[2], cat_cap=ok[3])
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_shortlist == 0 and ap.parse_args(["--eval_shortlist", "80"]).eval_shortlist == 80
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)

@@ -170,22 +170,23 @@ def test_shard_eval_shortlist_is_range_checked_and_refused_where_it_cannot_work(
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (1, 64, -3, 1025):
         with pytest.raises(ValueError, match=r"--shard_eval_shortlist must be in \[65, 1024\]"):
-            cli.check_shard_eval_shortlist(bad, 256, "sharded")
+            check(shard_eval_shortlist=bad, shard_eval_panel=256, dp_mode="sharded")
     with pytest.raises(ValueError, match="shard_eval_shortlist needs --shard_eval_panel"):
-        cli.check_shard_eval_shortlist(80, 0, "sharded")
+        check(shard_eval_shortlist=80, shard_eval_panel=0, dp_mode="sharded")
     with pytest.raises(ValueError, match="shard_eval_shortlist.*needs --dp_mode sharded"):
-        cli.check_shard_eval_shortlist(80, 256, "replica")
-    for ok in ((0, 0, "sharded"), (0, 0, "replica"), (0, 256, "replica"), (65, 128, "sharded"), (1024, 49152, "sharded")):
-        cli.check_shard_eval_shortlist(*ok)
+        check(shard_eval_shortlist=80, dp_mode="replica")  # (with --shard_eval_panel the refusal of --shard_eval_panel comes first)
+    for ok in ((0, 0, "sharded"), (0, 0, "replica"), (0, 256, "sharded"), (65, 128, "sharded"), (1024, 49152, "sharded")):
+        check(shard_eval_shortlist=ok[0], shard_eval_panel=ok[1], dp_mode=ok[2])
     ap = cli.build_parser()
     assert ap.parse_args([]).shard_eval_shortlist == 0 and ap.parse_args(["--shard_eval_shortlist", "80"]).shard_eval_shortlist == 80
     # the single-engine options keep refusing the sharded mode
     with pytest.raises(ValueError, match="eval_shortlist.*sharded"):
-        cli.check_eval_shortlist(80, 256, "sharded")
+        check(eval_shortlist=80, dp_mode="sharded")
     with pytest.raises(ValueError, match="eval_candidates.*sharded"):
-        cli.check_eval_candidates(16, "sharded")
+        check(eval_candidates=16, dp_mode="sharded")
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
     for kw in (dict(shard_eval_shortlist=80), dict(shard_eval_shortlist=80, shard_eval_panel=128),
                dict(shard_eval_shortlist=80, dp_mode="sharded"), dict(shard_eval_shortlist=2000, shard_eval_panel=128, dp_mode="sharded")):

@@ -194,23 +194,22 @@ def test_eval_sections_is_range_checked_and_refused_where_it_cannot_work():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     with pytest.raises(ValueError, match=r"--eval_sections must be in \[1, 16\]"):
-        cli.check_eval_sections(17, 128, "replica")
+        check(eval_sections=17, eval_panel=128, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_sections must be positive"):
-        cli.check_eval_sections(-1, 128, "replica")
+        check(eval_sections=-1, eval_panel=128, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_sections needs --eval_panel"):
-        cli.check_eval_sections(4, 0, "replica")
+        check(eval_sections=4, eval_panel=0, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_sections.*sharded"):
-        cli.check_eval_sections(4, 128, "sharded")
+        check(eval_sections=4, dp_mode="sharded")          # (with --eval_panel the refusal of --eval_panel comes first)
     for ok in ((0, 0, "sharded"), (0, 0, "replica"), (1, 128, "replica"), (16, 49152, "replica")):
-        cli.check_eval_sections(*ok)
+        check(eval_sections=ok[0], eval_panel=ok[1], dp_mode=ok[2])
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_sections == 0
     a = ap.parse_args(["--eval_sections", "4", "--eval_panel", "128", "--fresh_hours", "48", "--eval_mixed", "1"])
     assert (a.eval_sections, a.fresh_hours, a.eval_mixed) == (4, 48, 1)
-    cli.check_eval_sections(a.eval_sections, a.eval_panel, a.dp_mode)                        # the combinations the flag allows
-    cli.check_fresh_hours(a.fresh_hours, a.eval_panel, a.dp_mode)
-    cli.check_eval_mixed(a.eval_mixed, a.eval_panel, a.dp_mode, a.gpus, a.eval_candidates, a.eval_shortlist)
+    cli.check_eval_options(vars(a), gpus=a.gpus)                                            # the combinations the flag allows
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
     small = dict(batch_size=8, epoch=1, neg_num=2, hidden_size=8, time_hidden_size=4, lr=0.003, emb_stddev=0.3, stddev=0.1)
     for kw, text in ((dict(eval_sections=4), "eval_panel"), (dict(eval_sections=17, eval_panel=128), r"\[1, 16\]"),

@@ -133,25 +133,26 @@ def test_shard_eval_panel_is_validated_like_its_neighbours():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (-128, 100, 49152 + 128):
         with pytest.raises(ValueError, match="shard_eval_panel"):
-            cli.check_shard_eval_panel(bad, "sharded")
+            check(shard_eval_panel=bad, dp_mode="sharded")
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_shard_eval_panel(128, "replica")
-    cli.check_shard_eval_panel(0, "replica")
-    cli.check_shard_eval_panel(0, "sharded")
-    cli.check_shard_eval_panel(128, "sharded")
-    cli.check_shard_eval_panel(49152, "sharded")
+        check(shard_eval_panel=128, dp_mode="replica")
+    check(shard_eval_panel=0, dp_mode="replica")
+    check(shard_eval_panel=0, dp_mode="sharded")
+    check(shard_eval_panel=128, dp_mode="sharded")
+    check(shard_eval_panel=49152, dp_mode="sharded")
     assert cli.build_parser().parse_args([]).shard_eval_panel == 0
     a = cli.build_parser().parse_args(["--shard_eval_panel", "256", "--dp_mode", "sharded"])
     assert a.shard_eval_panel == 256 and a.eval_panel == 0
     # the refusals of the single-engine options under sharded stay what they were
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_eval_panel(128, "sharded")
+        check(eval_panel=128, dp_mode="sharded")
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_fresh_hours(48, 128, "sharded")
+        check(fresh_hours=48, eval_panel=128, dp_mode="sharded")
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_cat_cap(2, 128, "sharded")
+        check(cat_cap=2, eval_panel=128, dp_mode="sharded")
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
     small = dict(batch_size=8, epoch=1, neg_num=2, hidden_size=8, time_hidden_size=4, lr=0.003, emb_stddev=0.3, stddev=0.1)
     with pytest.raises(ValueError, match="sharded"):

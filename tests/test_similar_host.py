@@ -179,25 +179,26 @@ def test_the_engine_validates_the_request_before_any_device_call():
 def test_eval_related_is_range_checked_and_refused_where_it_cannot_work():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     for bad in (-1, 65, 1000):
         with pytest.raises(ValueError, match=r"--eval_related must be in \[1, 64\]"):
-            cli.check_eval_related(bad, "replica")
+            check(eval_related=bad, dp_mode="replica")
     for bad in (1.5, "3", True):
         with pytest.raises(ValueError, match="--eval_related must be an integer"):
-            cli.check_eval_related(bad, "replica")
+            check(eval_related=bad, dp_mode="replica")
     with pytest.raises(ValueError, match="eval_related.*sharded"):
-        cli.check_eval_related(5, "sharded")
+        check(eval_related=5, dp_mode="sharded")
     for ok in ((0, "sharded"), (1, "replica"), (64, "replica"), (np.int64(10), "replica")):
-        cli.check_eval_related(*ok)
+        check(eval_related=ok[0], dp_mode=ok[1])
     ap = cli.build_parser()
     assert ap.parse_args([]).eval_related == 0 and ap.parse_args(["--eval_related", "10"]).eval_related == 10
     m = Seq2SeqAttNN.__new__(Seq2SeqAttNN)
-    assert m._eval_related({}) == 0 and m._eval_related({"eval_related": 7}) == 7
+    assert m._eval_request({}).eval_related == 0 and m._eval_request({"eval_related": 7}).eval_related == 7
     m.eval_related = 9
-    assert m._eval_related({}) == 9 and m._eval_related({"eval_related": 0}) == 0
+    assert m._eval_request({}).eval_related == 9 and m._eval_request({"eval_related": 0}).eval_related == 0
     for kw, text in ((dict(eval_related=65), r"\[1, 64\]"), (dict(eval_related=4, dp_mode="sharded"), "sharded")):
         with pytest.raises(ValueError, match=text):
-            m._eval_related(kw)
+            m._eval_request(kw)
 
 
 def test_related_sums():

@@ -134,14 +134,15 @@ def test_fresh_hours_is_refused_where_it_cannot_work():
     from tcar_amd.host import cli
     from tcar_amd.host.model import Seq2SeqAttNN
     from tcar_amd.host.synth import SynthFold
+    check = lambda gpus=1, **values: cli.check_eval_options(values, gpus=gpus)
     with pytest.raises(ValueError, match="eval_panel"):
-        cli.check_fresh_hours(48, 0, "replica")
+        check(fresh_hours=48, eval_panel=0, dp_mode="replica")
     with pytest.raises(ValueError, match="sharded"):
-        cli.check_fresh_hours(48, 128, "sharded")
+        check(fresh_hours=48, eval_panel=128, dp_mode="sharded")
     with pytest.raises(ValueError, match="fresh_hours"):
-        cli.check_fresh_hours(-1, 128, "replica")
-    cli.check_fresh_hours(0, 0, "sharded")
-    cli.check_fresh_hours(48, 128, "replica")
+        check(fresh_hours=-1, eval_panel=128, dp_mode="replica")
+    check(fresh_hours=0, eval_panel=0, dp_mode="sharded")
+    check(fresh_hours=48, eval_panel=128, dp_mode="replica")
     assert cli.build_parser().parse_args([]).fresh_hours == 0
     assert cli.build_parser().parse_args(["--fresh_hours", "48", "--eval_panel", "128"]).fresh_hours == 48
     fold = SynthFold(n_items=60, dim=8, n_train=40, n_test=10, seed=1)
