@@ -1,44 +1,14 @@
 // Related items (include/tcar_similar.h): the cosine panels.  tcar_sim_queries copies the Q query rows into xq and computes their
 // 1 / norm; tcar_sim_panel writes panel[q, j] = sim(query q, item n0 + j), the [Q, n] block a fold of tcar_serve.h reads.
 //
-// Summation order (fixed by H alone, tcar_mmr.h): every dot is EIGHT fma chains, chain j over the columns c % 8 == j in ascending
-// order from +0, closed as ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)) — csrc/mmr.hip's two halves of four chains.  Columns
-// past H contribute fma(0, 0, acc) = acc.  Here the chains are plain scalar fmaf on the VALU, eight accumulators per output: this
-// form is certain to give the bits of mmr.hip (docs/KERNELS.md has the MFMA form that was not built).
-//
-// The panel kernel.  A workgroup of 256 threads owns a 64 x 64 tile (queries x items); thread (tq, tn) = (tid >> 4, tid & 15) owns
-// the 4 x 4 outputs (tq + 16 i, tn + 16 m), 128 accumulators.  K runs in chunks of 32 columns = 4 steps of 8 (one column per chain):
-// both operand tiles of a chunk sit in LDS as [64][32 + 4] floats (the pad makes the 16 rows a wave reads in one 16-byte LDS
-// instruction fall into 16 distinct bank quads), the next chunk's global loads are in flight in registers while the chunk is
-// contracted.  The item side's r comes from the same LDS tile: thread t adds chains 2 (t >> 6) and 2 (t >> 6) + 1 of item t & 63
-// as the chunks pass, the eight chains meet in LDS behind the K loop and every thread closes the four items it owns.
-// Row arithmetic is written on scalars: the library carries no packed fp32 math (DESIGN.md §7 observation 1).
-#include "tcar_common.h"
+// The summation order of every dot, the 64 x 64 tile and its K loop are those of csrc/sim_tile.h, which csrc/dupes.hip shares.  The
+// item side's r comes from the same LDS tile: thread t adds chains 2 (t >> 6) and 2 (t >> 6) + 1 of item t & 63 as the chunks pass
+// (sm_contract<true>), the eight chains meet in LDS behind the K loop and every thread closes the four items it owns.
+#include "sim_tile.h"
 #include "../../include/tcar_similar.h"
 #include <math.h>
 
 namespace {
-
-constexpr int SM_T = 64;                     // rows of a tile, queries and items alike
-constexpr int SM_KC = 32, SM_LD = SM_KC + 4; // columns of a K chunk; floats per LDS row
-constexpr int SM_NT = 256;
-constexpr int SM_R = 4;                      // outputs per thread and side: rows tq + 16 i, items tn + 16 m
-
-__device__ __forceinline__ float sm_rnorm(float ss) { return ss > 0.f ? __fdiv_rn(1.f, __fsqrt_rn(ss)) : 0.f; }
-__device__ __forceinline__ float sm_close(const float (&c)[8]) { return ((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])); }
-
-// columns c .. c + 3 of a row of H columns (row == nullptr: a row that does not exist): one 16-byte load where the table allows it
-// (vec: 16-byte aligned rows) and the four columns exist, else scalar loads; columns >= H are never read and count as 0
-__device__ __forceinline__ float4 sm_chunk(const float* __restrict__ row, int c, int H, bool vec) {
-  if (!row) return zero4();
-  if (vec && c + 3 < H) return *reinterpret_cast<const float4*>(row + c);
-  float4 v;
-  v.x = c < H ? row[c] : 0.f;
-  v.y = c + 1 < H ? row[c + 1] : 0.f;
-  v.z = c + 2 < H ? row[c + 2] : 0.f;
-  v.w = c + 3 < H ? row[c + 3] : 0.f;
-  return v;
-}
 
 // ---- the prologue: eight lanes per query, lane j is chain j
 __global__ __launch_bounds__(SM_NT) void sim_queries_kernel(int Q, int N, int H, const float* __restrict__ content, long ldc,
@@ -77,15 +47,11 @@ __global__ __launch_bounds__(SM_NT) void sim_panel_kernel(int Q, int n0, int n, 
   __shared__ float nrm[SM_T * 8];                                        // the eight chains of every item's x . x
   const int tid = threadIdx.x, tn = tid & 15, tq = tid >> 4;
   const int q0 = blockIdx.x * SM_T, j0 = blockIdx.y * SM_T;
-  // what this thread loads of a chunk: two 4-column pieces per tile — piece e = tid + 256 u is columns 4 (e & 7) .. + 3 of row e >> 3
   const float* xrow[2];
   const float* yrow[2];
-  int lcol[2], lat[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int e = tid + SM_NT * u, row = e >> 3;
-    lcol[u] = 4 * (e & 7);
-    lat[u] = row * SM_LD + lcol[u];
+    const int row = sm_piece_row(tid, u);
     xrow[u] = q0 + row < Q ? xq + (long)(q0 + row) * ldx : nullptr;
     yrow[u] = j0 + row < n ? content + ((long)n0 + j0 + row) * ldc : nullptr;
   }
@@ -99,53 +65,7 @@ __global__ __launch_bounds__(SM_NT) void sim_panel_kernel(int Q, int n0, int n, 
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][m][j] = 0.f;
   float na = 0.f, nb = 0.f;
-
-  float4 px[2], py[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    px[u] = sm_chunk(xrow[u], lcol[u], H, vecq != 0);
-    py[u] = sm_chunk(yrow[u], lcol[u], H, vecc != 0);
-  }
-  for (int k0 = 0; k0 < H; k0 += SM_KC) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      *reinterpret_cast<float4*>(xs + lat[u]) = px[u];
-      *reinterpret_cast<float4*>(ys + lat[u]) = py[u];
-    }
-    __syncthreads();
-    if (k0 + SM_KC < H) {
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        px[u] = sm_chunk(xrow[u], k0 + SM_KC + lcol[u], H, vecq != 0);
-        py[u] = sm_chunk(yrow[u], k0 + SM_KC + lcol[u], H, vecc != 0);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < SM_KC / 8; ++s) {
-      float b[SM_R][8];
-#pragma unroll
-      for (int m = 0; m < SM_R; ++m) {
-        const float4 lo = *reinterpret_cast<const float4*>(ys + (tn + 16 * m) * SM_LD + 8 * s);
-        const float4 hi = *reinterpret_cast<const float4*>(ys + (tn + 16 * m) * SM_LD + 8 * s + 4);
-        b[m][0] = lo.x; b[m][1] = lo.y; b[m][2] = lo.z; b[m][3] = lo.w;
-        b[m][4] = hi.x; b[m][5] = hi.y; b[m][6] = hi.z; b[m][7] = hi.w;
-      }
-#pragma unroll
-      for (int i = 0; i < SM_R; ++i) {
-        const float4 lo = *reinterpret_cast<const float4*>(xs + (tq + 16 * i) * SM_LD + 8 * s);
-        const float4 hi = *reinterpret_cast<const float4*>(xs + (tq + 16 * i) * SM_LD + 8 * s + 4);
-        const float a[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-        for (int m = 0; m < SM_R; ++m)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) acc[i][m][j] = fmaf(a[j], b[m][j], acc[i][m][j]);
-      }
-      const float ya = ys[nitem * SM_LD + 8 * s + npair], yb = ys[nitem * SM_LD + 8 * s + npair + 1];
-      na = fmaf(ya, ya, na);
-      nb = fmaf(yb, yb, nb);
-    }
-    __syncthreads();
-  }
+  sm_contract<true>(H, xrow, vecq != 0, yrow, vecc != 0, xs, ys, acc, na, nb);
 
   nrm[nitem * 8 + npair] = na;
   nrm[nitem * 8 + npair + 1] = nb;

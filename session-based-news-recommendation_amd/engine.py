@@ -1656,6 +1656,66 @@ class TcarEngine(OpLevelStep):
             self.sel_score[gone] = 0.0
         return self.sel_topk[:Q], self.sel_score[:Q]
 
+    # ---- the duplicate audit (include/tcar_dupes.h): every pair of content rows once, three numbers per item
+    DUP_LAUNCH_TILES = 2 ** 18        # tiles of 64 x 64 pairs in one launch at the default stripe (a choice: every launch stays short)
+
+    def _dupes_request(self, threshold, window, stripe):
+        """The request of a find_duplicates call, validated before anything is uploaded -> (t, (lo, hi) or None, stripe)"""
+        if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+                or not 0.0 < float(np.float32(threshold)) <= 1.0:
+            raise ValueError("threshold must be a real number in (0, 1]")
+        bounds = None
+        if window is not None:
+            if getattr(self, "_item_keys", None) is None:
+                raise ValueError("a window compares item keys: call set_item_keys(keys) first")
+            try:
+                lo, hi = (np.asarray(x) for x in window)
+                if lo.ndim or hi.ndim or not (np.issubdtype(lo.dtype, np.integer) and np.issubdtype(hi.dtype, np.integer)):
+                    raise TypeError
+            except (TypeError, ValueError):
+                raise ValueError("window = (lo, hi): ONE pair of integer scalars, the members are the items with lo <= key < hi") from None
+            bounds = tuple(int(min(max(int(x), -2 ** 31), 2 ** 31 - 1)) for x in (lo, hi))
+        blocks = (self.geo.N + 63) // 64
+        if stripe is None:
+            stripe = max(1, self.DUP_LAUNCH_TILES // blocks)
+        elif isinstance(stripe, (bool, np.bool_)) or not isinstance(stripe, (int, np.integer)) or stripe < 1:
+            raise ValueError("stripe must be an int >= 1 (row blocks of 64 items per launch; None: the default)")
+        return float(np.float32(threshold)), bounds, int(min(stripe, blocks))
+
+    def find_duplicates(self, threshold: float = 0.98, window=None, stripe: Optional[int] = None) -> "DuplicateAudit":
+        """Which articles of the catalog are copies of each other?  For every item i, over the `sim` of similar_items (the content
+        cosine of include/tcar_mmr.h, bit for bit): count[i] = the number of OTHER items j with sim(i, j) >= threshold, partner[i] =
+        the most similar of them (cosine, then item id, descending; -1 where there is none) and sim[i] = sim(i, partner[i]) (0
+        there).  DuplicateAudit(count int32 [N], partner int32 [N], sim f32 [N]): device views, valid until the next
+        find_duplicates.  window = (lo, hi), ONE pair of scalars over the keys of set_item_keys: only the items with lo <= key < hi
+        are audited, against each other (the others count 0).  One triangular pass over all pairs (include/tcar_dupes.h): no
+        matrix, no pair list, nothing that can overflow; the result is the same bits on every run and for every `stripe` (row
+        blocks of 64 items per launch; default: the most for which a launch holds at most 2^18 tiles).  Ordered on the engine's
+        stream behind every earlier update_items; no host synchronisation.  similar_items(flagged ids) lists ALL partners of a
+        flagged row."""
+        t, bounds, stripe = self._dupes_request(threshold, window, stripe)
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("find_duplicates needs the whole catalog on this engine (no shard)")
+        self.flush()
+        self.ws.ensure([Spec("dup_r", (g.N,), F32), Spec("dup_count", (g.N,), I32), Spec("dup_best", (g.N,), torch.int64),
+                        Spec("dup_partner", (g.N,), I32), Spec("dup_sim", (g.N,), F32)])
+        d = _lib.Dupes()
+        d.t, d.stripe = t, stripe
+        if bounds is not None:
+            d.key, d.lo, d.hi = self._item_keys.data_ptr(), bounds[0], bounds[1]
+        d.r, d.count, d.best = self.dup_r.data_ptr(), self.dup_count.data_ptr(), self.dup_best.data_ptr()
+        d.partner, d.partner_sim = self.dup_partner.data_ptr(), self.dup_sim.data_ptr()
+        check(self.lib.tcar_dupes_step(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_dupes_step")
+        return DuplicateAudit(self.dup_count[:g.N], self.dup_partner[:g.N], self.dup_sim[:g.N])
+
+
+class DuplicateAudit(NamedTuple):
+    """what TcarEngine.find_duplicates returns: device views [N], valid until the next find_duplicates"""
+    count: torch.Tensor                         # int32: other items at or above the threshold
+    partner: torch.Tensor                       # int32: the most similar of them, -1 where there is none
+    sim: torch.Tensor                           # f32: its similarity, 0 where there is none
+
 
 class SectionLists(NamedTuple):
     """what TcarEngine.recommend_sections returns: device views, valid until the next streamed call"""

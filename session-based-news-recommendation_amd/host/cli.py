@@ -241,11 +241,37 @@ def build_parser() -> argparse.ArgumentParser:
     by_name = {o.name: o for o in EVAL_OPTIONS}
     for name in _HELP_ORDER:                                 # every evaluation option defaults to 0: off
         ap.add_argument("--" + name, default=0, type=by_name[name].type, help=by_name[name].help)
+    ap.add_argument("--audit_duplicates", default=0.0, type=float,
+                    help="T in (0, 1]: behind training or testing, audit the WHOLE catalog for near-duplicate articles "
+                         "(include/tcar_dupes.h: every pair of content rows once, cosine >= T) and print how many articles fall into "
+                         "how many groups.  Not an evaluation option; not with --dp_mode sharded or --gpus > 1.  0: off")
     ap.add_argument("--synthetic", default=0, type=int, help="N items of a synthetic Globo-like fold (no files)")
     ap.add_argument("--synthetic_train", default=100000, type=int)
     ap.add_argument("--synthetic_test", default=10000, type=int)
     ap.add_argument("--seed", default=2020, type=int)
     return ap
+
+
+def check_audit_option(threshold, dp_mode="replica", gpus=1):
+    """Refuse an --audit_duplicates that cannot work, before any data is loaded (0: off, nothing to check)"""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or threshold != threshold \
+            or not 0 <= threshold <= 1:
+        raise ValueError("--audit_duplicates must be a cosine threshold in (0, 1] (0: off)")
+    if threshold and dp_mode == "sharded":
+        raise ValueError("--audit_duplicates pairs every article with every other on ONE engine with the whole catalog; it cannot be "
+                         "combined with --dp_mode sharded")
+    if threshold and gpus and gpus > 1:
+        raise ValueError("--audit_duplicates cannot be combined with --gpus > 1: one engine audits the catalog")
+
+
+def audit_duplicates(model, threshold):
+    """the audit behind --audit_duplicates: one line, and what it was computed from -> (groups, audit)"""
+    import torch
+    groups, audit = model.duplicate_articles(threshold=threshold)
+    pairs = int(audit.count.sum(dtype=torch.int64).item()) // 2             # every pair counts once at each of its two articles
+    print("duplicate audit (cosine >= {}): {} articles in {} groups, largest {}, {} pairs".format(
+        threshold, sum(len(g) for g in groups), len(groups), max((len(g) for g in groups), default=0), pairs))
+    return groups, audit
 
 
 def load_datas(args):
@@ -304,6 +330,7 @@ def main(argv=None):
     np.random.seed(args.seed)
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
     check_eval_options(vars(args), args.gpus)
+    check_audit_option(args.audit_duplicates, args.dp_mode, args.gpus)
     dp_group = None
     if args.gpus > 1:
         import torch
@@ -346,6 +373,8 @@ def main(argv=None):
         with np.load(model_path, allow_pickle=False) as ck:          # plain arrays only: nothing is unpickled
             model.engine.load_state(ck)
         model.test(None, sent, a)
+    if args.audit_duplicates:
+        audit_duplicates(model, args.audit_duplicates)
     if dp_group is not None:
         import torch.distributed as dist
         model.engine.close()                     # the direct RCCL communicator, before the group it was built through

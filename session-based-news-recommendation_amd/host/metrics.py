@@ -56,6 +56,32 @@ def related_sums(topk, sims, ids, cat):
     return float(np.asarray(sims, dtype=np.float64)[listed].sum()), float(same.sum())
 
 
+def duplicate_groups(partner):
+    """The partner array of a duplicate audit (engine.TcarEngine.find_duplicates: partner[i] = the item most similar to i among those
+    at or above the threshold, -1 = none) -> the groups of size >= 2, each a sorted list of ids, ordered by their first id: a
+    union-find over the edges i -- partner[i].  These are BEST-PARTNER clusters: every item is joined to its one best partner only,
+    so a group is a subset of a connected component of the threshold graph (two items above the threshold of each other whose best
+    partners lie elsewhere may fall into different groups).  similar_items(ids of a group) lists every partner."""
+    partner = np.asarray(partner, dtype=np.int64).reshape(-1)
+    root = np.arange(partner.size)
+
+    def find(i):
+        while root[i] != i:
+            root[i] = root[root[i]]
+            i = root[i]
+        return i
+
+    for i in np.flatnonzero(partner >= 0).tolist():
+        a, b = find(i), find(int(partner[i]))
+        if a != b:
+            root[max(a, b)] = min(a, b)
+    groups = {}
+    for i in np.flatnonzero(partner >= 0).tolist():
+        for j in (i, int(partner[i])):
+            groups.setdefault(find(j), set()).add(j)
+    return [sorted(g) for _, g in sorted(groups.items())]
+
+
 def cau_metrics(preds, labels, cutoff=20):
     """Same contract as util.py:8-18: rank = 1 + #{j: preds[j] > preds[label]} (strict)."""
     preds = np.asarray(preds)

@@ -563,6 +563,19 @@ class Seq2SeqAttNN():
             self._install_categories()
         return self.engine.similar_items(k=k, window=window, max_per_category=max_per_category, **query, **kw)
 
+    def duplicate_articles(self, threshold=0.98, window=None, **kw):
+        """Which articles of the catalog are copies of each other: (groups, audit).  `audit` is what engine.TcarEngine.find_duplicates
+        returns — for every article the number of others whose content cosine with it is >= threshold, the most similar of them and
+        its cosine, on the device — and `groups` the best-partner clusters of host.metrics.duplicate_groups: sorted lists of 0-based
+        ids, two or more each.  window = (lo, hi), ONE pair of scalars in minutes since the earliest publish time
+        (`minute_of(datetime)`): only the articles published in [lo, hi) are audited, against each other — e.g. the fresh window
+        behind update_articles.  Not on the catalog-sharded engine."""
+        from .metrics import duplicate_groups
+        if window is not None and not self._sharded():
+            self._item_keys()
+        audit = self.engine.find_duplicates(threshold=threshold, window=window, **kw)
+        return duplicate_groups(audit.partner.cpu().numpy()), audit
+
     def retrieve(self, sessions, C, window=None, **kw):      # noqa: N803
         """A shortlist of the C best next items (1 <= C <= 1024) of every session of `sessions` — a feed dict as `recommend` takes
         it — from coarse scores: (ids [B, C] int32, coarse_scores [B, C] f32) on the device, -1 / -inf where fewer than C items are

@@ -941,6 +941,12 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("similar_items() needs the whole catalog on one engine (no shard): related items over shards are not "
                              "built yet")
 
+    def find_duplicates(self, threshold: float = 0.98, window=None, stripe: Optional[int] = None):
+        """not on the catalog-sharded engine (TcarEngine.find_duplicates pairs every row with every other row of ONE table; the audit
+        over shards as a collective is not built)"""
+        raise _lib.TcarError("find_duplicates() needs the whole catalog on one engine (no shard): the audit over shards is not "
+                             "built yet")
+
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
         """not under this name on the catalog-sharded engine (include/tcar_catalog.h takes the whole catalog): a row's derived state
         lives on the rank that owns it and the ranks have to agree on the update — that is shard_update_items(), a collective"""

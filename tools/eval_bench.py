@@ -72,6 +72,16 @@ clock around `iters` calls ending in a device synchronise, the upload of the ids
 rounds.  Then the split of the call on the device: events around the whole tcar_similar_step and around its cosine panels alone
 (tcar_sim_panel over every panel, on the buffers the call left); the rest is the folds with the prologue and the finish.
 
+       python tools/eval_bench.py [iters] [--n_items N] --duplicates T [--dup_dense] [--rounds R]
+
+--duplicates T: TcarEngine.find_duplicates(T) (include/tcar_dupes.h: every pair of content rows once), each call synchronised, the
+median of max(iters, 3) calls per round, beside the workaround in the same process: similar_items(512 consecutive ids, k=1) over all
+N rows, the host clock around the whole sweep ending in a device synchronise.  Above N = 200,000 the workaround is timed on 16 batches
+and scaled to ceil(N / 512); the line says so.  Then the split of the audit by device events: tcar_dup_rnorm, the tcar_dup_tiles
+launches of the default stripe (with the fp32 FMA rate of the upper triangle, diagonal tiles whole, and the time per launch) and
+tcar_dup_reset + tcar_dup_finish.  --dup_dense: afterwards every content row is overwritten with ONE row — every pair matches, every
+tile flushes all its 128 rows — and the audit is timed again: what the atomics cost when everything matches.
+
        python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --update U[,U...] [--sharded W] [--rounds R]
 
 --update U: TcarEngine.update_items (include/tcar_catalog.h) of U random distinct rows on an engine whose time block is clean (so the
@@ -110,6 +120,8 @@ ap.add_argument("--diversity", type=float, default=0.0,
                      "with the plain two-stage call, and the tcar_mmr_walk launch alone with the bytes/s of its gather")
 ap.add_argument("--k", type=int, default=20, help="length of the lists of recommend / recommend_two_stage (with --retrieve) and of a section (with --sections)")
 ap.add_argument("--similar", type=int, default=0, help="Q: similar_items for Q catalog ids beside the torch workaround that materialises [N, Q]")
+ap.add_argument("--duplicates", type=float, default=0.0, help="T in (0, 1]: find_duplicates(T) beside similar_items(512 ids, k=1) over all rows")
+ap.add_argument("--dup_dense", action="store_true", help="with --duplicates: also the worst case, every content row equal")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
 ap.add_argument("--scoring", type=str, default="bf16x3-mixed", help="scoring mode of the engine (f32 | bf16x3 | bf16x3-mixed | bf16)")
@@ -427,6 +439,86 @@ if shorts:
                       "per further round" % (N, rnd, c, a.diversity, d2 * 1e3, d3 * 1e3, dd * 1e3, (dd - 0.5 * (d2 + d3)) * 1e3, K, wk,
                                              wk / (dd * 1e3), w1, gathered / 1e6, gathered / (w1 * 1e-3) / 1e12, (wk - w1) / max(K - 1, 1)))
         sys.stdout.flush()
+    sys.exit(0)
+if a.duplicates:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--duplicates needs the whole catalog on one engine: not with --sharded")
+    T_, g = a.duplicates, eng.geo
+    nb = (N + 63) // 64
+    calls = max(iters, 3) if N <= 200000 else 3
+    QB = 512
+    nbatch = (N + QB - 1) // QB
+    sampled = nbatch if N <= 200000 else 16
+
+    def audit_ms():
+        out = []
+        for _ in range(calls):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            eng.find_duplicates(T_)
+            torch.cuda.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return float(np.median(out))
+
+    def workaround_ms():
+        """similar_items(512 ids, k=1) over `sampled` batches spread over the catalog, scaled to all nbatch of them"""
+        starts = np.linspace(0, nbatch - 1, sampled).astype(np.int64) * QB
+        eng.similar_items(np.arange(0, min(QB, N), dtype=np.int32), k=1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s0 in starts:
+            eng.similar_items(np.arange(s0, min(s0 + QB, N), dtype=np.int32), k=1)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 * nbatch / sampled
+
+    def split_ms():
+        """device events around the three parts of one audit, on the buffers the last call left: rnorm | the stripes | reset + finish"""
+        lib, st = eng.lib, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        cp = C_.c_void_p(eng.E.data_ptr() + 4 * g.ldh)
+        stripe = eng._dupes_request(T_, None, None)[2]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ev[0].record()
+        assert lib.tcar_dup_rnorm(N, g.H, cp, g.ek, vp(eng.dup_r), st) == 0
+        ev[1].record()
+        launches = 0
+        for b0 in range(0, nb, stripe):
+            assert lib.tcar_dup_tiles(N, g.H, cp, g.ek, vp(eng.dup_r), b0, min(b0 + stripe, nb), T_, None, 0, 0, vp(eng.dup_count),
+                                      vp(eng.dup_best), st) == 0
+            launches += 1
+        ev[2].record()
+        assert lib.tcar_dup_reset(N, vp(eng.dup_count), vp(eng.dup_best), st) == 0
+        assert lib.tcar_dup_finish(N, vp(eng.dup_best), vp(eng.dup_partner), vp(eng.dup_sim), st) == 0
+        ev[3].record()
+        torch.cuda.synchronize()
+        return [ev[i].elapsed_time(ev[i + 1]) for i in range(3)] + [launches, stripe]
+
+    def report(what, rnd, with_workaround):
+        da = audit_ms()
+        dw = workaround_ms() if with_workaround else None
+        rn, tiles, fin, launches, stripe = split_ms()
+        count = eng.find_duplicates(T_).count
+        flagged, pairs = int((count > 0).sum().item()), int(count.sum(dtype=torch.int64).item()) // 2
+        flops = 2.0 * (nb * (nb + 1) // 2) * 64 * 64 * ((g.H + 7) // 8 * 8)
+        line = ("N=%d t=%g %s round %d: find_duplicates %.3f ms (median of %d synchronised calls; %d rows flagged, %d pairs); on the "
+                "device: rnorm %.3f ms, tiles %.3f ms in %d launches of %d row blocks (%.3f ms per launch, %.1f TFLOP/s fp32 over the "
+                "upper triangle), reset + finish %.3f ms" % (N, T_, what, rnd, da, calls, flagged, pairs, rn, tiles, launches, stripe,
+                                                            tiles / launches, flops / (tiles * 1e-3) / 1e12, fin))
+        if dw is not None:
+            line += ("; workaround similar_items(%d ids, k=1) over all rows %.1f ms (%s) = %.2fx the audit"
+                     % (QB, dw, "all %d batches timed" % nbatch if sampled == nbatch else
+                        "%d of %d batches timed, scaled" % (sampled, nbatch), dw / da))
+        print(line)
+        sys.stdout.flush()
+
+    for rnd in range(a.rounds):
+        report("synthetic content", rnd, True)
+    if a.dup_dense:
+        eng.E[:N, g.ldh:g.ldh + g.H] = eng.E[1, g.ldh:g.ldh + g.H].clone()      # the content is read in place: every row is now one row
+        torch.cuda.synchronize()
+        for rnd in range(a.rounds):
+            report("dense (all rows equal)", rnd, False)
     sys.exit(0)
 if a.similar:
     import ctypes as C_
