@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("TCAR_LIB") or os.path.join(PKG_DIR, "libtcar_hip.so")
 SOURCES = ["gemm_f32.hip", "gemm_bf16.hip", "embed.hip", "pool.hip", "score.hip", "ce.hip", "optim.hip", "step.hip", "mha.hip",
            "sampler.hip", "norm.hip", "shard.hip", "segsum.hip", "query.hip", "select.hip", "cand.hip", "retrieve.hip",
-           "sections.hip", "catalog.hip", "mmr.hip", "similar.hip", "dupes.hip", "buildid.hip"]
+           "sections.hip", "catalog.hip", "mmr.hip", "similar.hip", "dupes.hip", "warm.hip", "buildid.hip"]
 BUILD_ID_TU = "buildid.hip"        # the one translation unit that carries the digest of all sources
 
 
@@ -38,13 +38,15 @@ def _hipcc() -> str:
 # side; streamed score-and-select; its publish-time
 # windows; its per-category caps; one list per category from one pass (bound before the ragged layer, so its ragged twin takes the
 # ragged descriptor as a plain pointer); the state merge and the shard's fold of the catalog-sharded serving path; candidate-list scoring;
+# warm start (tcar_warm.h: item rows of cold articles blended from their related items' rows and installed by the catalog update; bound
+# before the layers whose descriptors it names — its struct holds them as plain pointers —, as the sections are before the ragged layer);
 # the streamed top-C shortlist and the two-stage step; its diversified close (the MMR walk over content; bound before the ragged
 # layer, like the sections); related items by content cosine (the cosine panels of tcar_similar.h under the folds of the serving layers);
 # the all-pairs duplicate audit over the same cosine (tcar_dupes.h: its own kernels, on the tile of the panels);
 # the shortlist merge, the owner-aware candidate gather and the shard's side of both on the catalog-sharded engine; ragged batches (sessions of mixed lengths) under every serving step.
 ABI_LAYERS = [("", "tcar_hip.h"), ("CATALOG", "tcar_catalog.h"), ("CATALOG_SHARD", "tcar_catalog_shard.h"), ("SERVE", "tcar_serve.h"),
               ("WINDOW", "tcar_window.h"), ("QUOTA", "tcar_quota.h"), ("SECTIONS", "tcar_sections.h"),
-              ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"), ("RETRIEVE", "tcar_retrieve.h"),
+              ("SERVE_SHARD", "tcar_serve_shard.h"), ("CAND", "tcar_cand.h"), ("WARM", "tcar_warm.h"), ("RETRIEVE", "tcar_retrieve.h"),
               ("MMR", "tcar_mmr.h"), ("SIMILAR", "tcar_similar.h"), ("DUPES", "tcar_dupes.h"), ("RETRIEVE_SHARD", "tcar_retrieve_shard.h"),
               ("RAGGED", "tcar_ragged.h")]
 

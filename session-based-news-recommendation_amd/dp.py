@@ -435,6 +435,12 @@ class DPEngine(TcarEngine):
         replica_update_items(), a collective"""
         raise _lib.TcarError("update_items() is not for the data-parallel replicas: the ranks would have to agree on the update")
 
+    def warm_start_items(self, ids, k: int = 16, min_sim: float = 0.0, exclude=None, window=None, panel=None):
+        """not on a replica: the call writes catalog rows, and the ranks would have to agree on it as they do in
+        replica_update_items(); the collective form is not built"""
+        raise _lib.TcarError("warm_start_items() needs the whole catalog on one engine, not the data-parallel replicas: the ranks "
+                             "would have to agree on the rows")
+
     def replica_update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None, verify: bool = True) -> None:
         """TcarEngine.update_items on every replica.  A COLLECTIVE when `verify` is set and collectives are live: every rank passes
         the same request; it is validated (the same ValueErrors, before anything else), the ranks compare its digest

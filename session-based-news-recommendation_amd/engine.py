@@ -1241,18 +1241,24 @@ class TcarEngine(OpLevelStep):
         return SectionLists(self.sec_topk[:B], self.sec_score[:B], self.sel_topk[:B], self.sel_score[:B])
 
     # ---- in-place catalog updates (include/tcar_catalog.h): publish, correct and retire articles in a live engine
+    def _catalog_ids(self, ids) -> np.ndarray:
+        """the rows a call names, as update_items and warm_start_items take them: an integer array [U], U >= 1, 0-based, each in
+        [0, N), pairwise distinct"""
+        ids = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        if ids.ndim != 1 or ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("ids must be an integer array [U] of at least one catalog row")
+        if int(ids.min()) < 0 or int(ids.max()) >= self.geo.N:
+            raise ValueError("ids must lie in [0, N = %d)" % self.geo.N)
+        if np.unique(ids).size != ids.size:
+            raise ValueError("ids must be pairwise distinct")
+        return ids
+
     def _update_request(self, ids, content, item_rows, mwdhm, keys, categories):
         """The request of an update_items call, validated before anything is uploaded or launched -> (ids int32 [U], then content /
         item_rows float32 [U, H], mwdhm int32 [U, 5], keys / categories int32 [U], each None where the call brings none)."""
         g = self.geo
-        ids = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
-        if ids.ndim != 1 or ids.size == 0 or not np.issubdtype(ids.dtype, np.integer):
-            raise ValueError("ids must be an integer array [U] of at least one catalog row")
+        ids = self._catalog_ids(ids)
         U = int(ids.size)
-        if int(ids.min()) < 0 or int(ids.max()) >= g.N:
-            raise ValueError("ids must lie in [0, N = %d)" % g.N)
-        if np.unique(ids).size != U:
-            raise ValueError("ids must be pairwise distinct")
         if all(x is None for x in (content, item_rows, mwdhm, keys, categories)):
             raise ValueError("update_items needs at least one of content, item_rows, mwdhm, keys, categories")
 
@@ -1361,6 +1367,103 @@ class TcarEngine(OpLevelStep):
         if mwdhm is not None:
             self._mwdhm_host[ids] = mwdhm
             self._index_stale = True
+
+    # ---- warm start (include/tcar_warm.h): item rows for newly published articles from the rows of their content neighbours
+    def _warm_request(self, ids, k, min_sim, exclude, window, panel: Optional[int]):
+        """The request of a warm_start_items call, validated before anything is uploaded -> (ids int32 [U], k, min_sim, exclude
+        int32 [U, X] or None, (lo, hi) int32 [U] each or None, panel)"""
+        ids = self._catalog_ids(ids)
+        U = int(ids.size)
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 64:
+            raise ValueError("k must be an int in [1, 64] (the donors of one row)")
+        if isinstance(min_sim, (bool, np.bool_)) or not isinstance(min_sim, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(min_sim) <= 1.0:
+            raise ValueError("min_sim must be a real number in [0, 1]")
+        excl = None
+        if exclude is not None:
+            ex = exclude.detach().cpu().numpy() if isinstance(exclude, torch.Tensor) else np.asarray(exclude)
+            if ex.ndim != 2 or ex.shape[0] != U or not np.issubdtype(ex.dtype, np.integer):
+                raise ValueError("exclude must be an integer array [U, X] with U = %d rows" % U)
+            if ex.shape[1]:
+                e64 = ex.astype(np.int64)
+                excl = np.ascontiguousarray(np.where((e64 < 0) | (e64 >= 2 ** 31), -1, e64), dtype=np.int32)
+        panel = self._panel_request(panel, window, self.geo.Npad)
+        bounds = self._window_bounds(window, U) if window is not None else None      # (ONE pair of scalars, or one pair per id)
+        return np.ascontiguousarray(ids, dtype=np.int32), int(k), float(np.float32(min_sim)), excl, bounds, panel
+
+    def warm_start_items(self, ids, k: int = 16, min_sim: float = 0.0, exclude=None, window=None, panel: Optional[int] = None) -> "WarmStart":
+        """Give the COLD rows `ids` (int [U], validated as update_items validates them: 0-based, in [0, N), pairwise distinct) — newly
+        published articles, whose item row is an untrained draw or a retired article's — the cosine-weighted mean of the trained
+        item rows of their k nearest CONTENT neighbours (the rule of include/tcar_warm.h), computed on the device and installed in
+        place; nothing crosses the host.  The neighbour lists are those of similar_items(ids, k, exclude = ids + exclude, window):
+        every id of the call is excluded as a donor — cold rows do not donate to each other —, exclude int [U, X] adds more per
+        row, and window = (lo, hi), ONE pair of scalars or one pair per id over the keys of set_item_keys, keeps spare and retired
+        rows out of the donor pool (they carry keys above every hi).  A neighbour with a cosine <= 0 or below min_sim (in [0, 1])
+        donates nothing; a row without donors becomes +0 (support 0), which adds nothing to a logit.
+        flush() first, then three calls on the engine's stream, ordered as update_items is; no synchronisation.  Afterwards every
+        buffer of the engine holds, for the named rows, the bytes of an engine built from tables whose item rows are `rows`, and
+        their Adam moments are zero: the contract of update_items(item_rows=rows).  WarmStart(rows [U, H], support [U], wsum [U],
+        donors [U, k], sims [U, k]): views of the workspace on the device, valid until the next streamed call.
+        Workspace: besides the [U, panel] panel buffer of similar_items, the exclusion lists are int32 [U, U + X] — every row names
+        every id of the call — so they grow with U SQUARED (64 MB at U = 4,096, 1 GB at U = 16,384), and every fold scans a row's
+        list once per panel.  Publish a large batch in slices of a few thousand ids, naming the other slices' ids in `exclude` if
+        they must not donate either, or keeping them out of the pool by `window`."""
+        ids, k, min_sim, excl, bounds, panel = self._warm_request(ids, k, min_sim, exclude, window, panel)
+        return self._warm_start(ids, k, min_sim, excl, bounds, panel, zero_moments=True)
+
+    def _warm_start(self, ids: np.ndarray, k: int, min_sim: float, excl, bounds, panel: int, zero_moments: bool) -> "WarmStart":
+        """one tcar_warm_step for a validated request; zero_moments False: the Mi / Vi rows keep every byte (test() hides and
+        restores rows of a model it is not allowed to change)"""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("warm_start_items needs the whole catalog on one engine (no shard)")
+        self.flush()
+        U, X = int(ids.size), int(ids.size) + (int(excl.shape[1]) if excl is not None else 0)
+        words = int(self.lib.tcar_select_state_bytes(1, k)) // 4
+        self._sm_rows = max(getattr(self, "_sm_rows", 0), U)
+        specs = [Spec("panel_buf", (U, panel), F32), Spec("sel_state", (U, words), I32), Spec("sel_topk", (U, k), I32),
+                 Spec("sel_score", (U, k), F32), Spec("sm_xq", (U, g.ldh), F32), Spec("sm_rq", (U,), F32), Spec("sm_qid", (U,), I32),
+                 Spec("excl", (U, X), I32), Spec("warm_rows", (U, _ru(g.H, 4)), F32), Spec("warm_support", (U,), I32),
+                 Spec("warm_wsum", (U,), F32)]
+        if bounds is not None:
+            specs.append(Spec("sm_lohi", (2, self._sm_rows), I32))
+        self.ws.ensure(specs)
+        self.sm_qid[:U].copy_(torch.from_numpy(ids))
+        self.excl[:U, :U] = self.sm_qid[:U][None, :]          # every named id, in every row: built on the device
+        if excl is not None:
+            self.excl[:U, U:].copy_(torch.from_numpy(excl))
+        s = self._serve_desc(k, panel, self.panel_buf, self.sel_state, self.excl, X, outputs=(self.sel_topk, self.sel_score))
+        win = None
+        if bounds is not None:
+            self.sm_lohi[:, :U].copy_(torch.from_numpy(np.stack(bounds)))
+            win = self._window_desc(self._item_keys, self.sm_lohi)
+        self.sel_score[:U].zero_()             # (the finish leaves the score of an empty place untouched: it reads 0)
+        d = _lib.Warm()
+        d.U, d.ids, d.min_sim = U, self.sm_qid.data_ptr(), min_sim
+        d.xq, d.rq, d.serve, d.window = self.sm_xq.data_ptr(), self.sm_rq.data_ptr(), C.addressof(s), C.addressof(win) if win is not None else None
+        d.rows, d.ld_rows = self.warm_rows.data_ptr(), _ru(g.H, 4)
+        d.support, d.wsum, d.zero_moments = self.warm_support.data_ptr(), self.warm_wsum.data_ptr(), int(zero_moments)
+        check(self.lib.tcar_warm_step(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_warm_step")
+        return WarmStart(self.warm_rows[:U, :g.H], self.warm_support[:U], self.warm_wsum[:U], self.sel_topk[:U], self.sel_score[:U])
+
+    def _hide_item_rows(self, ids: np.ndarray, rows: Optional[torch.Tensor] = None):
+        """test(): write `rows` (device f32 [U, ldh]; None: zeros) over the item rows `ids` WITHOUT touching their Adam moments and
+        return what _restore_item_rows takes to put the old rows back — (ids, the old rows), both on the device.  One gather and
+        one tcar_catalog_update on the engine's stream; the planes follow, so a restore leaves every buffer as it was, byte for byte."""
+        g = self.geo
+        if self.shard != (0, g.N):
+            raise _lib.TcarError("hiding item rows needs the whole catalog on one engine (no shard)")
+        self.flush()
+        ids_dev = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int32)).to(self.dev)
+        saved = self.E[ids_dev.long(), :g.ldh].contiguous()
+        self._restore_item_rows((ids_dev, torch.zeros_like(saved) if rows is None else rows))
+        return ids_dev, saved
+
+    def _restore_item_rows(self, token) -> None:
+        ids_dev, rows = token
+        d = _lib.CatalogUpdate()
+        d.U, d.ids, d.item, d.ld_item, d.zero_moments = int(ids_dev.numel()), ids_dev.data_ptr(), rows.data_ptr(), int(rows.stride(0)), 0
+        check(self.lib.tcar_catalog_update(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_catalog_update")
 
     # ---- candidate-list scoring (include/tcar_cand.h): only the rows a session names are read
     CAND_MAX_C = 1024             # slots of one list (CAND_MAX_C of csrc/tcar_common.h)
@@ -1708,6 +1811,15 @@ class TcarEngine(OpLevelStep):
         d.partner, d.partner_sim = self.dup_partner.data_ptr(), self.dup_sim.data_ptr()
         check(self.lib.tcar_dupes_step(C.byref(self._catalog_ctx()), C.byref(d), self._stream()), "tcar_dupes_step")
         return DuplicateAudit(self.dup_count[:g.N], self.dup_partner[:g.N], self.dup_sim[:g.N])
+
+
+class WarmStart(NamedTuple):
+    """what TcarEngine.warm_start_items returns: device views, valid until the next streamed call"""
+    rows: torch.Tensor                          # f32 [U, H]: the rows that were installed
+    support: torch.Tensor                       # int32 [U]: donors with a weight > 0
+    wsum: torch.Tensor                          # f32 [U]: the sum of their weights
+    donors: torch.Tensor                        # int32 [U, k]: the neighbour lists (-1: an empty place)
+    sims: torch.Tensor                          # f32 [U, k]: their cosines
 
 
 class DuplicateAudit(NamedTuple):

@@ -187,12 +187,13 @@ _HELP_ORDER = ("eval_panel", "fresh_hours", "cat_cap", "shard_eval_panel", "shar
 EvalRequest = NamedTuple("EvalRequest", [(o.name, o.type) for o in EVAL_OPTIONS])
 
 
-def check_eval_options(values, gpus=1):
+def check_eval_options(values, gpus=1, options=EVAL_OPTIONS):
     """Refuse a request for the evaluation loop that cannot work: `values` maps dp_mode and any of the options of EVAL_OPTIONS to
     their values (an absent option is off), `gpus` is the number of data-parallel ranks.  The options are walked in the table's
-    order, each one's rules in theirs, and the first broken rule is raised as a ValueError."""
+    order, each one's rules in theirs, and the first broken rule is raised as a ValueError.  `options`: another table of the same
+    shape (eval_passes.COLD_START_OPTIONS)."""
     sharded = values.get("dp_mode", "replica") == "sharded"
-    for opt in EVAL_OPTIONS:
+    for opt in options:
         v = values.get(opt.name, 0)
         for kind, arg, text in opt.rules:
             if kind == "type":
@@ -241,6 +242,10 @@ def build_parser() -> argparse.ArgumentParser:
     by_name = {o.name: o for o in EVAL_OPTIONS}
     for name in _HELP_ORDER:                                 # every evaluation option defaults to 0: off
         ap.add_argument("--" + name, default=0, type=by_name[name].type, help=by_name[name].help)
+    from .eval_passes import COLD_START_FLAGS, COLD_START_OPTIONS, DEFAULT_DONORS      # (here: eval_passes builds on this module)
+    for flag, opt in zip(COLD_START_FLAGS, COLD_START_OPTIONS):
+        ap.add_argument("--" + flag, dest=opt.name, default=DEFAULT_DONORS if opt.name == "coldstart_donors" else 0, type=opt.type,
+                        help=opt.help)
     ap.add_argument("--audit_duplicates", default=0.0, type=float,
                     help="T in (0, 1]: behind training or testing, audit the WHOLE catalog for near-duplicate articles "
                          "(include/tcar_dupes.h: every pair of content rows once, cosine >= T) and print how many articles fall into "
@@ -331,6 +336,8 @@ def main(argv=None):
     is_train, model_path, input_data = args.train, args.modelpath, args.inputdata
     check_eval_options(vars(args), args.gpus)
     check_audit_option(args.audit_duplicates, args.dp_mode, args.gpus)
+    from .eval_passes import check_cold_start_options
+    check_cold_start_options(vars(args), args.gpus)
     dp_group = None
     if args.gpus > 1:
         import torch

@@ -11,6 +11,9 @@
 
 `active_passes` lists them in the ONE order that is the order of their engine calls behind a streamed call, of their lines and of
 their collectives.  The classes say where a shared workspace of the engine fixes that order.
+
+A pass that WRITES the engine (ColdStart) declares its options here, in COLD_START_OPTIONS — rows of the same shape as
+cli.EVAL_OPTIONS, walked by the same cli.check_eval_options —, beside the pass they switch on.
 """
 from __future__ import annotations
 
@@ -19,7 +22,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import metrics as M
+from . import cli, metrics as M
+from .cli import EvalOption, Rule
 from .data import pack_sessions
 
 
@@ -236,8 +240,143 @@ class Capped(EvalPass):
         return {"mrr": c_mrr, "recall": c_hit, "ndcg": c_ndcg}
 
 
-def active_passes(model, req):
-    """the passes that `req` turns on, in the order of the module's docstring"""
+MAX_DONORS = 64            # donors of one warm-started row (the k of engine.TcarEngine.warm_start_items; SEL_MAX_K of csrc/tcar_common.h)
+DEFAULT_DONORS = 16
+
+# (name: the key of the model's args and the dest of the flag; the flags are COLD_START_FLAGS, in this order)
+COLD_START_OPTIONS = (
+    EvalOption("coldstart", float,
+               "FRAC in (0, 0.5]: behind its batches, evaluation draws a FRAC sample of the distinct label articles of the data "
+               "(a random stream of its own: a function of --seed alone) and evaluates the sessions whose label is in the sample "
+               "three ways — with the trained item rows, with those rows zeroed, and with those rows written by "
+               "warm_start_items (include/tcar_warm.h: the cosine-weighted mean of the rows of --coldstart_donors content "
+               "neighbours, no sampled article a donor) — and prints their Recall@20 and MRR@20 side by side: what a warm-started "
+               "row is worth.  The engine is left byte for byte as found.  Needs --eval_panel; not with --dp_mode sharded or "
+               "--gpus > 1.  0: off",
+               (Rule("type", (int, float, np.integer, np.floating), "--eval_coldstart must be a number (0: off)"),
+                Rule("finite", None, "--eval_coldstart must be a fraction in (0, 0.5] (0: off)"),
+                Rule("range", (None, 0.5, None), "--eval_coldstart must be at most 0.5: the donors are the articles that are NOT sampled"),
+                Rule("engine", "one", "--eval_coldstart rewrites item rows of ONE engine with the whole catalog; it cannot be combined with "
+                                      "--dp_mode sharded"),
+                Rule("one_process", None, "--eval_coldstart cannot be combined with --gpus > 1: the ranks would have to agree on the rows"),
+                Rule("needs", "eval_panel", "--eval_coldstart needs --eval_panel P: its sessions are evaluated by the streamed evaluation"))),
+    EvalOption("coldstart_donors", int,
+               "K: the donors of one warm-started row under --eval_coldstart, 1 <= K <= %d (default %d)" % (MAX_DONORS, DEFAULT_DONORS),
+               (Rule("type", (int, np.integer), "--coldstart_donors must be an integer in [1, %d]" % MAX_DONORS),
+                Rule("range", (1, MAX_DONORS, None), "--coldstart_donors must be in [1, %d]" % MAX_DONORS))),
+)
+COLD_START_FLAGS = ("eval_coldstart", "coldstart_donors")
+
+
+class ColdStartRequest(NamedTuple):
+    frac: float
+    donors: int
+
+
+def check_cold_start_options(values, gpus=1):
+    """refuse an --eval_coldstart / --coldstart_donors that cannot work: `values` as cli.check_eval_options takes them (dp_mode,
+    eval_panel and the names of COLD_START_OPTIONS), the first broken rule as a ValueError"""
+    cli.check_eval_options(values, gpus=gpus, options=COLD_START_OPTIONS)
+
+
+def cold_start_request(model, args, req) -> Optional[ColdStartRequest]:
+    """the cold-start pass of a test() call: `args` over the values the model was built with, else off; refused as the command
+    line refuses it -> None where it is off"""
+    values = {o.name: args.get(o.name, getattr(model, o.name, 0)) or 0 for o in COLD_START_OPTIONS}
+    if not any(values.values()):
+        return None
+    gpus = max(int(args.get('gpus', 1) or 1), getattr(model, 'dp_world', 1))
+    check_cold_start_options(dict(values, dp_mode=args.get('dp_mode', 'replica'), eval_panel=req.eval_panel), gpus=gpus)
+    if not values["coldstart"]:
+        return None
+    return ColdStartRequest(float(values["coldstart"]), int(values["coldstart_donors"]) or DEFAULT_DONORS)
+
+
+def cold_sample(labels, frac: float, seed: int) -> np.ndarray:
+    """the articles --eval_coldstart treats as cold: round(frac * A) of the A distinct label articles (at least one), drawn
+    without replacement by a RandomState(seed) of its own -> sorted int64 ids.  A function of the labels' SET, frac and seed."""
+    arts = np.unique(np.asarray(labels, dtype=np.int64))
+    if not arts.size:
+        return arts
+    take = min(arts.size, max(1, int(round(frac * arts.size))))
+    return np.sort(np.random.RandomState(seed).choice(arts, size=take, replace=False))
+
+
+def _take(feed, mask):
+    """the sessions of a rectangular feed that `mask` names: every per-session entry restricted, everything else as it is"""
+    B = len(mask)
+    out = {}
+    for name, v in feed.items():
+        if isinstance(v, np.ndarray) and v.shape[:1] == (B,):
+            out[name] = v[mask]
+        elif isinstance(v, (list, tuple)) and len(v) == B:
+            out[name] = [x for x, m in zip(v, mask) if m]
+        else:
+            out[name] = v
+    return out
+
+
+class ColdStart(EvalPass):
+    """eval_coldstart FRAC (include/tcar_warm.h): what is a warm-started item row worth?  The pass needs every label of the data
+    before it can draw its sample, so its engine calls are in `report`, behind the loop: it keeps the window of every streamed
+    call (the feeds are the loop's own results), then evaluates the sessions whose label is sampled again with the sampled rows zeroed and with
+    them warm-started.  The trained figures are the normal pass's own ranks, restricted.  It is the one pass that WRITES the engine:
+    the rows go in through paths that leave the Adam moments alone (engine._hide_item_rows, _warm_start(zero_moments=False)), the
+    old rows are kept on the device, and the restore puts back every byte — E, the planes, nothing else was touched."""
+    key = "coldstart"
+
+    def __init__(self, model, req, cold: ColdStartRequest):
+        super().__init__(model, req)
+        self.cold = cold
+
+    def after_feed(self, feeds, bt, topk, window, rows_cap):
+        self.kept.append((len(feeds), window))                      # (the feeds themselves are in the loop's results)
+
+    def _evaluate(self, sample, results):
+        """the streamed evaluation of the sessions whose label is in `sample`, one call per streamed call of the loop (its feeds
+        are the next ones of `results`) -> their ranks, in the order of the loop"""
+        ranks, at = [], 0
+        for count, window in self.kept:
+            feeds, at = [r.feed for r in results[at:at + count]], at + count
+            masks = [np.isin(np.asarray(f["label"], dtype=np.int64).reshape(-1), sample) for f in feeds]
+            subs = [_take(f, m) for f, m in zip(feeds, masks) if m.any()]
+            if not subs:
+                continue
+            if window is not None:
+                every = np.concatenate(masks)
+                window = tuple(np.asarray(w)[every] for w in window)
+            bt = self.eng.upload(subs[0] if len(subs) == 1 else pack_sessions(subs))
+            rank, _, _ = self.eng.eval_step_streamed(None, k=20, bt=bt, panel=self.req.eval_panel, window=window,
+                                                     max_per_category=self.req.cat_cap or None)
+            ranks.append(rank.clone())
+        return ranks
+
+    def report(self, n, results):
+        eng, k = self.eng, self.cold.donors
+        labels = _labels([r.feed for r in results]) if results else np.zeros(0, np.int64)
+        sample = cold_sample(labels, self.cold.frac, self.m.seed)
+        ranks = {"trained": np.concatenate([r.rank.cpu().numpy() for r in results])[np.isin(labels, sample)] if results else np.zeros(0)}
+        if sample.size:
+            token = eng._hide_item_rows(sample)                     # the sampled rows := 0, the old rows stay on the device
+            zeroed = self._evaluate(sample, results)
+            eng._warm_start(*eng._warm_request(sample, k, 0.0, None, None, self.req.eval_panel), zero_moments=False)
+            warm = self._evaluate(sample, results)
+            eng._restore_item_rows(token)
+            eng.check_forks()         # (synchronises) the figures below come from work enqueued behind test()'s own check
+            for name, kept in (("zeroed", zeroed), ("warm", warm)):
+                ranks[name] = np.concatenate([r.cpu().numpy() for r in kept]) if kept else np.zeros(0, np.int64)
+        recall, mrr = {}, {}
+        for name in ("trained", "zeroed", "warm"):
+            h, m, _ = M.metrics_from_ranks(ranks.get(name, np.zeros(0)), 20)
+            recall[name], mrr[name] = (float(np.mean(x)) if len(x) else 0.0 for x in (h, m))
+        print('cold start ({} articles, {} donors): Recall@20 trained {}, zeroed {}, warm-started {}; MRR@20 {}, {}, {}'.format(
+            int(sample.size), k, recall["trained"], recall["zeroed"], recall["warm"], mrr["trained"], mrr["zeroed"], mrr["warm"]))
+        return {"articles": int(sample.size), "donors": k, "sessions": int(len(ranks["trained"])), "sample": sample.tolist(),
+                "recall": recall, "mrr": mrr}
+
+
+def active_passes(model, req, cold: Optional[ColdStartRequest] = None):
+    """the passes that `req` turns on, in the order of the module's docstring; `cold`: the cold-start pass, behind all of them"""
     two = TwoStage(model, req) if req.eval_shortlist or req.shard_eval_shortlist else None
     return [p for p in (Candidates(model, req) if req.eval_candidates else None,
                         two,
@@ -245,4 +384,5 @@ def active_passes(model, req):
                         Sections(model, req) if req.eval_sections else None,
                         Related(model, req) if req.eval_related else None,
                         LabelsOutside(model, req) if req.fresh_hours else None,
-                        Capped(model, req) if req.cat_cap else None) if p is not None]
+                        Capped(model, req) if req.cat_cap else None,
+                        ColdStart(model, req, cold) if cold else None) if p is not None]

@@ -26,7 +26,7 @@ import torch
 from ..engine import TIME_NAMES, TIME_VOCAB, TcarEngine, VAR_ORDER
 from . import cli, metrics as M
 from .data import pack_sessions, publish_fields
-from .eval_passes import FeedResult, active_passes
+from .eval_passes import COLD_START_OPTIONS, FeedResult, active_passes, cold_start_request
 from .sampler import Sampler
 
 
@@ -142,6 +142,8 @@ class Seq2SeqAttNN():
         # test(): the evaluation options this model is built with (cli.EVAL_OPTIONS: eval_panel ... eval_mixed), each under its name
         for name, value in self._eval_request(args)._asdict().items():
             setattr(self, name, value)
+        for opt in COLD_START_OPTIONS:                               # (eval_passes.cold_start_request checks them, in test())
+            setattr(self, opt.name, args.get(opt.name, 0) or 0)
         self.publish_time = args.get('publish_time')                # per-item datetimes (the keys of a window), as the fold loader returns them
         self._keys = self._key_t0 = None
         self._ds_cache = {}
@@ -423,7 +425,7 @@ class Seq2SeqAttNN():
         # ILD / unexp pair counts and the set of recommended items stay on the device (tcar_eval_diversity)
         self._install_categories()
         eng.reset_coverage()
-        passes = active_passes(self, req)
+        passes = active_passes(self, req, cold_start_request(self, args, req))
         panel, mixed = req.eval_panel or req.shard_eval_panel, bool(req.eval_mixed)
         keep_lists = args.get('is_print') or req.cat_cap
         results, batch, eval_calls = [], 0, 0
@@ -587,7 +589,7 @@ class Seq2SeqAttNN():
         return call(self._feed(sessions), C, window=window, **kw)
 
     # ---------------------------------------------------------------------------------- catalog updates
-    def update_articles(self, ids, content=None, publish_time=None, category=None, item_rows=None):
+    def update_articles(self, ids, content=None, publish_time=None, category=None, item_rows=None, donors=16, donor_window=None):
         """Publish, correct or retire articles in the live engine (engine.TcarEngine.update_items; one call of it): ids int [U] in
         the id convention of the lists `recommend` returns (0-based), then any of content float [U, H], publish_time (U datetimes),
         category int [U] (codes of the fold's category table) and item_rows float [U, H] (new item-table rows; their Adam moments
@@ -599,8 +601,21 @@ class Seq2SeqAttNN():
         fold was loaded with.
         Routed by engine, as score_candidates: the catalog-sharded engine takes it as shard_update_items, the data-parallel replicas
         as replica_update_items, any other engine as update_items.  On the first two EVERY rank calls update_articles with the same
-        arguments — as every rank already builds the same batches — and the ranks check that they did (dp.Collectives.agree)."""
+        arguments — as every rank already builds the same batches — and the ranks check that they did (dp.Collectives.agree).
+        item_rows="neighbors": the update of content, time, key and category runs first, then `warm_start_articles(ids, donors,
+        donor_window)` gives the rows the cosine-weighted mean of the trained rows of their `donors` nearest content neighbours
+        (engine.TcarEngine.warm_start_items) — what a new article gets instead of the spare row's noise.  One engine with the whole
+        catalog only.  Any other string is a ValueError."""
         ids = np.asarray(ids)
+        neighbors = isinstance(item_rows, str)
+        if neighbors:
+            if item_rows != "neighbors":
+                raise ValueError('item_rows must be an array [U, H], None or the string "neighbors" (got %r)' % item_rows)
+            self._refuse_warm_start()
+            item_rows = None
+            if content is None and publish_time is None and category is None:      # nothing but the warm start
+                self.warm_start_articles(ids, donors=donors, window=donor_window)
+                return
         mw = keys = None
         if publish_time is not None:
             when = list(publish_time)
@@ -626,6 +641,25 @@ class Seq2SeqAttNN():
                 self._keys[ids] = keys.astype(np.int32)
         if category is not None:
             self._cat[ids] = np.asarray(category)          # in place: the table on the engine stays THIS table (_cat_on_engine)
+        if neighbors:
+            self.warm_start_articles(ids, donors=donors, window=donor_window)
+
+    def _refuse_warm_start(self):
+        if self._sharded() or hasattr(self.engine, "replica_update_items"):
+            from .._lib import TcarError
+            raise TcarError("warm start needs the whole catalog on one engine: it is not built for the catalog-sharded engine or the "
+                            "data-parallel replicas")
+
+    def warm_start_articles(self, ids, donors=16, window=None, min_sim=0.0, **kw):
+        """Item rows for cold articles from their content neighbours, and nothing else (engine.TcarEngine.warm_start_items; it has the
+        options: exclude, panel): ids int [U], 0-based; donors = the k of the neighbour lists; window = (lo, hi), ONE pair or one
+        pair per article, in minutes since the earliest publish time (`minute_of(datetime)`): only articles published in [lo, hi)
+        donate — the way to keep spare and retired rows, whose keys lie above every hi, out of the pool.  Returns the engine's
+        WarmStart(rows, support, wsum, donors, sims) on the device.  The model keeps no item table of its own: the engine's is the one."""
+        self._refuse_warm_start()
+        if window is not None:
+            self._item_keys()
+        return self.engine.warm_start_items(ids, k=donors, min_sim=min_sim, window=window, **kw)
 
     def _sharded(self) -> bool:
         """is the engine the catalog-sharded one (its serving calls are collectives under names of their own)?"""

@@ -32,6 +32,22 @@ class OpLevelStep:
         arr = (GemmDesc * len(descs))(*descs)
         check(self.lib.tcar_gemm_f32_grouped(layout, len(descs), arr, self._stream()), "tcar_gemm_f32_grouped")
 
+    def rows_blend(self, nbr, sim, table, min_sim: float = 0.0):
+        """tcar_rows_blend (include/tcar_warm.h) on its own: for U neighbour lists (nbr int32 [U, k], sim f32 [U, k], k <= 64; a
+        slot < 0 or >= N is empty) the cosine-weighted mean of the named rows of `table` (f32 [N, H], any row stride) ->
+        (rows f32 [U, H], support int32 [U], wsum f32 [U]), new device tensors.  Op-level: it allocates its results."""
+        import torch
+        U, k = (int(x) for x in nbr.shape)
+        N, H = (int(x) for x in table.shape)
+        ldo = (H + 3) // 4 * 4
+        out = torch.empty(U, ldo, dtype=torch.float32, device=table.device)
+        support = torch.empty(U, dtype=torch.int32, device=table.device)
+        wsum = torch.empty(U, dtype=torch.float32, device=table.device)
+        nbr, sim = nbr.contiguous(), sim.contiguous()
+        check(self.lib.tcar_rows_blend(U, k, N, H, nbr.data_ptr(), sim.data_ptr(), float(min_sim), table.data_ptr(), int(table.stride(0)),
+                                       out.data_ptr(), ldo, support.data_ptr(), wsum.data_ptr(), self._stream()), "tcar_rows_blend")
+        return out[:, :H], support, wsum
+
     # --------------------------------------------------------------------------------------------- forward
     def forward(self, bt: Batch):
         """model_combine.py:52-138 up to the full-catalog logits (Python-sequenced op-level path, fp32 scoring only;

@@ -947,6 +947,12 @@ class ShardedEngine(TcarEngine):
         raise _lib.TcarError("find_duplicates() needs the whole catalog on one engine (no shard): the audit over shards is not "
                              "built yet")
 
+    def warm_start_items(self, ids, k: int = 16, min_sim: float = 0.0, exclude=None, window=None, panel: Optional[int] = None):
+        """not on the catalog-sharded engine (TcarEngine.warm_start_items reads the donors' rows and the content of ONE table and
+        writes through the whole-catalog update; the collective form over shards is not built)"""
+        raise _lib.TcarError("warm_start_items() needs the whole catalog on one engine (no shard): the warm start over shards is "
+                             "not built yet")
+
     def update_items(self, ids, content=None, item_rows=None, mwdhm=None, keys=None, categories=None):
         """not under this name on the catalog-sharded engine (include/tcar_catalog.h takes the whole catalog): a row's derived state
         lives on the rank that owns it and the ranks have to agree on the update — that is shard_update_items(), a collective"""

@@ -92,7 +92,17 @@ in a device synchronise both times: `iters` calls back to back (ms per call at f
 synchronised (the median: what one publisher waits).  Everything alternates for `rounds` rounds.
 With --sharded W: ShardedEngine.shard_update_items(verify=False) (include/tcar_catalog_shard.h) at the shapes of rank 0 of W ranks —
 the sim world, so no collective and no agreement — beside load_params() + the first sharded recommend() on the same engine; the
-time refresh alone is the shard's."""
+time refresh alone is the shard's.
+
+       python tools/eval_bench.py [iters] [--n_items N] [--scoring MODE] --warm U[,U...] [--donors K] [--rounds R]
+
+--warm U: TcarEngine.warm_start_items (include/tcar_warm.h) of U random distinct rows, K donors each (--donors, default 16), beside the
+two calls it is to be read against on the same engine and the same ids: update_items(ids, item_rows = host rows) — what installing
+rows costs when they come from the host — and similar_items(ids, k = K) — what the neighbour lists cost.  Each is timed as --update
+times a call: `iters` calls back to back and single synchronised calls (the median), the host clock around work that ends in a device
+synchronise.  Then tcar_rows_blend alone, device events around `iters` launches on the lists the call left, and its share of the one
+synchronised call.  A warm start that costs much more than update_items + similar_items has a problem in the blend or a
+synchronisation that should not exist."""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -124,6 +134,8 @@ ap.add_argument("--duplicates", type=float, default=0.0, help="T in (0, 1]: find
 ap.add_argument("--dup_dense", action="store_true", help="with --duplicates: also the worst case, every content row equal")
 ap.add_argument("--ragged", type=int, default=0, help="LMAX (1 .. 40): one ragged recommend beside one recommend per length bucket")
 ap.add_argument("--update", type=str, default="", help="comma-separated row counts U for update_items")
+ap.add_argument("--warm", type=str, default="", help="comma-separated row counts U for warm_start_items (with --donors K)")
+ap.add_argument("--donors", type=int, default=16, help="K: the donors of one warm-started row and the k of similar_items beside it (with --warm)")
 ap.add_argument("--scoring", type=str, default="bf16x3-mixed", help="scoring mode of the engine (f32 | bf16x3 | bf16x3-mixed | bf16)")
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
@@ -240,6 +252,64 @@ if ups:
                 print("N=%d %s round %d %s U=%d (%s): %.4f ms per call back to back, %.4f ms one synchronised call = 1 / %.0f of the rebuild"
                       % (N, a.scoring, rnd, uname, U, name, rate, one, (lp + first) / one))
         sys.stdout.flush()
+    eng.check_forks()
+    sys.exit(0)
+warms = [int(u) for u in a.warm.split(",") if u]
+if warms:
+    import ctypes as C_
+    if a.sharded:
+        sys.exit("--warm needs the whole catalog on one engine: not with --sharded")
+    g, rng = eng.geo, np.random.RandomState(9)
+    K = a.donors
+
+    def call_times(call):
+        """(ms per call of `iters` calls back to back, median ms of single synchronised calls)"""
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            call()
+        torch.cuda.synchronize()
+        rate = (time.perf_counter() - t0) / iters
+        one = []
+        for _ in range(min(iters, 50)):
+            t0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            one.append(time.perf_counter() - t0)
+        return rate * 1e3, float(np.median(one)) * 1e3
+
+    def blend_alone(U):
+        """ms of tcar_rows_blend alone, device events, on the lists and the staging rows the last warm start left"""
+        lib, st = eng.lib, eng._stream()
+        vp = lambda t: C_.c_void_p(t.data_ptr())
+        args = (U, K, g.N, g.H, vp(eng.sel_topk), vp(eng.sel_score), 0.0, vp(eng.E), g.ek, vp(eng.warm_rows), (g.H + 3) // 4 * 4,
+                vp(eng.warm_support), vp(eng.warm_wsum), st)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        for it in range(5 + iters):
+            if it == 5:
+                ev[0].record()
+            assert lib.tcar_rows_blend(*args) == 0
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / iters
+
+    for rnd in range(a.rounds):
+        for U in warms:
+            ids = rng.choice(N, U, replace=False)
+            rows = (rng.standard_normal((U, g.H)) * 0.002).astype(np.float32)
+            upd = call_times(lambda: eng.update_items(ids, item_rows=rows))
+            sim = call_times(lambda: eng.similar_items(ids, k=K))
+            warm = call_times(lambda: eng.warm_start_items(ids, k=K))
+            blend = blend_alone(U)
+            gathered = U * K * g.H * 4
+            print("N=%d %s round %d U=%d k=%d: warm_start_items %.4f ms back to back, %.4f ms one synchronised call; update_items(item "
+                  "rows from the host) %.4f / %.4f ms; similar_items(Q=U) %.4f / %.4f ms; their sum %.4f / %.4f ms; tcar_rows_blend alone "
+                  "%.4f ms = %.1f%% of the one call (%.1f GB/s of donor rows)"
+                  % (N, a.scoring, rnd, U, K, warm[0], warm[1], upd[0], upd[1], sim[0], sim[1], upd[0] + sim[0], upd[1] + sim[1], blend,
+                     100 * blend / warm[1], gathered / blend / 1e6))
+            sys.stdout.flush()
     eng.check_forks()
     sys.exit(0)
 cands = [int(c) for c in a.candidates.split(",") if c]
